@@ -23,7 +23,19 @@ library on the stream it launches on, and "cpu_baseline": the C oracle (a port o
 algorithm; the reference is Rust and cannot be built here) timed on ONE host core and on all of
 them (count printed) over bounded samples of the same workloads, results checked equal to the GPU's.
 
-Launch: python bench.py --gpus N --steps K --warmup W        (N > 1: starts its own N ranks)
+A plain run measures the primary workload only: set-up, `--warmup` steps, `--steps` timed steps, the JSON line
+(`ms_per_step` = milliseconds of one timed step; `roofline` comes from the HIP events of those same steps and
+the committed counter passes).  Everything else above -- the protein arm, the compare matrix, the host-input
+run, the CPU baselines, the union across ranks at N > 1 and the checks that go with them -- runs only with `--full`;
+without it those keys of the line are null.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the sketch its last timed step computed (the sorted
+hashes a caller of add_sequences_dev receives) as float64 .npy files, a fixed seeded sample of at most
+DUMP_SAMPLE hashes when the sketch is larger: retained.npy (the number of hashes in the sketch), mins.npy (the
+sampled hashes, in ascending order), mins_low16.npy (their low 16 bits, which float64 may round away).  The
+inputs are synthetic and seeded, so the same arguments give the same inputs on every run.
+
+Launch: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N > 1: starts its own N ranks)
    or:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -55,6 +67,8 @@ VALU_CYCLES = 2.0                  # ... a wave64 VALU instruction issues over 2
 MAX_CLOCK_HZ = 2.4e9               # ... max clock
 LDS_READ_B32_PEAK_TBS = 75.0       # ... LDS aggregate for ds_read_b32, every CU streaming
 CONTAMINANT = 1                    # the hash every signature of the one-component collection shares
+DUMP_SAMPLE = 1 << 21              # --dump-outputs: hashes written at most (two float64 arrays of 16 MB)
+DUMP_SEED = 0                      # ... seed of the sample drawn from a larger sketch
 
 
 def host_cores():
@@ -188,6 +202,18 @@ def run_workers(specs):
 TMP_DIRS = []          # scratch directories of the CPU-baseline workers; removed when the line has been printed
 
 
+def dump_outputs(out_dir, mins):
+    """--dump-outputs: the sketch of the last timed step (ascending uint64 hashes) as float64 .npy files in out_dir."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = mins.size
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        mins = mins[idx]
+    np.save(os.path.join(out_dir, "retained.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, "mins.npy"), mins.astype(np.float64))
+    np.save(os.path.join(out_dir, "mins_low16.npy"), (mins & np.uint64(0xFFFF)).astype(np.float64))
+
+
 def spawn_ranks(args, argv):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start N ranks as fresh child
     processes (this process has not touched the GPU), relay their output, exit with their code."""
@@ -208,12 +234,19 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--gb", type=float, default=10.0, help="GB of DNA per GPU (BASELINE config: 10)")
-    ap.add_argument("--compare-n", type=int, default=0, help="signatures in the matrix (0 = by --gpus)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the 1-core sketch sample (others scale with it)")
-    ap.add_argument("--no-compare", action="store_true")
-    ap.add_argument("--protein-gb", type=float, default=12.5, help="GB of DNA per GPU through the protein arm (configs[4]: 100 GB / 8 GPUs; 0 = skip)")
-    ap.add_argument("--host-gb", type=float, default=2.0, help="GB of the workload also timed from HOST memory (PCIe-inclusive; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the protein arm, the compare matrix, the host-input run, the CPU baselines and the union "
+                         "across ranks, with their checks (a plain run times the primary workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the sketch of the last timed step to DIR/*.npy (float64, a seeded sample when large)")
+    ap.add_argument("--compare-n", type=int, default=0, help="--full: signatures in the matrix (0 = by --gpus)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: budget of the 1-core sketch sample (others scale with it)")
+    ap.add_argument("--no-compare", action="store_true", help="--full: leave out the compare matrix")
+    ap.add_argument("--protein-gb", type=float, default=12.5, help="--full: GB of DNA per GPU through the protein arm (configs[4]: 100 GB / 8 GPUs; 0 = skip)")
+    ap.add_argument("--host-gb", type=float, default=2.0, help="--full: GB of the workload also timed from HOST memory (PCIe-inclusive; 0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
@@ -285,7 +318,7 @@ def main():
     # N > 1: the ranks' partial sketches united into ONE sketch on the device (one all-gather of the padded hash arrays +
     # rank-arithmetic unions, distributed.union_across_ranks) -- reported on its own, never part of `value`
     union = None
-    if world > 1:
+    if args.full and world > 1:
         from sourmash_rust_amd import distributed as D
         barrier()
         t0 = time.perf_counter()
@@ -301,10 +334,16 @@ def main():
                          "reference src/lib.rs:307-403).  Not part of `value`" % world}
         del uni
     retained = len(mh)          # the sketch is still in HBM here (DeviceSketch); bringing it to the
-    t1 = time.perf_counter()    # host is a separate, untimed step whose cost is reported below
-    host_mins = mh.mins_np()
-    to_host_ms = (time.perf_counter() - t1) * 1e3
-    assert host_mins.size == retained and bool((host_mins[1:] > host_mins[:-1]).all())
+    to_host_ms = None           # host is a separate, untimed step whose cost is reported below
+    if args.full or args.dump_outputs:
+        t1 = time.perf_counter()
+        host_mins = mh.mins_np()
+        to_host_ms = (time.perf_counter() - t1) * 1e3
+        if args.full:
+            assert host_mins.size == retained and bool((host_mins[1:] > host_mins[:-1]).all())
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, host_mins)
+        del host_mins
 
     dt = max_over_ranks(dt)
     value = world * kmers_per_step * args.steps / dt
@@ -360,7 +399,7 @@ def main():
 
     # ---------------------------------------------------------------- protein arm (configs[4], one rank's share)
     protein, pseq, poffsets = None, None, None
-    if args.protein_gb > 0:
+    if args.full and args.protein_gb > 0:
         pn_rec = max(1, int(round(args.protein_gb * 1e9 / REC_LEN)))
         ptotal = pn_rec * REC_LEN
         pseq = torch.empty(ptotal, dtype=torch.uint8, device="cuda")
@@ -439,7 +478,7 @@ def main():
     # ---------------------------------------------------------------- compare matrix (secondary)
     compare = None
     cmp_outs = {}
-    if not args.no_compare:
+    if args.full and not args.no_compare:
         from sourmash_rust_amd import distributed as D, matrix as MX
         # strong scaling: N fixed at 10 000 (configs[3]) whatever the world size; world 1 also runs configs[2]'s 1 000
         sizes = [args.compare_n] if args.compare_n else ([10000, 1000] if world == 1 else [10000])
@@ -610,7 +649,7 @@ def main():
 
     # ---------------------------------------------------------------- host input (PCIe-inclusive, reported beside value)
     host_input = None
-    if rank == 0 and world == 1 and args.host_gb > 0:
+    if args.full and rank == 0 and world == 1 and args.host_gb > 0:
         nh = min(int(args.host_gb * 1e9), total) // REC_LEN * REC_LEN
         host = seq[:nh].cpu().numpy()                     # pageable host memory, like a caller's buffer
         hoff = np.arange(nh // REC_LEN + 1, dtype=np.uint64) * np.uint64(REC_LEN)
@@ -637,7 +676,7 @@ def main():
 
     # ---------------------------------------------------------------- CPU baseline (rank 0, N=1 only)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cores = host_cores()
         scale = args.cpu_seconds / 10.0
 
@@ -734,7 +773,9 @@ def main():
             "config": {"workload": "sketch %.1f GB synthetic DNA per GPU, %d records x 1 MB, k=31, num=0, "
                                    "max_hash=%d (scaled=1000), force=true, inputs resident in HBM" % (total / 1e9, n_rec, MAX_HASH),
                        "retained_hashes": retained, "records_sharded_across_ranks": True,
-                       "result": "sorted distinct hashes left in HBM; copy to host (PCIe, not in value) took %.1f ms" % to_host_ms},
+                       "result": "sorted distinct hashes left in HBM" +
+                                 ("; copy to host (PCIe, not in value) took %.1f ms" % to_host_ms if to_host_ms is not None else "")},
+            "full": args.full,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": "k_dna_rolling<31,...>", "kernel_ms_avg": kern_ms, "launches_per_step": launches_per_step,

@@ -35,7 +35,7 @@ def _multi_gpu_env(world):
 def test_bench_two_ranks_sharing_the_gpu(pkg):
     env = _multi_gpu_env(2)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--full",
            "--gb", "0.2", "--protein-gb", "0.2", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0", "--compare-n", "601"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -68,7 +68,7 @@ def test_bench_gpus_2_with_no_launcher_around_it(pkg):
     env = _multi_gpu_env(2)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--gb", "0.1", "--protein-gb", "0.1", "--steps", "1", "--warmup", "0", "--compare-n", "300"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--full", "--gb", "0.1", "--protein-gb", "0.1", "--steps", "1", "--warmup", "0", "--compare-n", "300"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
