@@ -237,6 +237,11 @@ typedef struct SmhCompareStats {
   uint32_t prefetched_after_halving; /* ... tiles in which prefetched boundary crossings were used after such a rebuild */
 } SmhCompareStats;
 void smh_compare_last_stats(SmhCompareStats *out);
+/* 1 = the tiled kernel of the last block compare read the range masks ("Range masks"); 0 = it walked every range
+ * from the first on, or another route served the block.  Whether a dictionary carries masks is decided when it is built: one
+ * built under no_range_masks = 1 walks for its whole life, also under later default tunings.  (Kept out of SmhCompareStats,
+ * which has no size field.) */
+uint32_t smh_compare_last_range_masks(void);
 
 /* The library keeps its device workspace (candidate buffers, the six-frame residue buffer, sort
  * scratch) between calls and only ever grows it; a long-running process can hand the memory back

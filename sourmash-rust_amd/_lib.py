@@ -130,6 +130,7 @@ _SIGS = {
     "smh_pool_set_limit": (None, [C.c_uint64]),
     "smh_pool_bytes": (C.c_uint64, []),
     "smh_compare_last_stats": (None, [C.POINTER(SmhCompareStats)]),
+    "smh_compare_last_range_masks": (C.c_uint32, []),
     "smh_compare_get_tuning": (None, [C.POINTER(SmhCompareTuning)]),
     "smh_compare_set_tuning": (C.c_int, [C.POINTER(SmhCompareTuning)]),
     "smh_synth_dna_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),

@@ -416,6 +416,8 @@ struct PlanState {
   uint32_t halvings;             // pipelined kernel: stretches whose speculative span did not fit and was rebuilt, halved, with plain loads
   uint32_t pf_after_halving;     // ... tiles in which a table was built from PREFETCHED boundary crossings after such a rebuild
   uint32_t bad_tables;           // a segment that would end before it starts (never, unless a table was built from crossings of the wrong boundary)
+  uint32_t masks;                // tiled: the kernel reads the range masks (asked for, built, and k_mask_layout kept them: k_plan_geometry)
+  uint32_t lazy_ran;             // several owners: the lazy mask chain passed lazy_go in this call (k_mask_layout)
 };
 // Workgroups are dealt to the 8 XCDs round-robin.  A kernel that goes through the SORTED positions and touches arrays in
 // collection order (by origin) touches, at any time, one line per sketch -- consecutive elements of a sketch are ~n sorted
@@ -941,7 +943,8 @@ __global__ __launch_bounds__(64 * WPB, MINW) void k_compare_tiled_pf(TiledArgs a
   // range's upper boundary minus the matches; the first range in which that reaches the row's cut is the pair's.  Pass 2:
   // that ONE range is walked by the pair's lane alone, from the rank arrays (the staged stretch loop below is not entered
   // when the masks exist); pairs that never reach a cut are final as they are.
-  const bool use_masks = ka.masks != nullptr && ka.minfo->ok != 0;      // (uniform)
+  // (uniform; the plan's word -- asked for, built AND kept -- written by k_plan_geometry, an earlier launch: a scalar load)
+  const bool use_masks = ka.masks != nullptr && *as_constant(&ka.st->masks) != 0;
   uint32_t first_r = 0;                 // the first range the tile walks (R: none)
   uint32_t mtot[kRowsPerWave];          // matches over all ranges
   uint32_t nocut = 0;                   // bit q: the pair (my q-th row, my column) needs no walk
@@ -1702,7 +1705,7 @@ __global__ __launch_bounds__(256) void k_mask_max(const uint32_t* __restrict__ c
 }
 // per range: the words its busiest component needs (wn), the frequent words behind them, the offsets; and whether the masks
 // are worth building.  One workgroup; lane per range for the maximum over the components' counters.
-// (lazy_go: the plan walks tiles, the masks do not exist yet, and there are enough pairs that can share a hash for them to
+// (lazy_go: the plan walks tiles, the masks do not exist yet (DictState::masks_built), and there are enough pairs that can share a hash for them to
 // pay -- building them is two passes over ALL pooled hashes plus the masks themselves, whatever part of the matrix this owner
 // computes: ~0.35 ms at 20 M hashes, against ~0.35 ns saved per pair.  Measured on the 50-family collection: worth it for
 // one rank of two, a wash for one of four or eight.)
@@ -1712,10 +1715,11 @@ __device__ __forceinline__ bool lazy_go(const PlanState* st, const uint32_t* bui
 __global__ __launch_bounds__(1024) void k_mask_layout(const uint32_t* __restrict__ kmax, const uint32_t* __restrict__ fcnt,
                                                       const uint32_t* __restrict__ total, uint32_t R, uint32_t wmax,
                                                       uint32_t* __restrict__ wn, uint32_t* __restrict__ woff, MaskInfo* __restrict__ info,
-                                                      const PlanState* __restrict__ plan = nullptr, const uint32_t* __restrict__ built = nullptr,
+                                                      PlanState* __restrict__ plan = nullptr, const uint32_t* __restrict__ built = nullptr,
                                                       uint32_t n_lazy = 0) {
   __shared__ uint32_t wt[16], st[16];
   if (plan && !lazy_go(plan, built, n_lazy)) return;
+  if (plan && threadIdx.x == 0) plan->lazy_ran = 1;       // (the host tries again in a later call if this chain did not run)
   const uint32_t per = (R + 1023) / 1024, r0 = min(threadIdx.x * per, R), r1 = min(r0 + per, R);
   __shared__ uint32_t wide;
   if (threadIdx.x == 0) wide = 0;
@@ -1794,6 +1798,8 @@ struct DictState {
   uint32_t nfreq;              // frequent hashes set aside, over all slices (<= kMaxFreq)
   uint32_t part_built;         // the range partition table exists (k_partition, k_plan_geometry)
   uint32_t overflow;           // one owner: the four-pass sort gave up (RangeState::overflow) -- the dictionary is void and is built again
+  uint32_t masks_built;        // the range masks and partT were written (k_build_masks ran and MaskInfo::ok: k_plan_geometry); gates
+                               // k_build_masks and the lazy chain -- part_built says nothing about them
   uint32_t rbase[64];          // dense rank of the first hash of slice g
   uint64_t freq_hash[64];
 };
@@ -1805,7 +1811,7 @@ __global__ __launch_bounds__(64) void k_slice_header(const RangeState* __restric
   if (k == 0) { h->n_elems = n; h->nruns = rs->nruns; h->nfreq = rs->nfreq; h->id_space = sparse_ids ? n : rs->nruns; }
   h->freq_hash[k] = f;
   if (ds) {
-    if (k == 0) { ds->nruns = rs->nruns; ds->nfreq = rs->nfreq; ds->part_built = 0; ds->overflow = rs->overflow; }
+    if (k == 0) { ds->nruns = rs->nruns; ds->nfreq = rs->nfreq; ds->part_built = 0; ds->overflow = rs->overflow; ds->masks_built = 0; }
     ds->rbase[k] = 0;
     ds->freq_hash[k] = f;
   }
@@ -1823,6 +1829,7 @@ __global__ void k_dict_state(const uint8_t* __restrict__ gathered, uint64_t shar
   ds->nfreq = nf;
   ds->part_built = 0;
   ds->overflow = 0;
+  ds->masks_built = 0;
 }
 // ---- the same bits from an ASSEMBLED dictionary (built by `world` owners, each sorting one slice of hash space): there are no
 // runs to look at -- every owner has the ranks of all elements, the roots and the crossings, and builds the masks of all
@@ -2381,8 +2388,18 @@ __device__ __host__ inline TileShape tile_shape_for(uint64_t count16, uint32_t f
   if (17 * count16 < 5ull * fill_tiles) return {4u, 1u};
   return {8u, 1u};
 }
-__global__ void k_plan_geometry(PlanState* st, uint32_t forced_rpw, uint32_t forced_pf, uint32_t fill_tiles, uint32_t* part_built) {
-  if (!st->skip_tiled) *part_built = 1;   // k_partition ran just before this launch (same stream)
+// (mask_build: 0 no k_build_masks in this call; 1 launched behind the route, gated on skip_tiled like k_partition; 2 launched
+// before the route was known -- early_tables -- so it ran whatever the plan decided.  minfo: null when neither is asked for.)
+__global__ void k_plan_geometry(PlanState* st, uint32_t forced_rpw, uint32_t forced_pf, uint32_t fill_tiles, DictState* ds,
+                                const MaskInfo* minfo, uint32_t mask_build, uint32_t want_masks) {
+  // one owner, and the four-pass sort gave up: the dictionary is void and is built again where the call synchronises -- no
+  // tile walks it, and nothing of it is recorded as built
+  if (ds->overflow) st->skip_tiled = 1;
+  if (!st->skip_tiled) ds->part_built = 1;   // k_partition ran just before this launch (same stream)
+  const uint32_t ok = minfo ? minfo->ok : 0u;
+  if (!ds->overflow && ok && (mask_build == 2 || (mask_build == 1 && !st->skip_tiled))) ds->masks_built = 1;
+  // the tiled kernels read the masks on this word alone: never unless they were written for this dictionary
+  st->masks = (want_masks && !st->skip_tiled && ds->masks_built && ok) ? 1u : 0u;
   TileShape sh = {forced_rpw, forced_pf};
   if (!forced_rpw) sh = tile_shape_for(st->count16, fill_tiles);
   st->rpw = sh.rpw; st->pf = sh.pf;
@@ -2948,8 +2965,9 @@ void collection_compare(CollectionDict* Dp, uint32_t row_lo, uint32_t row_hi, ui
 
   // ---- a large block of one owner's dictionary: the partition table and the masks (both the dictionary's, built once) are
   // made NOW, beside the fill -- they need nothing of the plan, and behind it they were 0.16 ms on the way to the first tile
-  // (st->skip_tiled is still 0 here: the gate they share with the plan's route is open; part_built says "already there")
+  // (st->skip_tiled is still 0 here: the gate they share with the plan's route is open; part_built / masks_built say "already there")
   const bool early_tables = fill_pending && tune.route != kRouteComponents && D.world == 1 && D.finished;
+  uint32_t mask_build = 0;              // k_plan_geometry: whether (and how) k_build_masks was launched in this call
   if (early_tables) {
     DictState* ds = D.dstate.as<DictState>();
     const uint32_t R = D.R;
@@ -2960,7 +2978,8 @@ void collection_compare(CollectionDict* Dp, uint32_t row_lo, uint32_t row_hi, ui
       D.partT.ensure((size_t)D.n * (R + 1) * 4);
       hipLaunchKernelGGL(k_build_masks, dim3((unsigned)(((uint64_t)D.n * (R + 1) + 255) / 256)), dim3(256), 0, s, D.part.as<uint32_t>(), off,
                          D.sid.as<uint16_t>(), D.sb.as<uint32_t>(), D.woff.as<uint32_t>(), D.minfo.as<MaskInfo>(), D.n, R,
-                         D.masks.as<unsigned long long>(), D.partT.as<uint32_t>(), &st->skip_tiled, &ds->part_built);
+                         D.masks.as<unsigned long long>(), D.partT.as<uint32_t>(), &st->skip_tiled, &ds->masks_built);
+      mask_build = 2;
     }
   }
 
@@ -3036,6 +3055,7 @@ void collection_compare(CollectionDict* Dp, uint32_t row_lo, uint32_t row_hi, ui
   // ---- tiled kernel: tile list, launch
   const int wpb = ex.wpb, minw = ex.minw;
   uint32_t tiles_cap = 0;
+  bool lazy_launched = false;           // the lazy mask chain of a sliced dictionary was queued in this call
   if (tune.route != kRouteComponents) {
     const uint32_t R = D.R;
     TileTest tt;
@@ -3064,7 +3084,9 @@ void collection_compare(CollectionDict* Dp, uint32_t row_lo, uint32_t row_hi, ui
     const bool lazy_masks = D.world > 1 && D.lazy_ready && tune.no_range_masks == 0 && !ex.no_masks;
     const bool use_masks = (D.has_masks || lazy_masks) && tune.no_range_masks == 0 && !ex.no_masks;
     if (lazy_masks && !D.lazy_tried) {
-      // (once per dictionary: a later block compare finds the masks, or -- the plan of this one skipped the tiles -- walks)
+      lazy_launched = true;
+      // (once per dictionary: a later block compare finds the masks -- or, if lazy_go held this one back (the plan skipped the
+      // tiles, or too few pairs share a hash), tries again: PlanState::lazy_ran, read where the call synchronises)
       D.lazy_tried = true;
       const size_t ids = (size_t)D.total + 1;                    // (ranks are below the number of pooled hashes)
       T.mv1.ensure(ids * 4);
@@ -3079,22 +3101,24 @@ void collection_compare(CollectionDict* Dp, uint32_t row_lo, uint32_t row_hi, ui
       const uint32_t nt = (uint32_t)D.total;
       const unsigned gb = (unsigned)((D.total + 255) / 256);
       hipLaunchKernelGGL(k_claim_bits, dim3(gb), dim3(256), 0, s, D.rank_ptr, D.hashes, off, D.part.as<uint32_t>(), D.root_ptr, ds, D.n, R,
-                         nt, D.sid.as<uint16_t>(), T.mv1.as<uint32_t>(), cnt, fcnt, D.split ? 1u : 0u, st, &ds->part_built);
+                         nt, D.sid.as<uint16_t>(), T.mv1.as<uint32_t>(), cnt, fcnt, D.split ? 1u : 0u, st, &ds->masks_built);
       hipLaunchKernelGGL(k_elem_bits, dim3(gb), dim3(256), 0, s, D.rank_ptr, nt, T.mv1.as<uint32_t>(), D.sid.as<uint16_t>(), st,
-                         &ds->part_built);
+                         &ds->masks_built);
       hipLaunchKernelGGL(k_mask_max_lazy, dim3((unsigned)(((uint64_t)D.n * R + 255) / 256)), dim3(256), 0, s, cnt, (uint64_t)D.n * R, R, kmax,
-                         total, st, &ds->part_built, nt);
+                         total, st, &ds->masks_built, nt);
       hipLaunchKernelGGL(k_mask_layout, dim3(1), dim3(1024), 0, s, kmax, fcnt, total, R, D.mask_words_max, D.sb.as<uint32_t>(),
-                         D.woff.as<uint32_t>(), D.minfo.as<MaskInfo>(), st, &ds->part_built, nt);
+                         D.woff.as<uint32_t>(), D.minfo.as<MaskInfo>(), st, &ds->masks_built, nt);
     }
     if (use_masks && !(early_tables && D.has_masks)) {
       D.masks.ensure((size_t)D.n * (D.mask_words_max + 3) * 8);      // (+3 words: the kernel reads three words per range whatever it has)
       D.partT.ensure((size_t)D.n * (R + 1) * 4);
       hipLaunchKernelGGL(k_build_masks, dim3((unsigned)(((uint64_t)D.n * (R + 1) + 255) / 256)), dim3(256), 0, s, D.part.as<uint32_t>(), off,
                          D.sid.as<uint16_t>(), D.sb.as<uint32_t>(), D.woff.as<uint32_t>(), D.minfo.as<MaskInfo>(), D.n, R,
-                         D.masks.as<unsigned long long>(), D.partT.as<uint32_t>(), &st->skip_tiled, &ds->part_built);
+                         D.masks.as<unsigned long long>(), D.partT.as<uint32_t>(), &st->skip_tiled, &ds->masks_built);
+      mask_build = 1;
     }
-    hipLaunchKernelGGL(k_plan_geometry, dim3(1), dim3(1), 0, s, st, forced_rpw, forced_pf, fill_tiles, &ds->part_built);
+    hipLaunchKernelGGL(k_plan_geometry, dim3(1), dim3(1), 0, s, st, forced_rpw, forced_pf, fill_tiles, ds,
+                       (mask_build || use_masks) ? D.minfo.as<MaskInfo>() : (const MaskInfo*)nullptr, mask_build, use_masks ? 1u : 0u);
     // the list: at 16 rows per tile at most every tile; shorter tiles are only chosen when fewer than
     // fill_tiles 16-row tiles are flagged (each splits into at most 4)
     const uint32_t rows_min = (forced_rpw ? forced_rpw : 1u) * (uint32_t)wpb;
@@ -3190,6 +3214,7 @@ void collection_compare(CollectionDict* Dp, uint32_t row_lo, uint32_t row_hi, ui
   HIP_CHECK(hipMemcpyAsync(&h, st, sizeof(PlanState), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(hd, D.dstate.ptr, 16, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
+  if (lazy_launched && !h.lazy_ran) D.lazy_tried = false;       // (lazy_go held the chain back: a later compare may build them)
   if (hd[3] && D.world == 1 && !D.force_radix) {
     // the dictionary was void (keys that tie in the sorted bits were left out of order: equal hashes may carry different
     // ranks): what the kernels compared was rubbish, though nothing of it was used as an address.  Again, with the full sort.
@@ -3213,6 +3238,7 @@ void collection_compare(CollectionDict* Dp, uint32_t row_lo, uint32_t row_hi, ui
     rec.span_halvings = h.halvings;
     rec.prefetched_after_halving = h.pf_after_halving;
     if (h.bad_tables) throw_internal("compare block: a range table of the tiled kernel was inconsistent (segment end before its start)");
+    rec.range_masks = h.masks;
   }
   rec.frequent_hashes = D.split ? hd[1] : 0;
   set_stats(rec);

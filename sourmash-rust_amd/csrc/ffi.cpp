@@ -969,6 +969,7 @@ void smh_compare_last_stats(SmhCompareStats* out) {
   out->span_halvings = st.span_halvings;
   out->prefetched_after_halving = st.prefetched_after_halving;
 }
+uint32_t smh_compare_last_range_masks(void) { return smh::compare_last_stats().range_masks; }
 void smh_compare_get_tuning(SmhCompareTuning* out) {
   if (!out) return;
   const smh::CompareTuning t = smh::compare_get_tuning();

@@ -203,6 +203,7 @@ struct CompareStats {                      // of the last block compare
   uint32_t pipelined = 0;                  // tiled: k_compare_tiled_pf walked the tiles
   uint32_t span_halvings = 0;              // pipelined kernel: stretches rebuilt with a halved span (their speculative span did not fit LDS)
   uint32_t prefetched_after_halving = 0;   // ... tiles in which prefetched crossings were used after such a rebuild
+  uint32_t range_masks = 0;                // tiled: the kernel read the range masks (not in SmhCompareStats: smh_compare_last_range_masks)
 };
 void compare_set_tuning(const CompareTuning& t);
 CompareTuning compare_get_tuning();

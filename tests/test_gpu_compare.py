@@ -40,6 +40,8 @@ def routed(pkg, tune, expect, fn):
         assert st["route"] == expect, st
         if tune.get("visit_all_tiles") and not tune.get("use_symmetry", True):
             assert st["tiles_visited"] == st["tiles_total"], st
+    if not tune.get("range_masks", True) or st["route"] != "tiled":
+        assert st["range_masks"] == 0, (tune, st)          # (smh_compare_last_range_masks: the walk from the first range on)
     return out
 
 
@@ -276,15 +278,28 @@ def _profile_count(pkg, name):
 @pytest.mark.parametrize("num", [0, 150, 400])
 def test_range_masks_with_many_words_per_range_and_cuts_near_a_sketch_end(num, pkg, coracle):
     """The corners of the masked tiled kernel ("Range masks"): (i) components whose sketches draw from a pool
-    twenty times their length -- hundreds of shared hashes per range, so a range's words exceed the three the kernel keeps
-    in registers (the tail loop); (ii) SHORT sketches next to long ones, cut by `num` close to their last element, so that
+    twelve times their length -- hundreds of shared hashes per range, so a range's words (up to five) exceed the three the
+    kernel keeps in registers (the tail loop), yet the table stays within its budget: the masks are READ (range_masks);
+    (ii) SHORT sketches next to long ones, cut by `num` close to their last element, so that
     the four-ranks-at-a-time windows of the cut-range walk run past the end of a sketch (sentinels by hand) and past the end
     of the rank array (the padding); (iii) two components in every 64-column tile plus unrelated sketches (per-component bits:
     the short forms must not be taken); (iv) the all-vs-all block with its self pairs.  Every pair against the oracle, with
     masks and without, symmetric and as a rows x columns block."""
+    _range_mask_corners(num, 4500, True, pkg, coracle)
+
+
+@pytest.mark.parametrize("num", [0, 150, 400])
+def test_range_masks_dropped_when_the_table_exceeds_its_budget(num, pkg, coracle):
+    """The same corners with pools twenty times a sketch's length: ~7 words per range, more than the table's budget
+    (2 R + 64 words) -- k_mask_layout drops the masks and the tiled kernel walks from the first range on (range_masks 0),
+    with the oracle's numbers."""
+    _range_mask_corners(num, 8000, False, pkg, coracle)
+
+
+def _range_mask_corners(num, pool_n, masks, pkg, coracle):
     import torch
     rng = np.random.RandomState(11 + num)
-    pools = [np.unique(rng.randint(0, 1 << 62, size=9000, dtype=np.int64).astype(np.uint64))[:8000] for _ in range(2)]
+    pools = [np.unique(rng.randint(0, 1 << 62, size=pool_n + 1000, dtype=np.int64).astype(np.uint64))[:pool_n] for _ in range(2)]
     sk = []
     for i in range(150):
         pool = pools[i % 2]
@@ -312,7 +327,12 @@ def test_range_masks_with_many_words_per_range_and_cuts_near_a_sketch_end(num, p
                  dict(route="tiled", visit_all_tiles=True), dict(route="tiled", dictionary="full"), dict()):
         with pkg.matrix.tuning(**tune):
             out = pkg.matrix.compare_block_dev(t, off, t, off, num, want=("jaccard", "common", "size", "count_common"))
+            st = pkg.matrix.last_stats()
             blk = pkg.matrix.compare_block_dev(tr, roff, t, off, num, want=("jaccard", "common", "count_common"))
+            stb = pkg.matrix.last_stats()
+        for s in (st, stb):
+            on = masks and tune.get("range_masks", True) and s["route"] == "tiled"
+            assert s["range_masks"] == (1 if on else 0), (tune, s)
         assert (out["jaccard"].cpu().numpy() == ojac).all(), tune
         assert (out["common"].cpu().numpy().view(np.uint64) == ocommon).all(), tune
         assert (out["size"].cpu().numpy().view(np.uint64) == osize).all(), tune
@@ -447,6 +467,10 @@ def _full_size_matrix_check(pkg, coracle, n, seed, sample_rows, tunes):
         for tune, expect in tunes:
             out = routed(pkg, tune, expect, lambda: pkg.matrix.compare_block_dev(t, off, t, off, 2000, want=("jaccard", "common", "size")))
             st = pkg.matrix.last_stats()
+            # the masked kernel runs on these shapes -- except with ONE component (the contaminant not set aside), whose
+            # shared hashes need ~37 words per range, far past the table's budget: dropped, walked
+            if st["route"] == "tiled" and tune.get("range_masks", True):
+                assert st["range_masks"] == (0 if contaminated and not tune.get("split_frequent", True) else 1), (contaminated, tune, st)
             if contaminated and st["route"] == "tiled" and not tune.get("split_frequent", True):
                 assert st["tiles_visited"] * 2 >= st["tiles_total"], st        # one component: (the upper half of) every tile
             if contaminated and tune.get("split_frequent", True):

@@ -129,8 +129,9 @@ def test_c4_dense_matrix_on_four_simulated_ranks(pkg, coracle):
         return ms.value
 
     single = pkg.matrix.compare_block_dev(t, off, t, off, num, want=("jaccard",))["jaccard"]      # warm-up + reference
-    # (the walked work is compared walk for walk: a single owner's dictionary also carries range masks, which start every
-    # pair's walk at its cut -- a sliced dictionary does not yet -- so they are switched off for the timing)
+    # (the walked work is compared walk for walk: a single owner's dictionary carries range masks from its build, a sliced
+    # one builds them with the first block compare whose plan walks enough pairs -- lazy_go -- so the timing switches them
+    # off on both sides; the masked sliced matrices are checked below)
     with pkg.matrix.tuning(range_masks=False):
         L.smh_profile_reset(); L.smh_profile_enable(1)
         nomask = pkg.matrix.compare_block_dev(t, off, t, off, num, want=("jaccard",))["jaccard"]
@@ -151,6 +152,23 @@ def test_c4_dense_matrix_on_four_simulated_ranks(pkg, coracle):
     # boundary are walked by both sides)
     print("tiled kernel: 1 rank %.2f ms, 4 ranks summed %.2f ms" % (one, four))
     assert four <= 1.3 * one, (one, four)
+    # with the masks (default tuning): every rank's slice builds them (k_claim_bits / k_elem_bits / k_mask_max_lazy) and its
+    # tiled kernel reads them; the row blocks equal the single-rank matrix
+    from sourmash_rust_amd import matrix as MX
+    colls = [MX.Collection(t, off, world, r) for r in range(world)]
+    gathered = torch.empty(world * colls[0].share_bytes, dtype=torch.uint8, device="cuda")
+    for r, c in enumerate(colls):
+        c.share_to(gathered[r * c.share_bytes:(r + 1) * c.share_bytes])
+    for c in colls:
+        c.finish(gathered)
+    for r, c in enumerate(colls):
+        lo, hi, _ = D.shard_range(n, world, r)
+        blk = c.compare(lo, hi, num, want=("jaccard",))["jaccard"]
+        st = pkg.matrix.last_stats()
+        assert st["route"] == "tiled" and st["range_masks"] == 1, (r, st)
+        assert bool((blk == single[lo:hi]).all()), r
+        del blk
+        c.close()
 
 
 @pytest.mark.parametrize("world", [1, 3])
