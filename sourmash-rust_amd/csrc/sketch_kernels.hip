@@ -275,8 +275,39 @@ __device__ __forceinline__ uint64_t open_finish(W2 a, W2 b) {
   a.lo ^= a.hi >> 1; b.lo ^= b.hi >> 1;
   return ((((uint64_t)a.hi << 32) | a.lo) + (((uint64_t)b.hi << 32) | b.lo));
 }
+// a + b as ONE v_lshl_add_u64 that leaves both operands intact (w2_add hides its operands behind an empty asm that
+// "modifies" them, which costs a v_mov_b64 when an operand is still needed afterwards)
+__device__ __forceinline__ W2 w2_add_keep(W2 a, W2 b) {
+  uint64_t r;
+  asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(r) : "v"(((uint64_t)a.hi << 32) | a.lo), "v"(((uint64_t)b.hi << 32) | b.lo));
+  return w2_split(r);
+}
+// The DNA kernel stops one multiply earlier than w2_fmix_open: ka = w2_fmix_pre(h1), kb = w2_fmix_pre(h2), and
+// a = ka * C, b = kb * C with C = fmix's second constant.  The filter needs only a.hi + b.hi + 1, and the high dword
+// of x * C is mul_hi(x.lo, C.lo) + x.lo * C.hi + x.hi * C.lo (mod 2^32): the four cross terms chain through the
+// addends of four v_mad_u64_u32 (only the low dword of each is used; the first addend is the + 1), the two mul_hi
+// and the chain meet in one v_add3.  Seven instructions, against the six mads, two adds and the v_add3 of two whole
+// multiplies and open_may_pass.  The products' low dwords are only formed for the rare window that may pass
+// (open_full).
+constexpr uint64_t kFmixC2 = 0xc4ceb9fe1a85ec53ULL;
+__device__ __forceinline__ W2 w2_fmix_pre(W2 k) {
+  k.lo ^= k.hi >> 1;                                   // k ^= k >> 33
+  k = w2_mul(k, 0xff51afd7ed558ccdULL);
+  k.lo ^= k.hi >> 1;
+  return k;
+}
+__device__ __forceinline__ uint32_t open_hi_sum1(W2 ka, W2 kb) {   // == a.hi + b.hi + 1 (mod 2^32)
+  const uint32_t cl = (uint32_t)kFmixC2, ch = (uint32_t)(kFmixC2 >> 32);
+  uint64_t s0, s1, s2, s3, cy;
+  asm("v_mad_u64_u32 %0, %1, %2, %3, 1" : "=v"(s0), "=s"(cy) : "v"(ka.hi), "s"(cl));
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(s1), "=s"(cy) : "v"(ka.lo), "s"(ch), "v"(s0));
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(s2), "=s"(cy) : "v"(kb.hi), "s"(cl), "v"(s1));
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(s3), "=s"(cy) : "v"(kb.lo), "s"(ch), "v"(s2));
+  return (uint32_t)s3 + __umulhi(ka.lo, cl) + __umulhi(kb.lo, cl);
+}
+__device__ __forceinline__ uint64_t open_full(W2 ka, W2 kb) { return open_finish(w2_mul(ka, kFmixC2), w2_mul(kb, kFmixC2)); }
 // murmur64 from premultiplied words: M[w] = word_w * (w even ? c1 : c2)
-// The digest is left OPEN: (a, b) with h = open_finish(a, b).
+// The digest is left OPEN one multiply early: (ka, kb) with h = open_full(ka, kb), filtered by open_hi_sum1.
 template <int L>
 __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], int K, uint64_t seed, W2 seedv, W2& a, W2& b) {
   W2 h1 = seedv, h2 = seedv;                            // (seedv: the seed's halves in vector registers, see k_dna_rolling)
@@ -289,7 +320,7 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], int K, uin
       if (blk == 0) h1 = w2_mul5_add(w2_rotl(h1, 27), seed * 5 + 0x52dce729u);
       else h1 = w2_mul5_add(w2_add(w2_rotl(h1, 27), h2), 0x52dce729u);
       h2 = w2_xor(h2, w2_mul(w2_rotl(M[2 * blk + 1], 33), kC1));    // rest of mix_k2
-      h2 = w2_mul5_add(w2_add(w2_rotl(h2, 31), h1), 0x38495ab5u);
+      h2 = w2_mul5_add(w2_add_keep(w2_rotl(h2, 31), h1), 0x38495ab5u);
     } else if (blk == nblocks) {
       if (tail > 8) h2 = w2_xor(h2, w2_mul(w2_rotl(M[2 * blk + 1], 33), kC1));
       if (tail > 0) h1 = w2_xor(h1, w2_mul(w2_rotl(M[2 * blk], 31), kC2));
@@ -297,7 +328,7 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], int K, uin
   }
   h1.lo ^= (uint32_t)K; h2.lo ^= (uint32_t)K;          // ^= len (K <= 128)
   w2_cross_add(h1, h2);
-  a = w2_fmix_open(h1); b = w2_fmix_open(h2);         // first word of the digest = open_finish(a, b)
+  a = w2_fmix_pre(h1); b = w2_fmix_pre(h2);           // first word of the digest = open_full(a, b)
 }
 
 // KT > 0: ksize fixed at compile time; KT == 0: any ksize the limb count allows, at run time.
@@ -501,6 +532,15 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
     uint32_t cf[L], fle[L];
 #pragma unroll
     for (int i = 0; i < L; i++) { cf[i] = 0; fle[i] = 0; }
+    // k = 31, packed tile: the windows are not rolled base by base but taken once per base from state kept per GROUP,
+    // with one funnel shift (v_alignbit) per limb.  fa = the forward window before the group, with the group's first
+    // code in its spare top bits 62..63, so that {w >> 2, fa} is the forward stream and the window ending at base q of
+    // the group is that stream >> 2(q+1).  cs = the complement window before the group; wr = the complements of the
+    // quad's 16 codes in reverse order (base j of the quad in bits 30-2j), moved up 8 bits per group, so that the window
+    // ending at base q is {cs, wr} << 2(q+1).  Per base: four v_alignbit and two masks, against two v_alignbit, two
+    // v_and_or and five plain shifts/masks for rolling both windows one base at a time.
+    constexpr bool kRoll31 = PK && L == 2 && KT == 31;
+    uint32_t fa0 = 0, fa1 = 0, cs0 = 0, cs1 = 0, wr = 0;
 
     // one group of four bases; hashing = false for the warm-up groups
     auto group = [&](uint32_t i0, auto hashing) {
@@ -513,6 +553,11 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
           w = __builtin_amdgcn_alignbit(pnxt, pcur, sh2);
           pcur = pnxt;
           wc = ~w;
+          if (kRoll31) {
+            fa1 |= w << 30;                                          // (the last group of a quad left those bits zero)
+            const uint32_t r = __builtin_bitreverse32(w);            // digits reversed, each digit's two bits swapped
+            wr = ~(((r >> 1) & 0x55555555u) | ((r << 1) & 0xaaaaaaaau));
+          }
         }
       } else {
         const uint32_t xn = xu + i0 + 4;                             // uniform: byte index of the next dword
@@ -579,6 +624,15 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
           const int bb = g0b + q;
           const uint32_t code = PK ? (w >> (2 * bb)) & 3u : (code4 >> (8 * bb)) & 3u;
           const uint32_t ccode = PK ? (wc >> (2 * bb)) & 3u : (ccode4 >> (8 * bb)) & 3u;
+          if (kRoll31) {
+            // (L == 2: limb 0 needs no mask; the shift amounts are constants)
+            const uint32_t fhu = __builtin_amdgcn_alignbit(w >> 2, fa1, 2 * bb + 2);   // top bits: the next base
+            fle[0] = __builtin_amdgcn_alignbit(fa1, fa0, 2 * bb + 2);
+            fle[L - 1] = fhu & MASK[L - 1];
+            cf[0] = __builtin_amdgcn_alignbit(cs0, wr, 30 - 2 * bb);
+            cf[L - 1] = __builtin_amdgcn_alignbit(cs1, cs0, 30 - 2 * bb) & MASK[L - 1];
+            if (bb == 3) { fa0 = fle[0]; fa1 = fhu; cs0 = cf[0]; cs1 = cf[L - 1]; }
+          } else {
           // cf = ((cf << 2) | (3 - code)) & MASK ; fle = (fle >> 2) | code << (2K-2)   (limb-wise)
 #pragma unroll
           for (int li = L - 1; li > 0; li--) cf[li] = __builtin_amdgcn_alignbit(cf[li], cf[li - 1], 30) & MASK[li];
@@ -589,6 +643,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
 #pragma unroll
           for (int li = 0; li < L; li++)
             if (li == top_limb) fle[li] |= code << top_sh;
+          }
           if (kHash) {
             // canonical strand: kmer < rc  <=>  fle < cf (see above), decided from the top limb down
             bool fwd = false;
@@ -606,7 +661,10 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
             for (int li = 0; li < L; li++) X[q][li] = fwd ? fle[li] : cf[li];  // chosen strand, first base low
           }
         }
-        if (kHash && i0 + g0b + HB >= (uint32_t)K) {  // uniform: some window of this block is complete
+        // uniform: some window of this block is complete, and some window of it ends inside a full run (windows end at
+        // bases K-1 .. R+K-2; the last group of four reaches past that by (R+K-1) mod 4 bases, whose windows belong to
+        // no lane and were hashed only to be masked out)
+        if (kHash && i0 + g0b + HB >= (uint32_t)K && i0 + g0b < R + (uint32_t)K - 1) {
           W2 ha[HB], hb[HB];
 #pragma unroll
           for (int q = 0; q < HB; q++) {
@@ -642,16 +700,17 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
           }
 #pragma unroll
           for (int q = 0; q < HB; q++)
-            if (open_may_pass(ha[q], hb[q], PR ? open_thr(tq[g0b + q]) : thr_hi1)) {   // ~1 in `scaled` windows gets here
+            if (open_hi_sum1(ha[q], hb[q]) <= (PR ? open_thr(tq[g0b + q]) : thr_hi1)) {   // ~1 in `scaled` windows gets here
               uint32_t om = okmask;
               asm volatile("" : "+v"(om));                  // keeps the mask test inside this rare block
-              const uint64_t h = open_finish(ha[q], hb[q]);
+              const uint64_t h = open_full(ha[q], hb[q]);
               if (h <= (PR ? tq[g0b + q] : thr) && ((om >> (g0b + q)) & 1u))
                 stage_emit(stage, sink, h, hp.pos_base + p0 + (i0 + g0b + q + 1 - (uint32_t)K));
             }
         }
       }
       if (PK) { w >>= 8; wc >>= 8; }
+      if (kRoll31) wr <<= 8;
     };
 
     set_clean_window(true, 0);
