@@ -198,8 +198,22 @@ __device__ __forceinline__ uint32_t upper(uint32_t c) { return (c >= 'a' && c <=
 // One copy of the tables per workgroup: replicas (per lane parity ... per 16 lanes) were measured
 // and never paid (1, 2: 37.8 ms; 4, 8: 39.7; 16: 50.5 per 10 GB) -- with one copy the entry address
 // is (digits << 3) plus an immediate, two full-rate instructions per group.
+//
+// Folded tables (packed tile).  Of a word's product M = W*c, the low dword m = a.lo comes from the low half's entry a
+// alone, and the high dword is S = a.hi + B (B: the low dword of the high half's entry).  The rest of murmur's word mix
+// is linear in S once m is fixed, so the part that depends on m alone is precomputed per entry:
+//   k2 words (x c2, rotl 33, x c1):  rotl(M, 33) = 2S + T'(m), T'(m) = (m >> 31) | (m mod 2^31) << 33,
+//                                    mixed = S * (2 c1) + T2(m),  T2 = T'(m) * c1
+//   k1 words (x c1, rotl 31, x c2):  rotl(M, 31) = (S >> 1) + m * 2^31 + (S & 1) * 2^63, and c2 is odd:
+//                                    mixed = (S >> 1) * c2 + T1(m) + (S << 63),  T1 = m * 2^31 * c2
+// (all mod 2^64).  A low-half entry is {T, a.hi, 0} in 16 bytes, one ds_read_b128; the high halves read the packed low
+// dwords as before.  The mix of a word is then one v_mad_u64_u32, one v_mul_lo_u32 and one add (k1: plus a shift and
+// the top bit), instead of a 64-bit rotate (two v_alignbit), three v_mad_u64_u32 and an add.  The byte tile keeps the
+// plain product tables: its 64 KiB tile leaves no room for two workgroups per CU with the larger ones.
 constexpr int kLutEntries = 256 + 256 + 64 + 1;              // P1, P2, partial group, one zero entry (groups past the k-mer)
 constexpr int kLutDwords = kLutEntries * 3;                  // u64 entries (4.5 KiB), then their low dwords once more, packed
+constexpr int kLutDwordsFold = kLutEntries * 5;              // folded: 16-byte entries (9 KiB), then the packed low dwords
+constexpr uint64_t kC1x2 = kC1 * 2;                          // (mod 2^64)
 
 // The hash runs on explicit 32-bit halves.  Issue rates on gfx950 (tools/instr_rate.hip,
 // profiles/r01_instr_rates.txt): two-operand VALU forms ~100 lanes/clk/CU, everything with three
@@ -306,24 +320,51 @@ __device__ __forceinline__ uint32_t open_hi_sum1(W2 ka, W2 kb) {   // == a.hi + 
   return (uint32_t)s3 + __umulhi(ka.lo, cl) + __umulhi(kb.lo, cl);
 }
 __device__ __forceinline__ uint64_t open_full(W2 ka, W2 kb) { return open_finish(w2_mul(ka, kFmixC2), w2_mul(kb, kFmixC2)); }
-// murmur64 from premultiplied words: M[w] = word_w * (w even ? c1 : c2)
+// The rest of a word's mix from a folded entry (see kLutDwordsFold): T = T1 or T2 of the low half, S = a.hi + B.
+__device__ __forceinline__ W2 mix_k1_fold(uint32_t S, W2 T) {   // (S >> 1) * c2 + T1 + (S << 63)
+  const uint32_t cl = (uint32_t)kC2, ch = (uint32_t)(kC2 >> 32), s1 = S >> 1;
+  uint64_t p, cy;
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(p), "=s"(cy) : "v"(s1), "s"(cl), "v"(((uint64_t)T.hi << 32) | T.lo));
+  uint32_t hi, top;
+  asm("v_add_u32 %0, %1, %2" : "=v"(hi) : "v"((uint32_t)(p >> 32)), "v"(s1 * ch));
+  asm("v_lshl_add_u32 %0, %1, 31, %2" : "=v"(top) : "v"(S), "v"(hi));
+  return {(uint32_t)p, top};
+}
+__device__ __forceinline__ W2 mix_k2_fold(uint32_t S, W2 T) {   // S * (2 c1) + T2
+  const uint32_t cl = (uint32_t)kC1x2, ch = (uint32_t)(kC1x2 >> 32);
+  uint64_t p, cy;
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(p), "=s"(cy) : "v"(S), "s"(cl), "v"(((uint64_t)T.hi << 32) | T.lo));
+  uint32_t hi;
+  asm("v_add_u32 %0, %1, %2" : "=v"(hi) : "v"((uint32_t)(p >> 32)), "v"(S * ch));
+  return {(uint32_t)p, hi};
+}
+// mix of word w (even: k1, odd: k2).  FOLD: M[w] = T of the low half's entry and S[w] = the word product's high dword;
+// otherwise M[w] = word_w * (w even ? c1 : c2) and S is not used
+template <bool FOLD>
+__device__ __forceinline__ W2 mix_word(int w, W2 M, uint32_t S) {
+  if (FOLD) return (w & 1) ? mix_k2_fold(S, M) : mix_k1_fold(S, M);
+  return (w & 1) ? w2_mul(w2_rotl(M, 33), kC1) : w2_mul(w2_rotl(M, 31), kC2);
+}
+// murmur64 from the table look-ups of the k-mer's words (mix_word).
 // The digest is left OPEN one multiply early: (ka, kb) with h = open_full(ka, kb), filtered by open_hi_sum1.
-template <int L>
-__device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], int K, uint64_t seed, W2 seedv, W2& a, W2& b) {
+template <int L, bool FOLD>
+__device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint32_t (&S)[2 * L], int K, uint64_t seed, W2 seedv,
+                                                W2& a, W2& b) {
   W2 h1 = seedv, h2 = seedv;                            // (seedv: the seed's halves in vector registers, see k_dna_rolling)
   const int nblocks = K >> 4, tail = K & 15;
 #pragma unroll
   for (int blk = 0; blk < L; blk++) {
+    const int w1 = 2 * blk, w2 = 2 * blk + 1;
     if (blk < nblocks) {
-      h1 = w2_xor(h1, w2_mul(w2_rotl(M[2 * blk], 31), kC2));        // rest of mix_k1
+      h1 = w2_xor(h1, mix_word<FOLD>(w1, M[w1], S[w1]));
       // (rotl(h1, 27) + h2) * 5 + c; in the first block h2 is still the seed: rotl * 5 + (seed * 5 + c)
       if (blk == 0) h1 = w2_mul5_add(w2_rotl(h1, 27), seed * 5 + 0x52dce729u);
       else h1 = w2_mul5_add(w2_add(w2_rotl(h1, 27), h2), 0x52dce729u);
-      h2 = w2_xor(h2, w2_mul(w2_rotl(M[2 * blk + 1], 33), kC1));    // rest of mix_k2
+      h2 = w2_xor(h2, mix_word<FOLD>(w2, M[w2], S[w2]));
       h2 = w2_mul5_add(w2_add_keep(w2_rotl(h2, 31), h1), 0x38495ab5u);
     } else if (blk == nblocks) {
-      if (tail > 8) h2 = w2_xor(h2, w2_mul(w2_rotl(M[2 * blk + 1], 33), kC1));
-      if (tail > 0) h1 = w2_xor(h1, w2_mul(w2_rotl(M[2 * blk], 31), kC2));
+      if (tail > 8) h2 = w2_xor(h2, mix_word<FOLD>(w2, M[w2], S[w2]));
+      if (tail > 0) h1 = w2_xor(h1, mix_word<FOLD>(w1, M[w1], S[w1]));
     }
   }
   h1.lo ^= (uint32_t)K; h2.lo ^= (uint32_t)K;          // ^= len (K <= 128)
@@ -355,10 +396,13 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], int K, uin
 template <int KT, int THREADS, int HB, int L, bool PR = false, bool PK = false, int MINW = (PK ? 8 : 4)>
 __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashParams hp, CandSink sink,
                                                                      int logR, uint32_t stage_cap) {
-  // LDS: static: the product tables (6.8 KiB; a compile-time address, so a table read is one
+  // LDS: static: the product tables (6.8 KiB, folded 11.3 KiB; a compile-time address, so a table read is one
   // ds_read with the table's base as its immediate offset); dynamic: [staged candidates: count,
   // hashes, positions][sequence tile]
-  __shared__ __attribute__((aligned(16))) uint32_t lut[kLutDwords];
+  // folded tables (kLutDwordsFold) for the packed tile and k <= 32.  The byte tile and the 4- and 8-limb windows keep the plain
+  // ones: the byte tile has no LDS to spare, and at L = 4 the folded look-ups push the kernel over 80 registers (spills).
+  constexpr bool FOLD = PK && L == 2;
+  __shared__ __attribute__((aligned(16))) uint32_t lut[FOLD ? kLutDwordsFold : kLutDwords];
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* st_ctl = smem;                                    // [0] = count, [2..3] = flush base
   uint64_t* st_hash = reinterpret_cast<uint64_t*>(st_ctl + 4);
@@ -392,11 +436,20 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
     const int nb = ent < 512 ? 4 : (ent < 576 ? nb_last : 0);
     uint32_t v = 0;
     for (int j = 0; j < nb; j++) v |= ((0x54474341u >> (8 * ((idx >> (2 * j)) & 3))) & 0xffu) << (8 * j);
-    const uint64_t prod = (uint64_t)v * (ent < 256 ? kC1 : (ent < 512 ? kC2 : c_last));
-    ptab[e] = prod;
+    const uint64_t c = ent < 256 ? kC1 : (ent < 512 ? kC2 : c_last);
+    const uint64_t prod = (uint64_t)v * c;
     // The high half of a word needs only the product's low dword.  Read out of the 8-byte entries those look-ups
     // touch the even banks only; the packed copy spreads them over all 64 (SQ_LDS_BANK_CONFLICT 43 -> ... per 64 k-mers).
-    lut[2 * kLutEntries + e] = (uint32_t)prod;
+    if (FOLD) {
+      // {T, a.hi, 0}: T1 for the k1 words' multiplier c1, T2 for c2 (the zero entry stays zero: mix(0) = 0)
+      const uint64_t mm = (uint32_t)prod;
+      const uint64_t t = c == kC1 ? (mm << 31) * kC2 : ((mm >> 31) | ((mm & 0x7fffffffu) << 33)) * kC1;
+      reinterpret_cast<uint4*>(lut)[e] = make_uint4((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)(prod >> 32), 0u);
+      lut[4 * kLutEntries + e] = (uint32_t)prod;
+    } else {
+      ptab[e] = prod;
+      lut[2 * kLutEntries + e] = (uint32_t)prod;
+    }
   }
   // table base (bytes) of every 4-letter group: a compile-time constant for a compile-time k, fixed for
   // the launch otherwise, so that the per-k-mer code is the same straight line either way
@@ -407,7 +460,8 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
     uint32_t ent0 = 576u;                                              // past the k-mer: the zero entry
     if (nb >= 4) ent0 = ((g >> 1) & 1) ? 256u : 0u;
     else if (nb > 0) ent0 = 512u;
-    gbase[g] = (g & 1) ? 8u * kLutEntries + ent0 * 4u : ent0 * 8u;   // odd groups (high halves): the packed low dwords
+    constexpr uint32_t esz = FOLD ? 16u : 8u;                          // bytes per low-half entry
+    gbase[g] = (g & 1) ? esz * kLutEntries + ent0 * 4u : ent0 * esz;  // odd groups (high halves): the packed low dwords
   }
   if (tid == 0) st_ctl[0] = 0;
 
@@ -669,8 +723,9 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
 #pragma unroll
           for (int q = 0; q < HB; q++) {
             W2 M[2 * L];
+            uint32_t S[2 * L];                                       // FOLD: the words' product high dwords
 #pragma unroll
-            for (int wi = 0; wi < 2 * L; wi++) M[wi] = W2{0u, 0u};
+            for (int wi = 0; wi < 2 * L; wi++) { M[wi] = W2{0u, 0u}; S[wi] = 0u; }
 #pragma unroll
             for (int g = 0; g < 4 * L; g++) {
               if (KT == 0 || 4 * g < K) {
@@ -682,21 +737,33 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
                 // rate on gfx950: 32.0 -> 30.8 ms per 10 GB).  No mask is needed, for any k: both windows are
                 // zero above their 2k bits, so a partial group indexes inside its 4^nb-entry table and a
                 // group past the k-mer reads entry 0 of the zero table.
-                uint32_t off;                                        // digits << 3 (8-byte entries) or << 2 (packed low dwords)
-                if ((g & 3) == 0) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(off) : "v"(xw));
+                uint32_t off;                  // digits << 3 (8-byte entries), << 4 (FOLD: 16-byte entries) or << 2 (packed low dwords)
+                if ((g & 3) == 0 && FOLD) asm("v_lshlrev_b32_sdwa %0, 4, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(off) : "v"(xw));
+                else if ((g & 3) == 0) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(off) : "v"(xw));
                 else if ((g & 3) == 1) asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(off) : "v"(xw));
+                else if ((g & 3) == 2 && FOLD) asm("v_lshlrev_b32_sdwa %0, 4, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(off) : "v"(xw));
                 else if ((g & 3) == 2) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(off) : "v"(xw));
                 else asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(off) : "v"(xw));
                 const char* at = reinterpret_cast<const char*>(lut) + gbase[g] + off;
-                if ((g & 1) == 0) {                                  // low half of the word: full product
+                if ((g & 1) == 0 && FOLD) {                          // low half, folded: {T, a.hi, 0}
+                  // (the empty asm "uses" the pad dword: otherwise the read shrinks to a ds_read_b96, which takes 8 LDS
+                  // cycles per wave where ds_read_b128 takes 4)
+                  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                  u32x4 e = *reinterpret_cast<const u32x4*>(at);
+                  asm("" : "+v"(e));
+                  M[g >> 1] = W2{e.x, e.y};
+                  S[g >> 1] = e.z;
+                } else if ((g & 1) == 0) {                           // low half of the word: full product
                   const uint2 e = *reinterpret_cast<const uint2*>(at);
                   M[g >> 1] = W2{e.x, e.y};
+                } else if (FOLD) {
+                  S[g >> 1] += *reinterpret_cast<const uint32_t*>(at);      // high half: (entry << 32), low dword only
                 } else {
                   M[g >> 1].hi += *reinterpret_cast<const uint32_t*>(at);   // high half: (entry << 32), low dword only
                 }
               }
             }
-            murmur_kmer_pre<L>(M, K, hp.seed, seedv, ha[q], hb[q]);
+            murmur_kmer_pre<L, FOLD>(M, S, K, hp.seed, seedv, ha[q], hb[q]);
           }
 #pragma unroll
           for (int q = 0; q < HB; q++)
