@@ -255,9 +255,68 @@ int smh_release_workspace(void);
 void smh_pool_set_limit(uint64_t bytes);
 uint64_t smh_pool_bytes(void);
 
+/* Nodegraph (reference src/index/nodegraph.rs): a khmer-style bloom filter of n_tables bit tables, hash h sets bit
+ * h % tablesize of each.  Single-hash calls and file I/O run on the host; count_many / get_many on the device.
+ * Table sizes must be 1 .. 2^32 - 1.  count_many leaves the two counters exactly as count() called on the hashes in
+ * array order would; out_new / out (nullable for count_many) receive one byte per hash.  load_* keep the header's
+ * n_occupied and set unique_kmers to 0; a bad magic, version, table type or a short file is an error.  save_buffer
+ * writes the reference's layout, including its quirk: a table whose size is a multiple of 8 is written one byte
+ * shorter than the reader reads (khmer's sizes are primes).  smh_nodegraph_tablesizes returns n_tables and fills
+ * `out` (nullable).  smh_nodegraph_bins is the device modulo on its own: out[i * n_tables + t] = hashes[i] %
+ * tablesizes[t]. */
+typedef struct SmhNodegraph SmhNodegraph;
+SmhNodegraph *smh_nodegraph_new(const uint64_t *tablesizes, uint32_t n_tables, uint32_t ksize);
+void smh_nodegraph_free(SmhNodegraph *ng);
+SmhNodegraph *smh_nodegraph_load_buffer(const char *data, uint64_t len);
+SmhNodegraph *smh_nodegraph_load_path(const char *path);
+SourmashStr smh_nodegraph_save_buffer(const SmhNodegraph *ng);
+bool smh_nodegraph_count(SmhNodegraph *ng, uint64_t hash);
+int smh_nodegraph_count_many(SmhNodegraph *ng, const uint64_t *hashes, uint64_t n, uint8_t *out_new);
+uint32_t smh_nodegraph_get(const SmhNodegraph *ng, uint64_t hash);
+int smh_nodegraph_get_many(const SmhNodegraph *ng, const uint64_t *hashes, uint64_t n, uint8_t *out);
+int smh_nodegraph_update(SmhNodegraph *ng, const SmhNodegraph *other);
+double smh_nodegraph_similarity(const SmhNodegraph *ng, const SmhNodegraph *other);
+double smh_nodegraph_containment(const SmhNodegraph *ng, const SmhNodegraph *other);
+uint32_t smh_nodegraph_tablesizes(const SmhNodegraph *ng, uint64_t *out);
+uint64_t smh_nodegraph_n_occupied_bins(const SmhNodegraph *ng);
+uint64_t smh_nodegraph_unique_kmers(const SmhNodegraph *ng);
+int smh_nodegraph_bins(const uint64_t *tablesizes, uint32_t n_tables, const uint64_t *hashes, uint64_t n, uint32_t *out);
+
+/* Sequence Bloom Tree (reference src/index/sbt.rs, MHBT = SBT<Node<Nodegraph>, Leaf<Signature>>), resident in HBM:
+ * every internal nodegraph (they share one set of table sizes) plus the leaves' first sketches.
+ *   load_path  a v5 JSON; storage = the JSON's directory joined with storage.args.path (nodes: OXLI files, leaves:
+ *              signature files whose first sketch of the first signature is the leaf's data).
+ *   build      leaves at the given positions of a d-ary tree; every ancestor position gets an internal node holding
+ *              the bloom filter of the leaves below it, min_n_below = the smallest leaf size below it, n_occupied =
+ *              popcount of table 0 (what a khmer file carries), unique_kmers = 0.
+ *   save       json_path (NAME.sbt.json) + the directory .sbt.NAME beside it: internal.POS nodegraphs and leaf signatures.
+ *   find       SBT::find with search_minhashes (containment false) or search_minhashes_containment: the positions of the
+ *              leaves that pass, in the reference's walk order; out_positions holds n_leaves entries.  A query
+ *              incompatible with a leaf the walk reaches is error 101-104; a node without min_n_below reached by a
+ *              non-empty query in similarity mode is an error.
+ *   find_many  the same for n queries at once: query i's list is positions[offsets[i] .. offsets[i + 1]); out_offsets
+ *              holds n + 1 entries, *out_positions points into the tree's own storage (valid until the next find on it).
+ * leaf_positions: ascending positions of the leaves (n_leaves entries); leaf_sketch(i) is a copy of leaf i's sketch in
+ * that order (free it with kmerminhash_free). */
+typedef struct SmhSbt SmhSbt;
+SmhSbt *smh_sbt_load_path(const char *json_path);
+SmhSbt *smh_sbt_build(uint32_t d, const uint64_t *positions, KmerMinHash *const *leaves, uint32_t n_leaves,
+                      const uint64_t *tablesizes, uint32_t n_tables, uint32_t ksize);
+int smh_sbt_save(const SmhSbt *sbt, const char *json_path);
+void smh_sbt_free(SmhSbt *sbt);
+uint32_t smh_sbt_n_nodes(const SmhSbt *sbt);
+uint32_t smh_sbt_n_leaves(const SmhSbt *sbt);
+int smh_sbt_leaf_positions(const SmhSbt *sbt, uint64_t *out);
+KmerMinHash *smh_sbt_leaf_sketch(const SmhSbt *sbt, uint32_t i);
+int smh_sbt_find(SmhSbt *sbt, const KmerMinHash *query, double threshold, bool containment, uint64_t *out_positions,
+                 uint32_t *out_count);
+int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, double threshold, bool containment,
+                      uint64_t *out_offsets, const uint64_t **out_positions);
+
 /* HIP-event timing of the library's kernels, on the stream they run on.
  * name: "dna_rolling", "dna_generic", "protein_fused", "translate", "hash_windows", "compare_wave", "compare_few",
- * "compare_pair", "compare_fill", "compare_comp", "compare_tiled" (the plain and the pipelined tiled kernels of one call together). */
+ * "compare_pair", "compare_fill", "compare_comp", "compare_tiled" (the plain and the pipelined tiled kernels of one call together),
+ * "sbt_bins", "sbt_nodes", "sbt_leaves", "sbt_build". */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -135,6 +135,32 @@ _SIGS = {
     "smh_compare_set_tuning": (C.c_int, [C.POINTER(SmhCompareTuning)]),
     "smh_synth_dna_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "smh_sort_u64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "smh_nodegraph_new": (C.c_void_p, [u64p, C.c_uint32, C.c_uint32]),
+    "smh_nodegraph_free": (None, [C.c_void_p]),
+    "smh_nodegraph_load_buffer": (C.c_void_p, [C.c_char_p, C.c_uint64]),
+    "smh_nodegraph_load_path": (C.c_void_p, [C.c_char_p]),
+    "smh_nodegraph_save_buffer": (SourmashStr, [C.c_void_p]),
+    "smh_nodegraph_count": (C.c_bool, [C.c_void_p, C.c_uint64]),
+    "smh_nodegraph_count_many": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_void_p]),
+    "smh_nodegraph_get": (C.c_uint32, [C.c_void_p, C.c_uint64]),
+    "smh_nodegraph_get_many": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_void_p]),
+    "smh_nodegraph_update": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "smh_nodegraph_similarity": (C.c_double, [C.c_void_p, C.c_void_p]),
+    "smh_nodegraph_containment": (C.c_double, [C.c_void_p, C.c_void_p]),
+    "smh_nodegraph_tablesizes": (C.c_uint32, [C.c_void_p, u64p]),
+    "smh_nodegraph_n_occupied_bins": (C.c_uint64, [C.c_void_p]),
+    "smh_nodegraph_unique_kmers": (C.c_uint64, [C.c_void_p]),
+    "smh_nodegraph_bins": (C.c_int, [u64p, C.c_uint32, u64p, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "smh_sbt_load_path": (C.c_void_p, [C.c_char_p]),
+    "smh_sbt_build": (C.c_void_p, [C.c_uint32, u64p, C.POINTER(C.c_void_p), C.c_uint32, u64p, C.c_uint32, C.c_uint32]),
+    "smh_sbt_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "smh_sbt_free": (None, [C.c_void_p]),
+    "smh_sbt_n_nodes": (C.c_uint32, [C.c_void_p]),
+    "smh_sbt_n_leaves": (C.c_uint32, [C.c_void_p]),
+    "smh_sbt_leaf_positions": (C.c_int, [C.c_void_p, u64p]),
+    "smh_sbt_leaf_sketch": (C.c_void_p, [C.c_void_p, C.c_uint32]),
+    "smh_sbt_find": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_bool, u64p, C.POINTER(C.c_uint32)]),
+    "smh_sbt_find_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.c_bool, u64p, C.POINTER(u64p)]),
     "smh_profile_enable": (None, [C.c_int]),
     "smh_profile_reset": (None, []),
     "smh_profile_get": (C.c_int, [C.c_char_p, f64p, u64p]),

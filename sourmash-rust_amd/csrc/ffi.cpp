@@ -10,6 +10,7 @@
 
 #include "../../include/sourmash_amd.h"
 #include "minhash.hpp"
+#include "sbt.hpp"
 #include "signature.hpp"
 
 using smh::Error;
@@ -1021,6 +1022,169 @@ int smh_profile_get(const char* name, double* total_ms, uint64_t* launches) {
     auto t = smh::Device::get().prof_get(name);
     if (total_ms) *total_ms = t.ms;
     if (launches) *launches = t.launches;
+  });
+}
+
+// ------------------------------------------------------------------ Nodegraph / SBT
+
+struct SmhNodegraph : smh::Nodegraph {
+  using smh::Nodegraph::Nodegraph;
+  SmhNodegraph(smh::Nodegraph&& o) : smh::Nodegraph(std::move(o)) {}
+};
+struct SmhSbt {
+  std::unique_ptr<smh::Sbt> t;
+  std::vector<uint64_t> offsets, positions;   // the last find_many's results (smh_sbt_find_many hands out a pointer)
+};
+
+SmhNodegraph* smh_nodegraph_new(const uint64_t* tablesizes, uint32_t n_tables, uint32_t ksize) {
+  return pad<SmhNodegraph*>([&] {
+    if (n_tables) require(tablesizes, "tablesizes");
+    return new SmhNodegraph(std::vector<uint64_t>(tablesizes, tablesizes + n_tables), ksize);
+  });
+}
+void smh_nodegraph_free(SmhNodegraph* ng) { delete ng; }
+SmhNodegraph* smh_nodegraph_load_buffer(const char* data, uint64_t len) {
+  return pad<SmhNodegraph*>([&] {
+    if (len) require(data, "data");
+    return new SmhNodegraph(smh::Nodegraph::load(data, (size_t)len));
+  });
+}
+SmhNodegraph* smh_nodegraph_load_path(const char* path) {
+  return pad<SmhNodegraph*>([&] {
+    require(path, "path");
+    const std::string raw = smh::read_file(path);
+    return new SmhNodegraph(smh::Nodegraph::load(raw.data(), raw.size()));
+  });
+}
+SourmashStr smh_nodegraph_save_buffer(const SmhNodegraph* ng) {
+  return pad<SourmashStr>([&] { require(ng, "ng"); return str_from_string(ng->save()); });
+}
+bool smh_nodegraph_count(SmhNodegraph* ng, uint64_t hash) {
+  return pad<bool>([&] { require(ng, "ng"); return ng->count(hash); });
+}
+int smh_nodegraph_count_many(SmhNodegraph* ng, const uint64_t* hashes, uint64_t n, uint8_t* out_new) {
+  return pad_code([&] {
+    require(ng, "ng");
+    if (n) require(hashes, "hashes");
+    ng->count_many(hashes, n, out_new);
+  });
+}
+uint32_t smh_nodegraph_get(const SmhNodegraph* ng, uint64_t hash) {
+  return pad<uint32_t>([&] { require(ng, "ng"); return ng->get(hash); });
+}
+int smh_nodegraph_get_many(const SmhNodegraph* ng, const uint64_t* hashes, uint64_t n, uint8_t* out) {
+  return pad_code([&] {
+    require(ng, "ng");
+    if (n) { require(hashes, "hashes"); require(out, "out"); }
+    ng->get_many(hashes, n, out);
+  });
+}
+int smh_nodegraph_update(SmhNodegraph* ng, const SmhNodegraph* other) {
+  return pad_code([&] { require(ng, "ng"); require(other, "other"); ng->update(*other); });
+}
+double smh_nodegraph_similarity(const SmhNodegraph* ng, const SmhNodegraph* other) {
+  return pad<double>([&] { require(ng, "ng"); require(other, "other"); return ng->similarity(*other); });
+}
+double smh_nodegraph_containment(const SmhNodegraph* ng, const SmhNodegraph* other) {
+  return pad<double>([&] { require(ng, "ng"); require(other, "other"); return ng->containment(*other); });
+}
+uint32_t smh_nodegraph_tablesizes(const SmhNodegraph* ng, uint64_t* out) {
+  if (!ng) return 0;
+  if (out) for (uint32_t t = 0; t < ng->L.n_tables(); t++) out[t] = ng->L.sizes[t];
+  return ng->L.n_tables();
+}
+uint64_t smh_nodegraph_n_occupied_bins(const SmhNodegraph* ng) { return ng ? ng->occupied_bins : 0; }
+uint64_t smh_nodegraph_unique_kmers(const SmhNodegraph* ng) { return ng ? ng->unique_kmers : 0; }
+int smh_nodegraph_bins(const uint64_t* tablesizes, uint32_t n_tables, const uint64_t* hashes, uint64_t n, uint32_t* out) {
+  return pad_code([&] {
+    if (n == 0 || n_tables == 0) return;
+    require(tablesizes, "tablesizes"); require(hashes, "hashes"); require(out, "out");
+    smh::TableLayout L;
+    L.init(std::vector<uint64_t>(tablesizes, tablesizes + n_tables));
+    auto& dev = smh::Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.stream();
+    smh::DeviceLayout DL;
+    DL.upload(L, s);
+    smh::DeviceBuffer dh, db;
+    dh.ensure(n * 8); db.ensure(n * n_tables * 4);
+    HIP_CHECK(hipMemcpyAsync(dh.ptr, hashes, n * 8, hipMemcpyHostToDevice, s));
+    smh::launch_sbt_bins(dh.as<uint64_t>(), n, DL, db.as<uint32_t>(), s);
+    HIP_CHECK(hipMemcpyAsync(out, db.ptr, n * n_tables * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+SmhSbt* smh_sbt_load_path(const char* json_path) {
+  return pad<SmhSbt*>([&] {
+    require(json_path, "json_path");
+    std::unique_ptr<SmhSbt> o(new SmhSbt());
+    o->t.reset(smh::Sbt::load(json_path));
+    return o.release();
+  });
+}
+SmhSbt* smh_sbt_build(uint32_t d, const uint64_t* positions, KmerMinHash* const* leaves, uint32_t n_leaves,
+                      const uint64_t* tablesizes, uint32_t n_tables, uint32_t ksize) {
+  return pad<SmhSbt*>([&] {
+    if (n_leaves) { require(positions, "positions"); require(leaves, "leaves"); }
+    if (n_tables) require(tablesizes, "tablesizes");
+    std::vector<const smh::KmerMinHash*> v(n_leaves);
+    for (uint32_t i = 0; i < n_leaves; i++) { require(leaves[i], "leaves[i]"); v[i] = leaves[i]; }
+    std::unique_ptr<SmhSbt> o(new SmhSbt());
+    o->t.reset(smh::Sbt::build(d, std::vector<uint64_t>(positions, positions + n_leaves), v,
+                               std::vector<uint64_t>(tablesizes, tablesizes + n_tables), ksize));
+    return o.release();
+  });
+}
+int smh_sbt_save(const SmhSbt* sbt, const char* json_path) {
+  return pad_code([&] { require(sbt, "sbt"); require(json_path, "json_path"); sbt->t->save(json_path); });
+}
+void smh_sbt_free(SmhSbt* sbt) {
+  if (!sbt) return;
+  (void)pad_code([&] {
+    std::lock_guard<std::recursive_mutex> lock(smh::Device::get().mutex());
+    delete sbt;
+  });
+}
+uint32_t smh_sbt_n_nodes(const SmhSbt* sbt) { return sbt ? sbt->t->n_nodes() : 0; }
+uint32_t smh_sbt_n_leaves(const SmhSbt* sbt) { return sbt ? sbt->t->n_leaves() : 0; }
+int smh_sbt_leaf_positions(const SmhSbt* sbt, uint64_t* out) {
+  return pad_code([&] {
+    require(sbt, "sbt");
+    const auto& p = sbt->t->leaf_positions();
+    if (!p.empty()) { require(out, "out"); std::copy(p.begin(), p.end(), out); }
+  });
+}
+KmerMinHash* smh_sbt_leaf_sketch(const SmhSbt* sbt, uint32_t i) {
+  return pad<KmerMinHash*>([&] {
+    require(sbt, "sbt");
+    if (i >= sbt->t->n_leaves()) smh::throw_panic("index out of bounds: leaf");
+    return new KmerMinHash(sbt->t->leaf_sketch(i));
+  });
+}
+int smh_sbt_find_many(SmhSbt* sbt, KmerMinHash* const* queries, uint32_t n, double threshold, bool containment,
+                      uint64_t* out_offsets, const uint64_t** out_positions) {
+  return pad_code([&] {
+    require(sbt, "sbt"); require(out_offsets, "out_offsets"); require(out_positions, "out_positions");
+    *out_positions = nullptr;
+    std::fill(out_offsets, out_offsets + n + 1, 0);
+    if (n) require(queries, "queries");
+    std::vector<const smh::KmerMinHash*> q(n);
+    for (uint32_t i = 0; i < n; i++) { require(queries[i], "queries[i]"); q[i] = queries[i]; }
+    sbt->t->find_many(q, threshold, containment, sbt->offsets, sbt->positions);
+    std::copy(sbt->offsets.begin(), sbt->offsets.end(), out_offsets);
+    *out_positions = sbt->positions.data();
+  });
+}
+int smh_sbt_find(SmhSbt* sbt, const KmerMinHash* query, double threshold, bool containment, uint64_t* out_positions,
+                 uint32_t* out_count) {
+  return pad_code([&] {
+    require(sbt, "sbt"); require(query, "query"); require(out_count, "out_count");
+    *out_count = 0;
+    std::vector<const smh::KmerMinHash*> q(1, query);
+    sbt->t->find_many(q, threshold, containment, sbt->offsets, sbt->positions);
+    if (!sbt->positions.empty()) { require(out_positions, "out_positions"); std::copy(sbt->positions.begin(), sbt->positions.end(), out_positions); }
+    *out_count = (uint32_t)sbt->positions.size();
   });
 }
 

@@ -8,6 +8,7 @@
 #include <cctype>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <map>
@@ -450,6 +451,52 @@ bool signature_equal(const Signature& a, const Signature& b) {
               a.has_filename == b.has_filename && (!a.has_filename || a.filename == b.filename) &&
               a.has_name == b.has_name && (!a.has_name || a.name == b.name);
   return meta && sketch_equal(a.signatures[0], b.signatures[0]);
+}
+
+SbtJson sbt_json_from(const char* data, size_t len) {
+  JParser ps{data, data + len};
+  JVal root;
+  ps.parse_value(root);
+  ps.ws();
+  if (ps.p != ps.end) serde_error("JSON error: trailing characters");
+  if (root.kind != JVal::Obj) serde_error("invalid type: expected struct SBTInfo");
+  SbtJson out;
+  out.d = (uint32_t)want_uint(root.get("d"), "d", UINT32_MAX);
+  out.version = (uint32_t)want_uint(root.get("version"), "version", UINT32_MAX);
+  const JVal* st = root.get("storage");
+  if (!st || st->kind != JVal::Obj) serde_error("missing field `storage`");
+  const JVal* args = st->get("args");
+  if (!args || args->kind != JVal::Obj) serde_error("missing field `args`");
+  out.storage_path = want_str(args->get("path"), "path");
+  const JVal* fac = root.get("factory");
+  if (!fac || fac->kind != JVal::Obj) serde_error("missing field `factory`");
+  out.factory_args = want_u64_array(fac->get("args"), "args");
+  auto entries = [&](const char* field, std::vector<SbtJsonEntry>& v, bool node) {
+    const JVal* m = root.get(field);
+    if (!m) serde_error(std::string("missing field `") + field + "`");
+    if (m->kind != JVal::Obj) serde_error(std::string("invalid type for field `") + field + "`: expected a map");
+    for (auto& kv : m->obj) {
+      SbtJsonEntry e;
+      char* endp = nullptr;
+      if (kv.first.empty() || !isdigit((unsigned char)kv.first[0])) serde_error("invalid map key: expected u64");
+      e.pos = strtoull(kv.first.c_str(), &endp, 10);
+      if (*endp) serde_error("invalid map key: expected u64");
+      e.filename = want_str(kv.second.get("filename"), "filename");
+      e.name = want_str(kv.second.get("name"), "name");
+      if (node) {
+        const JVal* md = kv.second.get("metadata");
+        if (!md || md->kind != JVal::Obj) serde_error("invalid type for field `metadata`: expected a map");
+        if (const JVal* mn = md->get("min_n_below")) {
+          e.has_min_n_below = true;
+          e.min_n_below = want_uint(mn, "min_n_below", UINT64_MAX);
+        }
+      }
+      v.push_back(std::move(e));
+    }
+  };
+  entries("nodes", out.nodes, true);
+  entries("leaves", out.leaves, false);
+  return out;
 }
 
 std::string read_file(const std::string& path) {

@@ -29,4 +29,21 @@ std::vector<Signature> signatures_from_json(const char* data, size_t len);
 std::vector<Signature> load_signatures(const char* data, size_t len, size_t ksize, const char* moltype);
 std::string read_file(const std::string& path);
 
+// The SBT v5 JSON layout (reference src/index/sbt.rs:72-135, 246-277): d, storage path, factory args, and the node and
+// leaf maps keyed by position.  A node's metadata.min_n_below may be missing (has_min_n_below false).
+struct SbtJsonEntry {
+  uint64_t pos = 0;
+  std::string filename, name;
+  bool has_min_n_below = false;
+  uint64_t min_n_below = 0;
+};
+struct SbtJson {
+  uint32_t d = 2;
+  uint32_t version = 5;
+  std::string storage_path;
+  std::vector<uint64_t> factory_args;
+  std::vector<SbtJsonEntry> nodes, leaves;
+};
+SbtJson sbt_json_from(const char* data, size_t len);
+
 }  // namespace smh
