@@ -383,8 +383,9 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint
 // CLEAN when all four bases are ACGT, none lies outside the current record's valid part, and all four
 // windows that end in it are complete and belong to the lane's run: then there is nothing to decide
 // per base.  One unsigned compare tells (g_span), and only groups that are not clean -- the first
-// one of a run, the ones around a record boundary or a non-ACGT byte, the last one -- take the
-// per-base path below, which produces a 4-bit mask of the windows that may be emitted.
+// and the last one of a run that is not whole (see kEdgeFree), the ones around a record boundary
+// or a non-ACGT byte -- take the per-base path below, which produces a 4-bit mask of the windows
+// that may be emitted.
 //
 // PK: the tile is staged PACKED -- two bits per base (the 2-bit code the rolling needs anyway: the upper-casing, the
 // encoding and the validity check are done once, by the lane that stages the bytes, 16 at a time) plus one "dirty" bit per
@@ -494,26 +495,46 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
       if (tid == 0) st_ctl[1] = 0;                                   // "some dword of this tile is dirty"
       __syncthreads();
     }
+    // chunks that lie inside the (16-byte padded) input: one 32-bit compare per chunk instead of a 64-bit address compare
+    const uint64_t cin64 = gend > ga ? (uint64_t)(gend - ga) >> 4 : 0ull;
+    const uint32_t cin = cin64 < nchunks ? (uint32_t)cin64 : nchunks;
+    // "ACTG", the letters in the order of bits 1..2 of their codes, in a SCALAR register: v_perm_b32 is a three-operand form
+    // at either rate, and a vector register held for the constant across the whole kernel costs the k-mer loop a spill
+    uint32_t kActg;
+    asm("s_mov_b32 %0, 0x47544341" : "=s"(kActg));
     for (uint32_t c = tid; c < nchunks; c += THREADS) {
-      uintptr_t addr = ga + ((uintptr_t)c << 4);
       uint4 v = make_uint4(0, 0, 0, 0);
-      if (addr < gend) v = *reinterpret_cast<const uint4*>(addr);
+      if (c < cin) v = *reinterpret_cast<const uint4*>(ga + ((uintptr_t)c << 4));
       if (PK) {
-        // 16 bases -> 32 bits of codes (base j of the chunk in bits 2j, 2j+1) + 4 dirty bits
+        // 16 bases -> 32 bits of codes (base j of the chunk in bits 2j, 2j+1) + 4 dirty bits.  Per source dword: upper-case,
+        // bits 1..2 of every letter (A0 C1 T2 G3, a Gray code of A0 C1 G2 T3), validity by re-expanding THAT code, and the
+        // four 2-bit fields gathered into one byte by one v_dot4_u32_u8 with the weights 1, 4, 16, 64 (it issues a little
+        // faster than v_mul_lo_u32 by 2^24 + 2^18 + 2^12 + 2^6: tools/instr_rate.hip).  The Gray code is turned into the
+        // binary one once per 16 bases, on the assembled dword.  Every byte is encoded on its own: a valid base inside a
+        // dirty dword keeps its correct code (the per-base path rolls the windows from it).
         const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
-        uint32_t codes = 0, bad = 0;
+        uint32_t xany = 0, gray = 0;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           const uint32_t u4 = w4[q] & 0xDFDFDFDFu;
-          const uint32_t c2 = (u4 >> 1) & 0x03030303u;
-          const uint32_t code4 = c2 ^ ((c2 >> 1) & 0x01010101u);
-          const uint32_t exp4 = __builtin_amdgcn_perm(0u, 0x54474341u, code4);
-          bad |= (u4 != exp4) ? (1u << q) : 0u;
-          const uint32_t pk = code4 | (code4 >> 6);                   // bytes 0,1 -> bits 0..3; bytes 2,3 -> bits 16..19
-          codes |= ((pk & 0xfu) | ((pk >> 12) & 0xf0u)) << (8 * q);
+          const uint32_t g4 = (u4 >> 1) & 0x03030303u;
+          xany |= u4 ^ __builtin_amdgcn_perm(0u, kActg, g4);
+          gray |= __builtin_amdgcn_udot4(g4, 0x40100401u, 0u, false) << (8 * q);   // the dword's four codes in one byte
         }
-        tile[c + (c >> (logR - 4))] = codes;                         // one pad dword per run: lane-strided reads hit distinct banks
-        if (bad) { atomicOr(&dirty[c >> 3], bad << (4u * (c & 7u))); st_ctl[1] = 1; }
+        tile[c + (c >> (logR - 4))] = gray ^ ((gray >> 1) & 0x55555555u);   // one pad dword per run: lane-strided reads hit distinct banks
+        if (xany) {
+          // rare: some byte other than ACGT.  Which dwords hold one is found from the 16 bytes read again, so that the
+          // common path carries one word of differences instead of four.
+          const volatile uint32_t* src = reinterpret_cast<const volatile uint32_t*>(ga + ((uintptr_t)c << 4));
+          uint32_t bad = 0;
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            const uint32_t u4 = (c < cin ? src[q] : 0u) & 0xDFDFDFDFu;
+            bad |= u4 != __builtin_amdgcn_perm(0u, kActg, (u4 >> 1) & 0x03030303u) ? 1u << q : 0u;
+          }
+          atomicOr(&dirty[c >> 3], bad << (4u * (c & 7u)));
+          st_ctl[1] = 1;
+        }
       } else {
         uint32_t x = c << 4;
         uint32_t o = (x >> 2) + (x >> logR);
@@ -552,14 +573,21 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
       dmask = (lo64 >> sft) | (sft ? ((uint64_t)d2 << (64 - sft)) : 0ull);
       if (m & 3u) dmask |= (dmask >> 1) | ((uint64_t)((d2 >> sft) & 1u) << 63);
     }
+    // The uniform guard of a hashing block, i0 + g0b + HB >= K && i0 + g0b < R + K - 1, hashes exactly the complete windows
+    // of a full run when the blocks line up with base K - 1 ((K - 1) % HB == 0; R is a multiple of HB).  Then a run that has
+    // seen no invalid base (vstart == 0) and that the range does not cut short (nk == R) needs no mask for its first and
+    // its last hashing group either: its clean stretch starts with the group of base K - 1 and only `lim` and the dirty
+    // bits end it -- the walk's last bases, past the run, must be valid for that, or the group goes base by base as before.
+    constexpr bool kEdgeFree = KT > 0 && (KT - 1) % HB == 0;
     auto set_clean_window = [&](bool warm, uint32_t from_i) {
-      uint32_t lim2 = warm ? lim : (lim < hi_ok ? lim : hi_ok);
+      const bool whole = warm || (kEdgeFree && vstart == 0 && nk == R);
+      uint32_t lim2 = whole ? lim : (lim < hi_ok ? lim : hi_ok);
       if (PK) {
         const uint32_t g = from_i >> 2;
         const uint64_t rem = g < 64 ? (dmask >> g) : 0ull;
         if (rem) lim2 = min(lim2, (g + (uint32_t)__builtin_ctzll(rem)) * 4u);      // clean groups end before the next dirty one
       }
-      g_lo = warm ? vstart : vstart + (uint32_t)K - 1;   // warm-up groups emit nothing: only validity matters
+      g_lo = whole ? vstart : vstart + (uint32_t)K - 1;  // warm-up groups emit nothing: only validity matters
       g_span = lim2 >= g_lo + 4 ? lim2 - 3 - g_lo : 0u;
     };
 
@@ -640,9 +668,9 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
             if (at < b.len) d |= (uint32_t)b.seq[at] << (8 * q);
           }
           const uint32_t u4 = d & 0xDFDFDFDFu;
-          const uint32_t c2 = (u4 >> 1) & 0x03030303u;
-          const uint32_t cd = c2 ^ ((c2 >> 1) & 0x01010101u);
-          diff4 = u4 ^ __builtin_amdgcn_perm(0u, 0x54474341u, cd);
+          uint32_t actg;                                             // (a scalar register: see the staging loop)
+          asm("s_mov_b32 %0, 0x47544341" : "=s"(actg));
+          diff4 = u4 ^ __builtin_amdgcn_perm(0u, actg, (u4 >> 1) & 0x03030303u);   // as the staging lanes check
         }
         // ---- not clean (rare): base by base, exactly the reference's conditions
         okmask = 0;
@@ -781,10 +809,28 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
     };
 
     set_clean_window(true, 0);
-    uint32_t i0 = 0;
-    for (; i0 < warm_end; i0 += 4) group(i0, std::false_type{});
-    set_clean_window(false, i0);
-    for (; i0 < nsteps; i0 += 4) group(i0, std::true_type{});
+    if (kRoll31 && !PR && g_span > 24u) {
+      // k = 31, packed tile, all seven warm-up groups clean (g_lo = 0 here: no dirty dword and no end of the record's valid
+      // part in bases 0..27): the state the groups would leave is a function of the run's first 28 codes (29 for fa's top
+      // bits), which sit in three tile dwords, and is formed directly.  q0, q1 = the codes of bases 0..15 and 16..31.
+      const uint32_t d1 = tile[cq + 1 + ((cq + 1) >> (logR - 4))], d2 = tile[cq + 2 + ((cq + 2) >> (logR - 4))];
+      const uint32_t q0 = __builtin_amdgcn_alignbit(d1, pcur, sh2), q1 = __builtin_amdgcn_alignbit(d2, d1, sh2);
+      cq += 2; pcur = d2;
+      fa0 = q0 << 6;                                                 // base 0 at bit 6 ... base 28 at bits 62..63
+      fa1 = __builtin_amdgcn_alignbit(q1, q0, 26);
+      const uint32_t r0 = __builtin_bitreverse32(q0), r1 = __builtin_bitreverse32(q1);
+      const uint32_t c0 = ~(((r0 >> 1) & 0x55555555u) | ((r0 << 1) & 0xaaaaaaaau));   // complements, base j in bits 30-2j
+      const uint32_t c1 = ~(((r1 >> 1) & 0x55555555u) | ((r1 << 1) & 0xaaaaaaaau));
+      cs0 = __builtin_amdgcn_alignbit(c0, c1, 8);                    // base 27 at bits 0..1 ... base 0 at bits 54..55
+      cs1 = c0 >> 8;
+      w = q1 >> 24; wc = ~q1 >> 24; wr = c1 << 24;                   // the quad's last group: bases 28..31
+    } else {
+      for (uint32_t i0 = 0; i0 < warm_end; i0 += 4) group(i0, std::false_type{});
+    }
+    // (the hashing loop's counter starts at a constant on either path: it stays in a scalar register, and the tests
+    // on it -- a new dword every 16 bases, the block guards -- stay uniform)
+    set_clean_window(false, warm_end);
+    for (uint32_t i0 = warm_end; i0 < nsteps; i0 += 4) group(i0, std::true_type{});
     }  // p0 < range_hi
 
     // ---- flush the staged candidates: ONE global atomic per tile, coalesced stores

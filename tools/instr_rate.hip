@@ -42,6 +42,11 @@ constexpr int ITERS = 2048;
 #define I_ADDCO(n) "v_add_co_u32 %" #n ", vcc, %" #n ", %8\n"
 #define I_ADDC(n) "v_addc_co_u32 %" #n ", vcc, %" #n ", %8, vcc\n"
 #define I_AND_LIT(n) "v_and_b32 %" #n ", 0xDFDFDFDF, %" #n "\n"
+#define I_DOT4(n) "v_dot4_u32_u8 %" #n ", %" #n ", %8, 0\n"
+#define I_DOT4_ACC(n) "v_dot4_u32_u8 %" #n ", %8, %8, %" #n "\n"
+#define I_BFI(n) "v_bfi_b32 %" #n ", %8, %" #n ", %8\n"
+#define I_OR3(n) "v_or3_b32 %" #n ", %" #n ", %8, %8\n"
+#define I_LSHL_OR(n) "v_lshl_or_b32 %" #n ", %" #n ", 8, %8\n"
 
 template <int OP>
 __global__ __launch_bounds__(256) void k32(uint32_t* out, uint32_t b, uint32_t c) {
@@ -74,6 +79,11 @@ __global__ __launch_bounds__(256) void k32(uint32_t* out, uint32_t b, uint32_t c
   if (OP == 26) BODY8(I_ADDCO)
   if (OP == 27) BODY8(I_ADDC)
   if (OP == 28) BODY8(I_AND_LIT)
+  if (OP == 29) BODY8(I_DOT4)
+  if (OP == 30) BODY8(I_DOT4_ACC)
+  if (OP == 31) BODY8(I_BFI)
+  if (OP == 32) BODY8(I_OR3)
+  if (OP == 33) BODY8(I_LSHL_OR)
   uint32_t r = 0;
   for (int i = 0; i < 8; i++) r ^= a[i];
   out[blockIdx.x * blockDim.x + threadIdx.x] = r;
@@ -139,6 +149,7 @@ int main() {
   RUN32(16, "v_mad_u32_u24") RUN32(17, "v_lshrrev_b32") RUN32(18, "v_and_or_b32")
   RUN32(19, "v_xor_b32 literal") RUN32(28, "v_and_b32 literal") RUN32(20, "v_add_u32 inline7") RUN32(21, "v_xor_b32 sgpr") RUN32(22, "v_lshlrev_sdwa")
   RUN32(23, "v_alignbyte_b32") RUN32(24, "v_cmp_lt_u32 vcc") RUN32(25, "v_mov_b32") RUN32(26, "v_add_co_u32") RUN32(27, "v_addc_co_u32")
+  RUN32(29, "v_dot4_u32_u8") RUN32(30, "v_dot4_u32_u8 acc") RUN32(31, "v_bfi_b32") RUN32(32, "v_or3_b32") RUN32(33, "v_lshl_or_b32")
   RUN64(0, "v_mad_u64_u32") RUN64(1, "v_lshl_add_u64") RUN64(2, "v_lshlrev_b64") RUN64(3, "v_lshrrev_b64")
   RUN64(4, "mad_u64 v,v,v64") RUN64(5, "mad_u64 v,s,0") RUN64(6, "mad_u64 v,v,0") RUN64(7, "v_mov_b64") RUN64(8, "lshl_add_u64 sh0")
   return 0;
