@@ -212,7 +212,17 @@ __device__ __forceinline__ uint32_t upper(uint32_t c) { return (c >= 'a' && c <=
 // plain product tables: its 64 KiB tile leaves no room for two workgroups per CU with the larger ones.
 constexpr int kLutEntries = 256 + 256 + 64 + 1;              // P1, P2, partial group, one zero entry (groups past the k-mer)
 constexpr int kLutDwords = kLutEntries * 3;                  // u64 entries (4.5 KiB), then their low dwords once more, packed
-constexpr int kLutDwordsFold = kLutEntries * 5;              // folded: 16-byte entries (9 KiB), then the packed low dwords
+// The high dword's cross term of a k2 word comes from the tables too.  With ch = hi32(2 c1), S * (2 c1) =
+// S * lo32(2 c1) + ((S * ch mod 2^32) << 32), and mod 2^32 the product S * ch is linear in a.hi and B -- the wrap of
+// a.hi + B drops out (2^32 * ch == 0) -- so a.hi * ch is added to the high dword of the low half's T2 (T2'') and the high
+// halves of the k2 words read 8-byte entries {B, B' = B * ch}: mixed = S * lo32(2 c1) + T2'' + (B' << 32), one
+// v_mad_u64_u32 and one add, no v_mul_lo_u32.  The k1 words' multiplier sees S >> 1, which is not linear in a.hi and B:
+// their high halves stay on the packed dwords.
+constexpr int kLutHiEntries = 256 + 64 + 1;                  // a high half's table: full groups, partial group, the zero entry
+constexpr int kLutFoldB8 = kLutEntries * 4;                  // dword index of the k2 high halves' {B, B'} (8-byte aligned)
+constexpr int kLutFoldB4 = kLutFoldB8 + kLutHiEntries * 2;   // dword index of the k1 high halves' packed low dwords
+constexpr int kLutDwordsCross = kLutFoldB4 + kLutHiEntries;  // folded: 16-byte entries (9 KiB), {B, B'} (2.5 KiB), packed B (1.25 KiB)
+constexpr int kLutDwordsFold = kLutEntries * 5;              // folded, cross term multiplied: 16-byte entries, then the packed low dwords
 constexpr uint64_t kC1x2 = kC1 * 2;                          // (mod 2^64)
 
 // The hash runs on explicit 32-bit halves.  Issue rates on gfx950 (tools/instr_rate.hip,
@@ -330,25 +340,27 @@ __device__ __forceinline__ W2 mix_k1_fold(uint32_t S, W2 T) {   // (S >> 1) * c2
   asm("v_lshl_add_u32 %0, %1, 31, %2" : "=v"(top) : "v"(S), "v"(hi));
   return {(uint32_t)p, top};
 }
-__device__ __forceinline__ W2 mix_k2_fold(uint32_t S, W2 T) {   // S * (2 c1) + T2
+// CROSS: S * lo32(2 c1) + T2'' + (B' << 32); otherwise S * (2 c1) + T2
+template <bool CROSS>
+__device__ __forceinline__ W2 mix_k2_fold(uint32_t S, W2 T, uint32_t Bp) {
   const uint32_t cl = (uint32_t)kC1x2, ch = (uint32_t)(kC1x2 >> 32);
   uint64_t p, cy;
   asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(p), "=s"(cy) : "v"(S), "s"(cl), "v"(((uint64_t)T.hi << 32) | T.lo));
   uint32_t hi;
-  asm("v_add_u32 %0, %1, %2" : "=v"(hi) : "v"((uint32_t)(p >> 32)), "v"(S * ch));
+  asm("v_add_u32 %0, %1, %2" : "=v"(hi) : "v"((uint32_t)(p >> 32)), "v"(CROSS ? Bp : S * ch));
   return {(uint32_t)p, hi};
 }
-// mix of word w (even: k1, odd: k2).  FOLD: M[w] = T of the low half's entry and S[w] = the word product's high dword;
-// otherwise M[w] = word_w * (w even ? c1 : c2) and S is not used
-template <bool FOLD>
-__device__ __forceinline__ W2 mix_word(int w, W2 M, uint32_t S) {
-  if (FOLD) return (w & 1) ? mix_k2_fold(S, M) : mix_k1_fold(S, M);
+// mix of word w (even: k1, odd: k2).  FOLD: M[w] = T of the low half's entry, S[w] = the word product's high dword and
+// (CROSS, k2 words) P[w] = B' of the high half's entry; otherwise M[w] = word_w * (w even ? c1 : c2) and S, P are not used
+template <bool FOLD, bool CROSS>
+__device__ __forceinline__ W2 mix_word(int w, W2 M, uint32_t S, uint32_t P) {
+  if (FOLD) return (w & 1) ? mix_k2_fold<CROSS>(S, M, P) : mix_k1_fold(S, M);
   return (w & 1) ? w2_mul(w2_rotl(M, 33), kC1) : w2_mul(w2_rotl(M, 31), kC2);
 }
 // murmur64 from the table look-ups of the k-mer's words (mix_word).
 // The digest is left OPEN one multiply early: (ka, kb) with h = open_full(ka, kb), filtered by open_hi_sum1.
-template <int L, bool FOLD>
-__device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint32_t (&S)[2 * L], int K, uint64_t seed, W2 seedv,
+template <int L, bool FOLD, bool CROSS>
+__device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint32_t (&S)[2 * L], const uint32_t (&P)[2 * L], int K, uint64_t seed, W2 seedv,
                                                 W2& a, W2& b) {
   W2 h1 = seedv, h2 = seedv;                            // (seedv: the seed's halves in vector registers, see k_dna_rolling)
   const int nblocks = K >> 4, tail = K & 15;
@@ -356,15 +368,15 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint
   for (int blk = 0; blk < L; blk++) {
     const int w1 = 2 * blk, w2 = 2 * blk + 1;
     if (blk < nblocks) {
-      h1 = w2_xor(h1, mix_word<FOLD>(w1, M[w1], S[w1]));
+      h1 = w2_xor(h1, mix_word<FOLD, CROSS>(w1, M[w1], S[w1], P[w1]));
       // (rotl(h1, 27) + h2) * 5 + c; in the first block h2 is still the seed: rotl * 5 + (seed * 5 + c)
       if (blk == 0) h1 = w2_mul5_add(w2_rotl(h1, 27), seed * 5 + 0x52dce729u);
       else h1 = w2_mul5_add(w2_add(w2_rotl(h1, 27), h2), 0x52dce729u);
-      h2 = w2_xor(h2, mix_word<FOLD>(w2, M[w2], S[w2]));
+      h2 = w2_xor(h2, mix_word<FOLD, CROSS>(w2, M[w2], S[w2], P[w2]));
       h2 = w2_mul5_add(w2_add_keep(w2_rotl(h2, 31), h1), 0x38495ab5u);
     } else if (blk == nblocks) {
-      if (tail > 8) h2 = w2_xor(h2, mix_word<FOLD>(w2, M[w2], S[w2]));
-      if (tail > 0) h1 = w2_xor(h1, mix_word<FOLD>(w1, M[w1], S[w1]));
+      if (tail > 8) h2 = w2_xor(h2, mix_word<FOLD, CROSS>(w2, M[w2], S[w2], P[w2]));
+      if (tail > 0) h1 = w2_xor(h1, mix_word<FOLD, CROSS>(w1, M[w1], S[w1], P[w1]));
     }
   }
   h1.lo ^= (uint32_t)K; h2.lo ^= (uint32_t)K;          // ^= len (K <= 128)
@@ -397,13 +409,16 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint
 template <int KT, int THREADS, int HB, int L, bool PR = false, bool PK = false, int MINW = (PK ? 8 : 4)>
 __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashParams hp, CandSink sink,
                                                                      int logR, uint32_t stage_cap) {
-  // LDS: static: the product tables (6.8 KiB, folded 11.3 KiB; a compile-time address, so a table read is one
+  // LDS: static: the product tables (6.8 KiB, folded 11.3 KiB, folded with the cross term 12.8 KiB; a compile-time address, so a table read is one
   // ds_read with the table's base as its immediate offset); dynamic: [staged candidates: count,
   // hashes, positions][sequence tile]
   // folded tables (kLutDwordsFold) for the packed tile and k <= 32.  The byte tile and the 4- and 8-limb windows keep the plain
   // ones: the byte tile has no LDS to spare, and at L = 4 the folded look-ups push the kernel over 80 registers (spills).
   constexpr bool FOLD = PK && L == 2;
-  __shared__ __attribute__((aligned(16))) uint32_t lut[FOLD ? kLutDwordsFold : kLutDwords];
+  // the k2 words' cross term from the tables (kLutDwordsCross).  Not in the per-record kernels: held to 64 registers for
+  // eight waves per SIMD, they already spill, and the second dword of the {B, B'} reads makes them spill more.
+  constexpr bool CROSS = FOLD && !PR;
+  __shared__ __attribute__((aligned(16))) uint32_t lut[CROSS ? kLutDwordsCross : (FOLD ? kLutDwordsFold : kLutDwords)];
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* st_ctl = smem;                                    // [0] = count, [2..3] = flush base
   uint64_t* st_hash = reinterpret_cast<uint64_t*>(st_ctl + 4);
@@ -442,11 +457,22 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
     // The high half of a word needs only the product's low dword.  Read out of the 8-byte entries those look-ups
     // touch the even banks only; the packed copy spreads them over all 64 (SQ_LDS_BANK_CONFLICT 43 -> ... per 64 k-mers).
     if (FOLD) {
-      // {T, a.hi, 0}: T1 for the k1 words' multiplier c1, T2 for c2 (the zero entry stays zero: mix(0) = 0)
+      // {T, a.hi, 0}: T1 for the k1 words' multiplier c1, T2'' for c2 (the zero entry stays zero: mix(0) = 0)
       const uint64_t mm = (uint32_t)prod;
-      const uint64_t t = c == kC1 ? (mm << 31) * kC2 : ((mm >> 31) | ((mm & 0x7fffffffu) << 33)) * kC1;
-      reinterpret_cast<uint4*>(lut)[e] = make_uint4((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)(prod >> 32), 0u);
-      lut[4 * kLutEntries + e] = (uint32_t)prod;
+      const uint32_t ahi = (uint32_t)(prod >> 32), ch = (uint32_t)(kC1x2 >> 32);
+      const uint64_t t = c == kC1 ? (mm << 31) * kC2
+                                  : ((mm >> 31) | ((mm & 0x7fffffffu) << 33)) * kC1 + (CROSS ? (uint64_t)(ahi * ch) << 32 : 0ull);
+      reinterpret_cast<uint4*>(lut)[e] = make_uint4((uint32_t)t, (uint32_t)(t >> 32), ahi, 0u);
+      // high halves: full groups of the k1 words -> packed B, of the k2 words -> {B, B'}; the partial group and the zero
+      // entry go to both (a partial group is the high half of a k1 or of a k2 word, depending on k; when it is not that of
+      // a k2 word its {B, B'} entries mean nothing and are never read)
+      const uint32_t B = (uint32_t)prod;
+      const uint32_t he = ent < 256 ? ent : ent - 256u;              // index in a high half's table
+      if (!CROSS) lut[4 * kLutEntries + e] = B;
+      else {
+        if (ent < 256 || ent >= 512) lut[kLutFoldB4 + he] = B;
+        if (ent >= 256) reinterpret_cast<uint2*>(lut + kLutFoldB8)[he] = make_uint2(B, B * ch);
+      }
     } else {
       ptab[e] = prod;
       lut[2 * kLutEntries + e] = (uint32_t)prod;
@@ -462,7 +488,11 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
     if (nb >= 4) ent0 = ((g >> 1) & 1) ? 256u : 0u;
     else if (nb > 0) ent0 = 512u;
     constexpr uint32_t esz = FOLD ? 16u : 8u;                          // bytes per low-half entry
-    gbase[g] = (g & 1) ? esz * kLutEntries + ent0 * 4u : ent0 * esz;  // odd groups (high halves): the packed low dwords
+    gbase[g] = (g & 1) ? esz * kLutEntries + ent0 * 4u : ent0 * esz;  // odd groups (high halves): the packed low dwords (CROSS: see below)
+    if (CROSS && (g & 1)) {                                            // {B, B'} for a k2 word, packed B for a k1 word
+      const uint32_t he = nb >= 4 ? 0u : (nb > 0 ? 256u : 320u);
+      gbase[g] = (g & 2) ? 4u * kLutFoldB8 + he * 8u : 4u * kLutFoldB4 + he * 4u;
+    }
   }
   if (tid == 0) st_ctl[0] = 0;
 
@@ -622,6 +652,9 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
     // ending at base q is {cs, wr} << 2(q+1).  Per base: four v_alignbit and two masks, against two v_alignbit, two
     // v_and_or and five plain shifts/masks for rolling both windows one base at a time.
     constexpr bool kRoll31 = PK && L == 2 && KT == 31;
+    // strand choice by a floating-point minimum: compile-time k <= 31 on the packed two-limb kernels (at k = 32, which the
+    // run-time-k kernel serves, bit 63 can be set)
+    constexpr bool kMinF64 = PK && L == 2 && KT > 0 && KT <= 31;
     uint32_t fa0 = 0, fa1 = 0, cs0 = 0, cs1 = 0, wr = 0;
 
     // one group of four bases; hashing = false for the warm-up groups
@@ -729,7 +762,18 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
           if (kHash) {
             // canonical strand: kmer < rc  <=>  fle < cf (see above), decided from the top limb down
             bool fwd = false;
-            if (L == 2) {
+            if (kMinF64) {
+              // Both windows are below 2^62 (k <= 31): as IEEE doubles they are non-negative, never NaN or infinite (bit 62,
+              // the exponent's top bit, is clear), and ordered like the integers, so the smaller window is ONE v_min_f64
+              // instead of v_cmp_lt_u64 + two v_cndmask_b32.  A window below 2^52 is a DENORMAL: the result is the operand
+              // unchanged only because the kernels run with 64-bit denormals kept (float_denorm_mode_16_64 = 3, the
+              // compiler's default for this target; -fno-fast-math, see csrc/Makefile).  Inline asm, not fmin(): no
+              // canonicalising step.  With denormals flushed every k = 21 window would hash as zero:
+              // tests/test_gpu_dna_strand_min.py fails at once.
+              uint64_t x;
+              asm("v_min_f64 %0, %1, %2" : "=v"(x) : "v"(((uint64_t)fle[1] << 32) | fle[0]), "v"(((uint64_t)cf[1] << 32) | cf[0]));
+              X[q][0] = (uint32_t)x; X[q][L - 1] = (uint32_t)(x >> 32);
+            } else if (L == 2) {
               fwd = (((uint64_t)fle[1] << 32) | fle[0]) < (((uint64_t)cf[1] << 32) | cf[0]);
             } else {
               bool decided = false;
@@ -739,8 +783,10 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
                 if (!decided && f != r) { fwd = f < r; decided = true; }
               }
             }
+            if (!kMinF64) {
 #pragma unroll
-            for (int li = 0; li < L; li++) X[q][li] = fwd ? fle[li] : cf[li];  // chosen strand, first base low
+              for (int li = 0; li < L; li++) X[q][li] = fwd ? fle[li] : cf[li];  // chosen strand, first base low
+            }
           }
         }
         // uniform: some window of this block is complete, and some window of it ends inside a full run (windows end at
@@ -751,9 +797,9 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
 #pragma unroll
           for (int q = 0; q < HB; q++) {
             W2 M[2 * L];
-            uint32_t S[2 * L];                                       // FOLD: the words' product high dwords
+            uint32_t S[2 * L], P[2 * L];                             // FOLD: the words' product high dwords; B' of the k2 words
 #pragma unroll
-            for (int wi = 0; wi < 2 * L; wi++) { M[wi] = W2{0u, 0u}; S[wi] = 0u; }
+            for (int wi = 0; wi < 2 * L; wi++) { M[wi] = W2{0u, 0u}; S[wi] = 0u; P[wi] = 0u; }
 #pragma unroll
             for (int g = 0; g < 4 * L; g++) {
               if (KT == 0 || 4 * g < K) {
@@ -766,11 +812,13 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
                 // zero above their 2k bits, so a partial group indexes inside its 4^nb-entry table and a
                 // group past the k-mer reads entry 0 of the zero table.
                 uint32_t off;                  // digits << 3 (8-byte entries), << 4 (FOLD: 16-byte entries) or << 2 (packed low dwords)
+                                               // (CROSS, high half of a k2 word: << 3, the {B, B'} entries)
                 if ((g & 3) == 0 && FOLD) asm("v_lshlrev_b32_sdwa %0, 4, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(off) : "v"(xw));
                 else if ((g & 3) == 0) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(off) : "v"(xw));
                 else if ((g & 3) == 1) asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(off) : "v"(xw));
                 else if ((g & 3) == 2 && FOLD) asm("v_lshlrev_b32_sdwa %0, 4, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(off) : "v"(xw));
                 else if ((g & 3) == 2) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(off) : "v"(xw));
+                else if ((g & 3) == 3 && CROSS) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(off) : "v"(xw));
                 else asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(off) : "v"(xw));
                 const char* at = reinterpret_cast<const char*>(lut) + gbase[g] + off;
                 if ((g & 1) == 0 && FOLD) {                          // low half, folded: {T, a.hi, 0}
@@ -784,6 +832,10 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
                 } else if ((g & 1) == 0) {                           // low half of the word: full product
                   const uint2 e = *reinterpret_cast<const uint2*>(at);
                   M[g >> 1] = W2{e.x, e.y};
+                } else if (CROSS && (g & 2)) {                       // high half of a k2 word: {B, B'}
+                  const uint2 e = *reinterpret_cast<const uint2*>(at);
+                  S[g >> 1] += e.x;
+                  P[g >> 1] = e.y;
                 } else if (FOLD) {
                   S[g >> 1] += *reinterpret_cast<const uint32_t*>(at);      // high half: (entry << 32), low dword only
                 } else {
@@ -791,7 +843,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
                 }
               }
             }
-            murmur_kmer_pre<L, FOLD>(M, S, K, hp.seed, seedv, ha[q], hb[q]);
+            murmur_kmer_pre<L, FOLD, CROSS>(M, S, P, K, hp.seed, seedv, ha[q], hb[q]);
           }
 #pragma unroll
           for (int q = 0; q < HB; q++)

@@ -104,11 +104,14 @@ __global__ __launch_bounds__(256) void k32(uint32_t* out, uint32_t b, uint32_t c
 #define J_MAD64_V0(n) "v_mad_u64_u32 %" #n ", vcc, %4, %4, 0\n"
 #define J_MOV64(n) "v_mov_b64 %" #n ", %6\n"
 #define J_LSHLADD64_0(n) "v_lshl_add_u64 %" #n ", %" #n ", 0, %6\n"
+#define J_MIN_F64(n) "v_min_f64 %" #n ", %" #n ", %6\n"
 
 template <int OP>
 __global__ __launch_bounds__(256) void k64(uint64_t* out, uint32_t b, uint32_t c, uint64_t d) {
   uint64_t a[4];
   for (int i = 0; i < 4; i++) a[i] = threadIdx.x * 7 + i;
+  // v_min_f64 on integer bit patterns: OP 9 as they are (denormal doubles), OP 10 with an exponent (normal doubles)
+  if (OP == 10) { d |= 0x3ff0000000000000ull; for (int i = 0; i < 4; i++) a[i] |= 0x3ff0000000000000ull; }
   if (OP == 0) BODY4_64(J_MAD64)
   if (OP == 1) BODY4_64(J_LSHLADD64)
   if (OP == 2) BODY4_64(J_SHL64)
@@ -118,6 +121,7 @@ __global__ __launch_bounds__(256) void k64(uint64_t* out, uint32_t b, uint32_t c
   if (OP == 6) BODY4_64(J_MAD64_V0)
   if (OP == 7) BODY4_64(J_MOV64)
   if (OP == 8) BODY4_64(J_LSHLADD64_0)
+  if (OP == 9 || OP == 10) BODY4_64(J_MIN_F64)
   out[blockIdx.x * blockDim.x + threadIdx.x] = a[0] ^ a[1] ^ a[2] ^ a[3];
 }
 
@@ -152,5 +156,6 @@ int main() {
   RUN32(29, "v_dot4_u32_u8") RUN32(30, "v_dot4_u32_u8 acc") RUN32(31, "v_bfi_b32") RUN32(32, "v_or3_b32") RUN32(33, "v_lshl_or_b32")
   RUN64(0, "v_mad_u64_u32") RUN64(1, "v_lshl_add_u64") RUN64(2, "v_lshlrev_b64") RUN64(3, "v_lshrrev_b64")
   RUN64(4, "mad_u64 v,v,v64") RUN64(5, "mad_u64 v,s,0") RUN64(6, "mad_u64 v,v,0") RUN64(7, "v_mov_b64") RUN64(8, "lshl_add_u64 sh0")
+  RUN64(9, "v_min_f64 denorm") RUN64(10, "v_min_f64 normal")
   return 0;
 }
