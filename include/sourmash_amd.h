@@ -56,6 +56,43 @@ int smh_add_sequences_grouped_dev(KmerMinHash *const *sketches, uint32_t n_sketc
                                   uint64_t total_len, const uint64_t *offsets, const uint32_t *groups,
                                   uint32_t n_records, bool force, void *stream);
 
+/* Records cut out of FASTA / FASTQ text ON THE DEVICE: the text, resident in HBM, becomes the layout the
+ * entry points above take -- one dense buffer of sequence bytes plus n+1 offsets -- without a host pass over lines.
+ *   Lines      end at '\n'; one '\r' directly in front of it, or a '\r' that is the text's last byte, belongs to the
+ *              terminator; every other byte belongs to the line.  A line is empty when nothing but the terminator is left.
+ *   FASTA      a line whose first byte is '>' starts a record; its sequence is every following non-header line up to the
+ *              next header, terminators removed; empty lines are ignored; a header followed by a header or by the end of
+ *              the text is a record of length 0.  A non-empty non-header line in front of the first header is an error
+ *              (code 3, the message names its byte offset).
+ *   FASTQ      strict four-line records ('@' line, sequence, '+' line, quality of the sequence's length); the line number
+ *              alone decides a line's role.  Empty lines at the end of the text are dropped; after that a last record of
+ *              three lines whose sequence line is empty is complete.  Anything else is an error (code 3); the message
+ *              names the lowest malformed record in file order as "record N", 0-based.
+ *   AUTO       the first byte of the first non-empty line decides: '>' FASTA, '@' FASTQ, anything else is an error.
+ * Sequence bytes are passed on untouched (lower case, N, IUPAC codes, a stray '\r'): what they mean is add_sequence's
+ * business, exactly as if the caller had cut the records by hand.  The handle owns the compacted bytes (device), the
+ * offsets (host) and the name spans; it keeps NO reference to the text, which may be freed when the parse returns.
+ * A record's name is its header line without the marker byte and the terminator, reported as a span (start, length)
+ * INTO THE TEXT: the library copies no names.  smh_records_parse uploads host text and parses it; *_parse_dev takes
+ * text already in HBM (any alignment).  More than 2^32 - 1 records in one text is an error at parse time.
+ * smh_add_records / smh_add_records_grouped give the result of smh_add_sequences_dev / smh_add_sequences_grouped_dev
+ * on the same records; groups == NULL: record i feeds sketches[i] and n_sketches must equal the number of records. */
+typedef struct SmhRecords SmhRecords;
+enum { SMH_FORMAT_AUTO = 0, SMH_FORMAT_FASTA = 1, SMH_FORMAT_FASTQ = 2 };
+SmhRecords *smh_records_parse(const char *text, uint64_t len, int format);
+SmhRecords *smh_records_parse_dev(const void *text_dev, uint64_t len, int format, void *stream);
+void smh_records_free(SmhRecords *r);
+uint32_t smh_records_len(const SmhRecords *r);
+uint64_t smh_records_total(const SmhRecords *r);          /* kept sequence bytes */
+int smh_records_format(const SmhRecords *r);              /* what AUTO resolved to */
+const void *smh_records_seq_dev(const SmhRecords *r);     /* the compacted bytes, device */
+const uint64_t *smh_records_offsets(const SmhRecords *r); /* n+1 host entries, valid while the handle lives */
+int smh_records_names(const SmhRecords *r, uint64_t *start_out, uint32_t *len_out);   /* n entries each */
+uint32_t smh_records_tile_bytes(void);                    /* bytes per workgroup tile of the parser (tests, tools) */
+int smh_add_records(KmerMinHash *ptr, const SmhRecords *r, bool force);
+int smh_add_records_grouped(KmerMinHash *const *sketches, uint32_t n_sketches, const SmhRecords *r, const uint32_t *groups,
+                            bool force);
+
 /* add_hash over an array (reference src/lib.rs:412-417 add_many) */
 int smh_add_many(KmerMinHash *ptr, const uint64_t *hashes, uint64_t n);
 
@@ -316,7 +353,7 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
 /* HIP-event timing of the library's kernels, on the stream they run on.
  * name: "dna_rolling", "dna_generic", "protein_fused", "translate", "hash_windows", "compare_wave", "compare_few",
  * "compare_pair", "compare_fill", "compare_comp", "compare_tiled" (the plain and the pipelined tiled kernels of one call together),
- * "sbt_bins", "sbt_nodes", "sbt_leaves", "sbt_build". */
+ * "sbt_bins", "sbt_nodes", "sbt_leaves", "sbt_build", "parse_scan" (tile summaries and their scan), "parse_compact". */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -97,6 +97,18 @@ _SIGS = {
     "smh_add_sequences_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint32, C.c_bool, C.c_void_p]),
     "smh_add_sequences_grouped": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_char_p, u64p, C.POINTER(C.c_uint32), C.c_uint32, C.c_bool]),
     "smh_add_sequences_grouped_dev": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, u64p, C.POINTER(C.c_uint32), C.c_uint32, C.c_bool, C.c_void_p]),
+    "smh_records_parse": (C.c_void_p, [C.c_char_p, C.c_uint64, C.c_int]),
+    "smh_records_parse_dev": (C.c_void_p, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "smh_records_free": (None, [C.c_void_p]),
+    "smh_records_len": (C.c_uint32, [C.c_void_p]),
+    "smh_records_total": (C.c_uint64, [C.c_void_p]),
+    "smh_records_format": (C.c_int, [C.c_void_p]),
+    "smh_records_seq_dev": (C.c_void_p, [C.c_void_p]),
+    "smh_records_offsets": (u64p, [C.c_void_p]),
+    "smh_records_names": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_uint32)]),
+    "smh_records_tile_bytes": (C.c_uint32, []),
+    "smh_add_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_bool]),
+    "smh_add_records_grouped": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_bool]),
     "smh_add_many": (C.c_int, [C.c_void_p, u64p, C.c_uint64]),
     "smh_add_many_with_abund": (C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64]),
     "smh_check_compatible": (C.c_int, [C.c_void_p, C.c_void_p]),

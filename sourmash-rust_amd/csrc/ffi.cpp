@@ -463,6 +463,179 @@ int smh_add_sequences_grouped_dev(KmerMinHash* const* sketches, uint32_t n_sketc
   });
 }
 
+// ------------------------------------------------------------------ records parsed on the device
+
+}  // extern "C"
+
+// The records of one FASTA / FASTQ text: the compacted sequence bytes and the name spans in HBM, the offsets on the host
+// (page-locked: the sketching paths walk them and upload them again).  Holds no reference to the text.
+struct SmhRecords {
+  void* seq = nullptr; size_t seq_cap = 0;          // total + 64 bytes, from the block pool
+  void* names = nullptr; size_t names_cap = 0;      // name_start[n], name_end[n]
+  uint64_t* offsets = nullptr;                      // n + 1, hipHostMalloc
+  uint32_t n = 0;
+  uint64_t total = 0;
+  int format = 0;
+  ~SmhRecords() {
+    if (seq) smh::device_pool_free(seq, seq_cap, true);
+    if (names) smh::device_pool_free(names, names_cap, true);
+    if (offsets) (void)hipHostFree(offsets);
+  }
+};
+
+namespace {
+
+struct PoolBlock {      // a transient device block
+  void* ptr = nullptr; size_t cap = 0;
+  explicit PoolBlock(size_t need) { ptr = smh::device_pool_alloc(need, &cap); }
+  ~PoolBlock() { if (ptr) smh::device_pool_free(ptr, cap, true); }
+  PoolBlock(const PoolBlock&) = delete;
+  PoolBlock& operator=(const PoolBlock&) = delete;
+};
+
+SmhRecords* parse_records(const uint8_t* text, uint64_t len, int format, hipStream_t s) {
+  if (format != smh::kFormatAuto && format != smh::kFormatFasta && format != smh::kFormatFastq)
+    throw Error(smh::kMsg, "unknown sequence file format " + std::to_string(format));
+  auto rec = std::make_unique<SmhRecords>();
+  PoolBlock small(256);
+  auto* totals_dev = static_cast<smh::ParseTotals*>(small.ptr);
+  if (format == smh::kFormatAuto) {
+    uint64_t first = ~0ull;
+    if (len) {
+      auto* first_dev = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(small.ptr) + 128);
+      smh::launch_first_content(text, len, first_dev, s);
+      HIP_CHECK(hipMemcpyAsync(&first, first_dev, 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (first == ~0ull || first == '>') format = smh::kFormatFasta;      // a text without content holds no records
+    else if (first == '@') format = smh::kFormatFastq;
+    else throw Error(smh::kMsg, "neither FASTA nor FASTQ: the first non-empty line starts with byte " + std::to_string(first));
+  }
+  rec->format = format;
+  smh::ParseTotals tot{0, 0, 0, 0, ~0ull};
+  if (len) {
+    PoolBlock ws(smh::parse_workspace_bytes(text, len));
+    const smh::ParseTileIn first{0, 0, 0, 0, 0};
+    auto& dev = smh::Device::get();
+    dev.prof_begin(s);
+    smh::launch_parse_scan(format, text, len, first, ws.ptr, totals_dev, s);
+    dev.prof_end("parse_scan", s);
+    HIP_CHECK(hipMemcpyAsync(&tot, totals_dev, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (tot.n_records > 0xffffffffull) throw Error(smh::kMsg, "more than 2^32 - 1 records in one text");
+    if (tot.total > len) smh::throw_internal("parse: more sequence bytes than text");
+    const uint64_t n = tot.n_records;
+    rec->seq = smh::device_pool_alloc(tot.total + 64, &rec->seq_cap);
+    rec->names = smh::device_pool_alloc(n * 16 + 16, &rec->names_cap);
+    PoolBlock offs(n * 8 + 8);
+    auto* names = static_cast<uint64_t*>(rec->names);
+    if (n) HIP_CHECK(hipMemsetAsync(rec->names, 0, n * 16, s));
+    dev.prof_begin(s);
+    smh::launch_parse_compact(format, text, len, ws.ptr, tot, static_cast<uint8_t*>(rec->seq), static_cast<uint64_t*>(offs.ptr),
+                              names, names + n, totals_dev, s);
+    dev.prof_end("parse_compact", s);
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&rec->offsets), (n + 1) * 8, hipHostMallocDefault));
+    if (n) HIP_CHECK(hipMemcpyAsync(rec->offsets, offs.ptr, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&tot.err, &totals_dev->err, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    rec->offsets[n] = tot.total;
+  } else {
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&rec->offsets), 8, hipHostMallocDefault));
+    rec->offsets[0] = 0;
+  }
+  if (tot.err != ~0ull) {
+    if (format == smh::kFormatFasta)
+      throw Error(smh::kMsg, "FASTA: sequence data in front of the first header at byte " + std::to_string(tot.err));
+    throw Error(smh::kMsg, "FASTQ: malformed record " + std::to_string(tot.err) +
+                               " (no '@', no '+', quality and sequence lengths differ, or the record is cut short)");
+  }
+  rec->n = (uint32_t)tot.n_records;
+  rec->total = tot.total;
+  return rec.release();
+}
+
+}  // namespace
+
+extern "C" {
+
+SmhRecords* smh_records_parse_dev(const void* text_dev, uint64_t len, int format, void* stream) {
+  return pad<SmhRecords*>([&] {
+    auto& dev = smh::Device::get();
+    if (len) require(text_dev, "text_dev");
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    return parse_records(static_cast<const uint8_t*>(text_dev), len, format, dev.user_stream(stream));
+  });
+}
+
+SmhRecords* smh_records_parse(const char* text, uint64_t len, int format) {
+  return pad<SmhRecords*>([&] {
+    auto& dev = smh::Device::get();
+    if (len) require(text, "text");
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.stream();
+    PoolBlock up(len + 64);
+    if (len) HIP_CHECK(hipMemcpyAsync(up.ptr, text, len, hipMemcpyHostToDevice, s));
+    return parse_records(static_cast<const uint8_t*>(up.ptr), len, format, s);
+  });
+}
+
+void smh_records_free(SmhRecords* r) { delete r; }
+uint32_t smh_records_len(const SmhRecords* r) { return r ? r->n : 0; }
+uint64_t smh_records_total(const SmhRecords* r) { return r ? r->total : 0; }
+int smh_records_format(const SmhRecords* r) { return r ? r->format : 0; }
+const void* smh_records_seq_dev(const SmhRecords* r) { return r ? r->seq : nullptr; }
+const uint64_t* smh_records_offsets(const SmhRecords* r) { return r ? r->offsets : nullptr; }
+uint32_t smh_records_tile_bytes(void) { return smh::kParseTileBytes; }
+
+int smh_records_names(const SmhRecords* r, uint64_t* start_out, uint32_t* len_out) {
+  return pad_code([&] {
+    require(r, "r");
+    if (r->n == 0) return;
+    require(start_out, "start_out"); require(len_out, "len_out");
+    auto& dev = smh::Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.stream();
+    std::vector<uint64_t> ends(r->n);
+    const uint64_t* names = static_cast<const uint64_t*>(r->names);
+    HIP_CHECK(hipMemcpyAsync(start_out, names, (size_t)r->n * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(ends.data(), names + r->n, (size_t)r->n * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < r->n; i++) {
+      const uint64_t l = ends[i] >= start_out[i] ? ends[i] - start_out[i] : 0;
+      if (l > 0xffffffffull) throw Error(smh::kMsg, "a record name longer than 2^32 - 1 bytes");
+      len_out[i] = (uint32_t)l;
+    }
+  });
+}
+
+int smh_add_records(KmerMinHash* ptr, const SmhRecords* r, bool force) {
+  return pad_code([&] {
+    require(ptr, "ptr"); require(r, "r");
+    ptr->add_sequences_device(static_cast<const uint8_t*>(r->seq), r->total, r->offsets, r->n, force,
+                              smh::Device::get().user_stream(nullptr), nullptr);
+  });
+}
+
+int smh_add_records_grouped(KmerMinHash* const* sketches, uint32_t n_sketches, const SmhRecords* r, const uint32_t* groups,
+                            bool force) {
+  return pad_code([&] {
+    require(r, "r");
+    if (r->n == 0) return;
+    require(sketches, "sketches");
+    for (uint32_t g = 0; g < n_sketches; g++) require(sketches[g], "sketches[g]");
+    std::vector<uint32_t> own;
+    if (!groups) {
+      if (n_sketches != r->n) smh::throw_internal("one sketch per record needs as many sketches as records");
+      own.resize(r->n);
+      for (uint32_t i = 0; i < r->n; i++) own[i] = i;
+      groups = own.data();
+    }
+    std::vector<smh::KmerMinHash*> mhs(sketches, sketches + n_sketches);
+    smh::add_sequences_grouped(mhs.data(), n_sketches, static_cast<const uint8_t*>(r->seq), r->total, r->offsets, groups, r->n,
+                               force, smh::Device::get().user_stream(nullptr), nullptr);
+  });
+}
+
 int smh_add_many(KmerMinHash* ptr, const uint64_t* hashes, uint64_t n) {
   return pad_code([&] { require(ptr, "ptr"); if (n) require(hashes, "hashes"); ptr->materialize(); ptr->add_many(hashes, n); });
 }

@@ -97,6 +97,35 @@ void launch_filter_hashes(const uint64_t* hashes, const HashParams& p, const Can
 void launch_synth_dna(uint8_t* out, uint64_t start, uint64_t len, uint64_t seed, uint64_t n_every,
                       hipStream_t s);
 
+// --- parse_kernels.hip -----------------------------------------------------------------
+// FASTA / FASTQ text in device memory -> dense sequence bytes + record offsets + name spans.
+enum ParseFormat : int { kFormatAuto = 0, kFormatFasta = 1, kFormatFastq = 2 };
+constexpr uint32_t kParseTileBytes = 4096;   // tiles are cut on 16-byte boundaries of the address: the first may hold fewer text bytes
+// The state a tile is entered in.  The first tile's is the caller's: a text parsed in one go starts with all zero.
+struct ParseTileIn {
+  uint64_t outpos;   // kept bytes in front of the tile
+  uint64_t count;    // FASTA: records started in front of it; FASTQ: '\n' bytes in front of it (= the running line's number)
+  int64_t bal;       // FASTQ: sequence bytes - quality bytes in front of it
+  uint32_t cls;      // FASTA: class of the running line (0 none, 1 sequence, 2 header)
+  uint32_t pad;
+};
+struct ParseTotals {
+  uint64_t n_records, total, lines;   // lines: FASTQ, after the empty ones at the end are dropped
+  int64_t balance;
+  uint64_t err;                       // ~0: none; FASTA: byte offset of data in front of the first header; FASTQ: lowest malformed record
+};
+size_t parse_workspace_bytes(const void* text, uint64_t len);
+// *out_dev = the first byte of the text that belongs to no line terminator (~0: there is none)
+void launch_first_content(const uint8_t* text, uint64_t len, uint64_t* out_dev, hipStream_t s);
+// passes 1 and 2: tile summaries and their scan into `workspace`; *totals_dev is written (err included)
+void launch_parse_scan(int format, const uint8_t* text, uint64_t len, const ParseTileIn& first, void* workspace,
+                       ParseTotals* totals_dev, hipStream_t s);
+// pass 3, with the totals read back: out (16-byte aligned, totals.total bytes), offsets / name_start / name_end
+// (totals.n_records entries each); totals_dev->err is lowered by the format checks
+void launch_parse_compact(int format, const uint8_t* text, uint64_t len, const void* workspace, const ParseTotals& totals,
+                          uint8_t* out, uint64_t* offsets_dev, uint64_t* name_start_dev, uint64_t* name_end_dev,
+                          ParseTotals* totals_dev, hipStream_t s);
+
 // --- sort.hip -----------------------------------------------------------------------
 // LSD radix sort, ping-pong between (k0,v0) and (k1,v1); returns which pair holds the result.
 // Only the byte passes [first_pass, last_pass) are run (default: all eight): a stable sort by a bit

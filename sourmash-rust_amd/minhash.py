@@ -140,6 +140,23 @@ class KmerMinHash:
         call(L.smh_add_sequences_grouped_dev, arr, len(sketches), C.c_void_p(dev_ptr), total_len, off.ctypes.data_as(u64p),
              grp.ctypes.data_as(C.POINTER(C.c_uint32)), off.size - 1, bool(force), C.c_void_p(stream or 0))
 
+    def add_records(self, records, force=False):
+        """Every record of a fastx.Records handle (parsed on the device), as add_sequences on the same records."""
+        call(self._L.smh_add_records, self._p, records._p, bool(force))
+
+    @staticmethod
+    def add_records_grouped(sketches, records, groups=None, force=False):
+        """Record r of a fastx.Records handle feeds sketches[groups[r]]; groups=None: record i feeds sketches[i]."""
+        L = sketches[0]._L
+        grp = None
+        if groups is not None:
+            grp = np.ascontiguousarray(groups, dtype=np.uint32)
+            if grp.size != len(records):
+                raise ValueError("one group per record")
+        arr = (C.c_void_p * len(sketches))(*[m._p for m in sketches])
+        call(L.smh_add_records_grouped, arr, len(sketches), records._p,
+             grp.ctypes.data_as(C.POINTER(C.c_uint32)) if grp is not None else None, bool(force))
+
     # --- a scaled sketch's state as device arrays (additive ABI; the cross-rank union, distributed.union_across_ranks)
     def export_dev(self, mins_t=None, abunds_t=None, stream=None):
         """copies the ascending hashes (and abundances) into CUDA int64 tensors; returns the number of hashes
