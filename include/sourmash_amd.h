@@ -224,6 +224,33 @@ void smh_index_drop_dictionary(SmhIndex *index);
 int smh_index_compare(SmhIndex *rows, SmhIndex *cols, double *jaccard, uint64_t *common, uint64_t *size,
                       uint64_t *count_common, double *containment);
 
+/* Gather: the greedy decomposition of a query against the resident nodes (the min-set-cover loop behind `sourmash gather`;
+ * the reference crate has none, so the rules are fixed here -- DESIGN.md 3.9, restated in tests/gather_restatement.py).
+ *   Inputs     the n resident sketches S_0 .. S_{n-1}; the query Q, position p = the p-th hash in ascending order;
+ *              threshold_common (0 is read as 1); rows_capacity.
+ *   Rounds     A_0 = every position of Q.  Round r: c_i = |A_r ^ S_i|; best = the LOWEST i with the largest c_i (the tie
+ *              rule of smh_most_common); if c_best < threshold_common or r == rows_capacity the call ends; else
+ *              rows[r] = { match = best, common_remaining = c_best, common_original = |Q ^ S_best|, size_match = |S_best|,
+ *              abund_sum = sum of the query's abundances over A_r ^ S_best (1 per hash when the query tracks none) },
+ *              assigned[p] = r for every p of A_r ^ S_best, and A_{r+1} = A_r \ S_best.
+ *   Outputs    *n_rows rows; assigned (nullable, |Q| entries): the round that consumed each position, 0xffffffff for the
+ *              positions nobody consumed.  An empty query, an empty index, empty sketches or a query that shares nothing
+ *              give zero rows and no error.
+ *   Errors     only scaled sketches take part: a query or ANY resident node with num != 0 is SOURMASH_ERROR_CODE_MSG
+ *              (decided at this call: such an index still serves smh_index_find); a query that is not compatible with
+ *              every node is 101-104 as smh_check_compatible reports it (O(1) when the nodes agree among themselves);
+ *              rows == NULL with rows_capacity > 0 is refused.
+ * A query whose state lives in HBM (a sketch just built on the device) is read there: nothing is copied to the host.
+ * The membership pass over the resident hashes runs once per call; a round is two small launches without host work, and
+ * smh_gather_rounds_per_sync() rounds are queued between two read-backs of 8 bytes. */
+typedef struct SmhGatherRow {
+  uint32_t match, common_remaining, common_original, size_match;
+  uint64_t abund_sum;
+} SmhGatherRow;   /* 24 bytes */
+int smh_index_gather(SmhIndex *index, const KmerMinHash *query, uint32_t threshold_common, SmhGatherRow *rows,
+                     uint32_t rows_capacity, uint32_t *n_rows, uint32_t *assigned);
+uint32_t smh_gather_rounds_per_sync(void);   /* rounds queued between two read-backs (tests, tools) */
+
 /* deterministic synthetic DNA of SURVEY.md 8d written to device memory (benchmark input) */
 int smh_synth_dna_dev(void *out_dev, uint64_t start, uint64_t len, uint64_t seed, uint64_t n_every,
                       void *stream);
@@ -353,7 +380,9 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
 /* HIP-event timing of the library's kernels, on the stream they run on.
  * name: "dna_rolling", "dna_generic", "protein_fused", "translate", "hash_windows", "compare_wave", "compare_few",
  * "compare_pair", "compare_fill", "compare_comp", "compare_tiled" (the plain and the pipelined tiled kernels of one call together),
- * "sbt_bins", "sbt_nodes", "sbt_leaves", "sbt_build", "parse_scan" (tile summaries and their scan), "parse_compact". */
+ * "sbt_bins", "sbt_nodes", "sbt_leaves", "sbt_build", "parse_scan" (tile summaries and their scan), "parse_compact",
+ * "gather_hits" (the membership pass), "gather_invert" (degree scan + inverted lists), "gather_rounds" (one entry per batch
+ * of smh_gather_rounds_per_sync() rounds). */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -30,6 +30,11 @@ class SmhCompareStats(C.Structure):
                 ("span_halvings", C.c_uint32), ("prefetched_after_halving", C.c_uint32)]
 
 
+class SmhGatherRow(C.Structure):
+    _fields_ = [("match", C.c_uint32), ("common_remaining", C.c_uint32), ("common_original", C.c_uint32),
+                ("size_match", C.c_uint32), ("abund_sum", C.c_uint64)]
+
+
 def build(force=False):
     """Compile the HIP/C++ sources in-tree (hipcc --offload-arch=gfx950)."""
     src = os.path.join(HERE, "csrc")
@@ -138,6 +143,9 @@ _SIGS = {
     "smh_index_find": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_bool, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smh_index_most_common": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), u64p]),
     "smh_index_compare": (C.c_int, [C.c_void_p, C.c_void_p, f64p, u64p, u64p, u64p, f64p]),
+    "smh_index_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SmhGatherRow), C.c_uint32, C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint32)]),
+    "smh_gather_rounds_per_sync": (C.c_uint32, []),
     "smh_release_workspace": (C.c_int, []),
     "smh_pool_set_limit": (None, [C.c_uint64]),
     "smh_pool_bytes": (C.c_uint64, []),

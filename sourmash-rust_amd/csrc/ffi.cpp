@@ -1,5 +1,6 @@
 // ffi.cpp -- the C ABI: every symbol of include/sourmash.h (the reference's surface, restating
 // src/ffi.rs and src/utils.rs) and the additive MI355X entry points of include/sourmash_amd.h.
+#include <cstddef>
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
@@ -775,6 +776,10 @@ struct SmhIndex {
   std::vector<smh::KmerMinHash> params;   // parameters only (mins cleared): check_compatible per node
   uint32_t max_len = 0;
   uint32_t n = 0;
+  // what gather asks of the whole set, decided once: every node has the parameters of node 0 (the query is then checked
+  // against that one block), and whether any node is a bottom-`num` sketch
+  bool uniform = true;
+  bool any_num = false;
   // the dictionary of the resident set (dense ranks, components, frequent hashes), built by the first all-vs-all compare
   // of the index with itself and kept: later ones skip the pre-pass (the nodes of an index never change)
   smh::CollectionDict* dict = nullptr;
@@ -803,6 +808,9 @@ SmhIndex* smh_index_new(KmerMinHash* const* nodes, uint32_t n_nodes) {
       idx->h_nums[i] = nodes[i]->num;
       smh::KmerMinHash p(nodes[i]->num, nodes[i]->ksize, nodes[i]->is_protein, nodes[i]->seed, nodes[i]->max_hash, false);
       idx->params.push_back(p);
+      const smh::KmerMinHash& p0 = idx->params[0];
+      idx->uniform &= p.ksize == p0.ksize && p.is_protein == p0.is_protein && p.max_hash == p0.max_hash && p.seed == p0.seed;
+      idx->any_num |= p.num != 0;
     }
     auto& dev = smh::Device::get();
     std::lock_guard<std::recursive_mutex> lock(dev.mutex());
@@ -895,6 +903,68 @@ int smh_index_most_common(SmhIndex* index, const KmerMinHash* leaf, uint32_t* be
     if (best_common) *best_common = mx;
   });
 }
+
+static_assert(sizeof(SmhGatherRow) == 24 && sizeof(smh::GatherRow) == 24, "SmhGatherRow is 24 bytes");
+static_assert(offsetof(SmhGatherRow, abund_sum) == 16 && offsetof(smh::GatherRow, abund_sum) == 16, "SmhGatherRow layout");
+
+int smh_index_gather(SmhIndex* index, const KmerMinHash* query, uint32_t threshold_common, SmhGatherRow* rows,
+                     uint32_t rows_capacity, uint32_t* n_rows, uint32_t* assigned) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();   // first: without a device the call says so, whatever it was handed
+    require(index, "index"); require(query, "query"); require(n_rows, "n_rows");
+    *n_rows = 0;
+    if (rows_capacity) require(rows, "rows");
+    if (query->num != 0) throw Error(smh::kMsg, "gather: the query is a num sketch; only scaled sketches (num == 0) can be gathered");
+    if (index->any_num) throw Error(smh::kMsg, "gather: the index holds a num sketch; only scaled sketches (num == 0) can be gathered");
+    if (index->n) {
+      if (index->uniform) index->params[0].check_compatible(*query);
+      else for (auto& p : index->params) p.check_compatible(*query);   // nodes that differ: one of them refuses the query
+    }
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.stream();
+    query->flush_pending();
+    // the query where it lives: a state in HBM is read there (uniq + counts or run starts), a host state is uploaded once
+    smh::GatherQuery q;
+    smh::DeviceBuffer up;
+    uint64_t lq = 0;
+    if (query->dev) {
+      const smh::DeviceSketch& S = *query->dev;
+      lq = S.n;
+      q.hashes = S.uniq.as<uint64_t>();
+      if (query->has_abunds) {
+        if (S.has_counts) q.counts = S.counts.as<uint64_t>();
+        else if (S.has_runs) { q.starts = S.starts.as<uint32_t>(); q.total = (uint32_t)S.total; }
+        else smh::throw_internal("gather: the query's device state carries no abundances");
+      }
+    } else {
+      lq = query->mins.size();
+      if (query->has_abunds && query->abunds.size() != lq)
+        smh::throw_internal("gather: the query's abundance vector does not match its hashes (quirks Q5/Q6)");
+      if (lq) {
+        up.ensure(lq * 8 * (query->has_abunds ? 2 : 1));
+        HIP_CHECK(hipMemcpyAsync(up.ptr, query->mins.data(), lq * 8, hipMemcpyHostToDevice, s));
+        q.hashes = up.as<uint64_t>();
+        if (query->has_abunds) {
+          HIP_CHECK(hipMemcpyAsync(up.as<uint64_t>() + lq, query->abunds.data(), lq * 8, hipMemcpyHostToDevice, s));
+          q.counts = up.as<uint64_t>() + lq;
+        }
+      }
+    }
+    if (lq >= 0xffffffffull) smh::throw_internal("gather: a query of 2^32 - 1 or more hashes");
+    q.n = (uint32_t)lq;
+    if (index->n == 0 || lq == 0) {
+      if (assigned && lq) std::fill(assigned, assigned + lq, 0xffffffffu);
+      return;
+    }
+    smh::SketchSet I;
+    I.hashes = index->hashes.as<uint64_t>(); I.offsets = index->offsets.as<uint64_t>(); I.n = index->n;
+    I.h_offsets = index->h_offsets.data();
+    *n_rows = smh::gather_run(I, index->max_len, q, threshold_common, reinterpret_cast<smh::GatherRow*>(rows), rows_capacity,
+                              assigned, dev, s);
+    up.release_after_sync();   // gather_run returns with the stream idle
+  });
+}
+uint32_t smh_gather_rounds_per_sync(void) { return smh::kGatherRoundsPerSync; }
 
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {

@@ -1,5 +1,5 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
-// compare_kernels.hip).  Plain structs and pointers; no torch types anywhere.
+// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip).  Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -266,5 +266,30 @@ void launch_compare_block(const SketchSet& rows, const SketchSet& cols, uint32_t
                           const uint32_t* row_nums, const CompareOut& out, Device& dev,
                           hipStream_t s, uint32_t max_row_len, uint32_t max_col_len, uint64_t nr_elems,
                           uint64_t nc_elems, bool same_sets = false);   // same_sets: rows and cols are one CSR
+
+// --- gather_kernels.hip ----------------------------------------------------------------
+// Gather: the greedy decomposition of one scaled query against a resident set.  In round r the sketch with
+// the largest count of still unassigned query positions wins (lowest index on ties), is reported as row r and its positions
+// are labelled r; it ends when the best count is below `threshold` (0 is read as 1) or `capacity` rows are written.
+struct GatherRow {
+  uint32_t match;              // index of the winning sketch
+  uint32_t common_remaining;   // |A_r ^ S_match|: query positions it consumed
+  uint32_t common_original;    // |Q ^ S_match|
+  uint32_t size_match;         // |S_match|
+  uint64_t abund_sum;          // sum of the query's abundances over the consumed positions
+};
+struct GatherQuery {           // ascending distinct hashes in device memory; abundances: u64 counts, or run starts, or none (1 each)
+  const uint64_t* hashes = nullptr;
+  uint32_t n = 0;
+  const uint64_t* counts = nullptr;
+  const uint32_t* starts = nullptr;   // abundance p = starts[p + 1] - starts[p], the last run ends at total
+  uint32_t total = 0;
+};
+constexpr uint32_t kGatherRoundsPerSync = 32;   // rounds queued between two 8-byte read-backs of {done, rounds}
+// idx needs h_offsets.  rows_host: room for min(capacity, idx.n) rows; assigned_host (nullable): q.n entries, the round that
+// consumed each query position or 0xffffffff.  Returns the number of rows; the stream is idle when it returns, and every
+// block it took from the device pool is back there.
+uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q, uint32_t threshold, GatherRow* rows_host,
+                    uint32_t capacity, uint32_t* assigned_host, Device& dev, hipStream_t s);
 
 }  // namespace smh

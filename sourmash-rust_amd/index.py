@@ -2,15 +2,39 @@
 
   LinearIndex.find          reference src/index/linear.rs:25-45 + src/index/search.rs:3-9
   most_common (scaffold)    reference src/index/sbt.rs:361-370 (nearest leaf = arg-max count_common)
+  ResidentIndex.gather      the greedy decomposition of a query (no counterpart in the reference crate: the rules are those
+                            of include/sourmash_amd.h, smh_index_gather)
 
 A "node" here is a KmerMinHash (the reference's Leaf wraps a Signature whose first sketch is used,
 src/index.rs:108-161)."""
+import collections
 import ctypes as C
+import math
 
 import numpy as np
 
-from ._lib import lib, u64p
+from ._lib import SmhGatherRow, lib, u64p
 from .errors import call
+
+UNASSIGNED = 0xFFFFFFFF
+
+GatherRecord = collections.namedtuple("GatherRecord", [
+    "match", "common_remaining", "common_original", "size_match", "abund_sum",   # the integers of SmhGatherRow
+    "f_orig_query",        # common_original / |query|
+    "f_match",             # common_remaining / size_match
+    "f_unique_to_query",   # common_remaining / |query|
+    "f_unique_weighted",   # abund_sum / sum of all the query's abundances
+    "average_abund",       # abund_sum / common_remaining
+    "median_abund", "std_abund",   # numpy median / std over the abundances of the positions this row consumed
+    "remaining_bp"])       # scaled * (query positions nobody has consumed after this row)
+GatherResult = collections.namedtuple("GatherResult", ["rows", "assigned"])
+
+
+def scaled_of_max_hash(max_hash):
+    """the `scaled` a max_hash stands for: max_hash = 2^64 // scaled, so scaled = round(2^64 / max_hash)"""
+    if max_hash <= 0:
+        raise ValueError("not a scaled sketch: max_hash is 0")
+    return max(1, ((1 << 64) + max_hash // 2) // max_hash)
 
 
 def search_minhashes(nodes, query, threshold):
@@ -64,6 +88,46 @@ class ResidentIndex:
         pos, cm = C.c_uint32(), C.c_uint64()
         call(self._L.smh_index_most_common, self._h, leaf._p, C.byref(pos), C.byref(cm))
         return pos.value, cm.value
+
+    def gather(self, query, threshold_bp=0, scaled=None, max_rows=None, abund_stats=True):
+        """Greedy decomposition of `query` against the resident sketches (smh_index_gather): GatherResult(rows, assigned).
+        rows: one GatherRecord per round; assigned: uint32 numpy array, the round that consumed each query position (the
+        hashes in ascending order) or UNASSIGNED.  threshold_common = ceil(threshold_bp / scaled); scaled defaults to the
+        value the query's max_hash stands for.  The integers come from the device; the floats are derived here.  The
+        device call leaves a query that lives in HBM where it is; f_unique_weighted, median_abund and std_abund of a query
+        that tracks abundances need those on the host afterwards -- abund_stats=False leaves the three None instead."""
+        if scaled is None:
+            mx = query.max_hash
+            scaled = scaled_of_max_hash(mx) if mx else 1   # (a num query is refused by the call below)
+        thr = int(math.ceil(threshold_bp / scaled))
+        nq = len(query)
+        cap = len(self) if max_rows is None else int(max_rows)
+        rows = (SmhGatherRow * max(min(cap, len(self)), 1))()
+        assigned = np.full(nq, UNASSIGNED, dtype=np.uint32)
+        n_rows = C.c_uint32()
+        call(self._L.smh_index_gather, self._h, query._p, thr, rows, cap, C.byref(n_rows),
+             assigned.ctypes.data_as(C.POINTER(C.c_uint32)))
+        # a query without abundances weighs 1 per hash: its statistics are known without looking at it
+        ab = query.abunds_np() if query.track_abundance and abund_stats and n_rows.value else None
+        flat = not query.track_abundance
+        total_ab = nq if flat else int(ab.sum(dtype=np.uint64)) if ab is not None else None
+        out, left = [], nq
+        if ab is not None:   # the positions of round r, for every r at once
+            order = np.argsort(assigned, kind="stable")
+            cuts = np.searchsorted(assigned[order], np.arange(n_rows.value + 1, dtype=np.uint32))
+        for r in range(n_rows.value):
+            w = rows[r]
+            left -= w.common_remaining
+            mine = ab[order[cuts[r]:cuts[r + 1]]] if ab is not None else None
+            out.append(GatherRecord(
+                w.match, w.common_remaining, w.common_original, w.size_match, w.abund_sum,
+                w.common_original / nq, w.common_remaining / w.size_match, w.common_remaining / nq,
+                w.abund_sum / total_ab if total_ab is not None else None,
+                w.abund_sum / w.common_remaining,
+                1.0 if flat else float(np.median(mine)) if ab is not None else None,
+                0.0 if flat else float(np.std(mine)) if ab is not None else None,
+                scaled * left))
+        return GatherResult(out, assigned)
 
     def compare(self, other, want=("jaccard",)):
         n, m = len(self), len(other)
