@@ -251,6 +251,70 @@ int smh_index_gather(SmhIndex *index, const KmerMinHash *query, uint32_t thresho
                      uint32_t rows_capacity, uint32_t *n_rows, uint32_t *assigned);
 uint32_t smh_gather_rounds_per_sync(void);   /* rounds queued between two read-backs (tests, tools) */
 
+/* Angular similarity on abundances: what `sourmash compare` and `sourmash search` report by default for sketches that
+ * track abundances.  The reference crate has no weighted compare, so the rules are fixed here -- DESIGN.md 3.10, restated
+ * in tests/angular_restatement.py.  For two sketches A and B that both track abundances, hashes ascending and distinct, one
+ * abundance per hash:
+ *   norm2(A)   the sum of a_h^2 over the hashes h of A.
+ *   dot(A, B)  the sum of a_h * b_h over the hashes h that A and B both hold.
+ *   Exactness  both are exact unsigned 64-bit integers.  A sketch whose norm2 does not fit 64 bits is refused with
+ *              SOURMASH_ERROR_CODE_MSG and the message names the node (the LOWEST one when several are bad); that includes
+ *              any single abundance of 2^32 or more.  So every accepted abundance fits 32 bits, and since
+ *              dot <= sqrt(norm2(A) * norm2(B)) <= max(norm2), the dot of two accepted sketches cannot overflow.
+ *   cosine     as double, in exactly this order: c = (double)dot / (sqrt((double)norm2A) * sqrt((double)norm2B)); every
+ *              conversion rounds to nearest; IEEE sqrt, multiply and divide (no fast math, no reciprocal).  dot == 0 or a
+ *              norm of 0: c = 0.0.  c > 1.0: c = 1.0.  (For a sketch against itself the literal formula can land one or
+ *              two ulp below 1.0 -- sqrt(n) * sqrt(n) need not round back to n -- so the matrix of an index with ITSELF
+ *              sets its diagonal, see smh_index_angular.)
+ *   angular    as double: 0.0 when c == 0.0, 1.0 when c == 1.0, else 1.0 - (2.0 * acos(c)) / M_PI.
+ *   num        does not truncate: every hash of both sketches takes part, as in sourmash.
+ *   Compatible check_compatible applies to every pair: 101-104 as smh_check_compatible reports them.
+ *   Refused    with SOURMASH_ERROR_CODE_MSG: a sketch that does not track abundances; a sketch whose abundance vector does
+ *              not match its hashes (quirks Q5/Q6 after a merge; smh_sketch_export_dev refuses the same case).
+ *   Empty      sketches are no error: dot = 0, cosine = 0.0, angular = 0.0.
+ * Argument and parameter checks come before the device is touched.
+ *
+ * smh_index_has_abundances  true when EVERY node tracked abundances, with a vector that matched its hashes, when the index
+ *                           was built.  Such an index keeps the abundances narrowed to 32 bits on the host (a copy, like the
+ *                           hashes); the first angular call moves them to HBM (4 B per hash) and computes the norms.  find,
+ *                           compare and gather on the index are unchanged, and an index nobody asks pays no HBM.
+ * smh_index_norms2          norm2 of every node, n entries.
+ * smh_index_angular         rows x cols, host outputs, row-major, any may be NULL.  rows == cols: only col > row is walked and
+ *                           mirrored (the matrix equals its transpose bit for bit) and the diagonal is dot = norm2, cosine =
+ *                           angular = 1.0 (0.0 for an empty sketch).  From smh_angular_prune_min_pairs() pairs on, the block
+ *                           compare first computes count_common (for an index against itself through its cached dictionary,
+ *                           see smh_index_compare) and only the pairs that share a hash are walked.  Device memory, all
+ *                           from the block pool: 8 B per pair and requested output, plus 8 B per pair when pruning.
+ * smh_index_angular_query   one query against every node: dot / cosine / angular with n entries each, query_norm2 with n
+ *                           entries all holding the query's norm2 (any may be NULL).  A query whose state lives in HBM is
+ *                           read there, as gather reads it.
+ * smh_angular_similarity    one pair through the same kernel; any output may be NULL.
+ * smh_angular_block_dev     the CSR / device form, next to smh_compare_block_dev: hashes (u64) and abundances (u32) in device
+ *                           memory, offsets (n + 1 entries) on the host; outputs stay on the device (any may be NULL;
+ *                           row_norm2_dev / col_norm2_dev receive n_rows / n_cols entries).  count_common_dev (nullable):
+ *                           a row-major u64 matrix, a pair whose entry is 0 is not walked and gets the zero outputs.
+ *                           symmetric: rows and columns are the same sketches, handled as rows == cols above.
+ * smh_angular_last_stats    of the last angular call: pairs whose column was streamed against the row, and pairs that got
+ *                           the zero outputs without a walk (pruned, or one side empty).  The diagonal and the mirrored
+ *                           half of a symmetric block are in neither.
+ * smh_angular_set_prune_min_pairs  process-wide; 0 restores the default, UINT64_MAX never prunes, 1 always does.  The result
+ *                           never depends on it. */
+bool smh_index_has_abundances(const SmhIndex *index);
+int smh_index_norms2(SmhIndex *index, uint64_t *out);
+int smh_index_angular(SmhIndex *rows, SmhIndex *cols, uint64_t *dot, double *cosine, double *angular);
+int smh_index_angular_query(SmhIndex *index, const KmerMinHash *query, uint64_t *dot, uint64_t *query_norm2, double *cosine,
+                            double *angular);
+int smh_angular_similarity(const KmerMinHash *a, const KmerMinHash *b, double *angular, double *cosine, uint64_t *dot,
+                           uint64_t *norm2_a, uint64_t *norm2_b);
+int smh_angular_block_dev(const uint64_t *row_hashes_dev, const uint32_t *row_abunds_dev, const uint64_t *row_offsets,
+                          uint32_t n_rows, const uint64_t *col_hashes_dev, const uint32_t *col_abunds_dev,
+                          const uint64_t *col_offsets, uint32_t n_cols, const uint64_t *count_common_dev, bool symmetric,
+                          uint64_t *dot_dev, uint64_t *row_norm2_dev, uint64_t *col_norm2_dev, double *cosine_dev,
+                          double *angular_dev, void *stream);
+void smh_angular_last_stats(uint64_t *pairs_walked, uint64_t *pairs_skipped);
+uint64_t smh_angular_prune_min_pairs(void);
+void smh_angular_set_prune_min_pairs(uint64_t pairs);
+
 /* deterministic synthetic DNA of SURVEY.md 8d written to device memory (benchmark input) */
 int smh_synth_dna_dev(void *out_dev, uint64_t start, uint64_t len, uint64_t seed, uint64_t n_every,
                       void *stream);
@@ -382,7 +446,7 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * "compare_pair", "compare_fill", "compare_comp", "compare_tiled" (the plain and the pipelined tiled kernels of one call together),
  * "sbt_bins", "sbt_nodes", "sbt_leaves", "sbt_build", "parse_scan" (tile summaries and their scan), "parse_compact",
  * "gather_hits" (the membership pass), "gather_invert" (degree scan + inverted lists), "gather_rounds" (one entry per batch
- * of smh_gather_rounds_per_sync() rounds). */
+ * of smh_gather_rounds_per_sync() rounds), "angular_block" (the angular similarity's block kernel). */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -146,6 +146,16 @@ _SIGS = {
     "smh_index_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SmhGatherRow), C.c_uint32, C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint32)]),
     "smh_gather_rounds_per_sync": (C.c_uint32, []),
+    "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
+    "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
+    "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),
+    "smh_index_angular_query": (C.c_int, [C.c_void_p, C.c_void_p, u64p, u64p, f64p, f64p]),
+    "smh_angular_similarity": (C.c_int, [C.c_void_p, C.c_void_p, f64p, f64p, u64p, u64p, u64p]),
+    "smh_angular_block_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_void_p, C.c_void_p, u64p, C.c_uint32,
+                                        C.c_void_p, C.c_bool, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "smh_angular_last_stats": (None, [u64p, u64p]),
+    "smh_angular_prune_min_pairs": (C.c_uint64, []),
+    "smh_angular_set_prune_min_pairs": (None, [C.c_uint64]),
     "smh_release_workspace": (C.c_int, []),
     "smh_pool_set_limit": (None, [C.c_uint64]),
     "smh_pool_bytes": (C.c_uint64, []),

@@ -784,6 +784,16 @@ struct SmhIndex {
   // of the index with itself and kept: later ones skip the pre-pass (the nodes of an index never change)
   smh::CollectionDict* dict = nullptr;
   uint32_t dict_split = 0;      // the frequent-hash setting the dictionary was built under
+  // angular similarity.  has_abunds: EVERY node tracks abundances and every abundance vector matches its
+  // hashes; h_abunds then holds them narrowed to u32 (a copy, like the hashes) until the first angular call uploads them
+  // and computes the norms -- an index nobody asks pays no HBM.  bad_node: the lowest node whose norm2 does not fit 64 bits.
+  bool has_abunds = false;
+  std::vector<uint32_t> h_abunds;
+  uint32_t wide_node = smh::kAngularNoError;   // the first node holding an abundance of 2^32 or more
+  bool angular_ready = false;
+  uint32_t bad_node = smh::kAngularNoError;
+  smh::DeviceBuffer abunds_dev, norm2_dev;
+  std::vector<uint64_t> h_norm2;
   SmhIndex() { std::lock_guard<std::mutex> g(registry_mu()); registry().insert(this); }
   ~SmhIndex() {
     { std::lock_guard<std::mutex> g(registry_mu()); registry().erase(this); }
@@ -817,6 +827,17 @@ SmhIndex* smh_index_new(KmerMinHash* const* nodes, uint32_t n_nodes) {
     hipStream_t s = dev.stream();
     smh::SketchSet set;
     smh::Engine::get().pack_sketches(v, idx->hashes, idx->offsets, &set, &idx->max_len, &idx->h_offsets, s);
+    // (pack_sketches has brought every node to the host)
+    idx->has_abunds = true;
+    for (uint32_t i = 0; i < n_nodes; i++) idx->has_abunds &= v[i]->has_abunds && v[i]->abunds.size() == v[i]->mins.size();
+    if (idx->has_abunds) {
+      idx->h_abunds.reserve(idx->h_offsets.back());
+      for (uint32_t i = 0; i < n_nodes; i++)
+        for (uint64_t a : v[i]->abunds) {
+          if (a >> 32) { idx->wide_node = std::min(idx->wide_node, i); a = 0xffffffffull; }
+          idx->h_abunds.push_back((uint32_t)a);
+        }
+    }
     idx->nums.ensure((size_t)n_nodes * 4 + 4);
     if (n_nodes) HIP_CHECK(hipMemcpyAsync(idx->nums.ptr, idx->h_nums.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -1016,6 +1037,363 @@ int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t*
     HIP_CHECK(hipStreamSynchronize(s));
   });
 }
+
+// ------------------------------------------------------------------ angular similarity on abundances
+
+}  // extern "C" (the helpers below hold templates)
+
+namespace {
+
+// a block of the device pool for the length of one call
+struct CallBlock {
+  void* ptr = nullptr;
+  size_t cap = 0;
+  bool synced = false;   // the stream was waited for: nothing can still be using the block
+  explicit CallBlock(size_t bytes) { ptr = smh::device_pool_alloc(bytes ? bytes : 1, &cap); }
+  CallBlock(const CallBlock&) = delete;
+  CallBlock& operator=(const CallBlock&) = delete;
+  ~CallBlock() { smh::device_pool_free(ptr, cap, !synced); }
+  template <class T> T* as() const { return reinterpret_cast<T*>(ptr); }
+};
+
+// From this many pairs on smh_index_angular first runs the block compare for count_common and walks only the pairs that
+// share a hash.  Chosen from tools/bench_angular.py's sweep ("The prune threshold").
+constexpr uint64_t kAngularPruneMinPairs = 4096;
+uint64_t g_angular_prune_min_pairs = kAngularPruneMinPairs;
+uint64_t g_angular_walked = 0, g_angular_skipped = 0;
+
+void angular_require_tracking(const smh::KmerMinHash* mh, const char* what) {
+  if (!mh->has_abunds) throw Error(smh::kMsg, std::string("angular: ") + what + " does not track abundances");
+}
+[[noreturn]] void angular_throw_norm(const std::string& who) {
+  throw Error(smh::kMsg, "angular: norm2 of " + who + " does not fit 64 bits (an abundance of 2^32 or more, or too many large ones)");
+}
+// what can be said about a sketch without the device: a host state whose abundance vector does not match its hashes
+void angular_check_host_state(const smh::KmerMinHash* mh, const char* what) {
+  if (!mh->dev && mh->pend_seq.empty() && mh->pend_words.empty() && mh->abunds.size() != mh->mins.size())
+    throw Error(smh::kMsg, std::string("angular: the abundance vector of ") + what + " does not match its hashes (quirks Q5/Q6)");
+}
+
+// One sketch in the form the kernels read: hashes and u32 abundances in device memory, offsets {0, n}, its norm2.  A state
+// that lives in HBM is read there (its abundances are narrowed by a kernel); a host state is uploaded.
+struct AngularOperand {
+  const uint64_t* hashes = nullptr;
+  const uint32_t* abunds = nullptr;
+  uint32_t n = 0;
+  std::unique_ptr<CallBlock> store, small;   // small: offsets (2 x u64), norm2 (u64), error word (u32)
+  std::vector<uint32_t> staged;
+  uint64_t off[2] = {0, 0};
+  uint64_t* offsets_dev() const { return small->as<uint64_t>(); }
+  uint64_t* norm2_dev() const { return small->as<uint64_t>() + 2; }
+  uint32_t* err_dev() const { return reinterpret_cast<uint32_t*>(small->as<uint64_t>() + 3); }
+  void done() { if (store) store->synced = true; if (small) small->synced = true; }
+};
+
+// queues the operand's upload / narrowing and its norm; the caller synchronises and then reads h_norm2 / h_err
+void angular_prepare(AngularOperand& op, const smh::KmerMinHash* mh, const char* what, uint64_t* h_norm2, uint32_t* h_err, hipStream_t s) {
+  mh->flush_pending();
+  op.small = std::make_unique<CallBlock>(32);
+  HIP_CHECK(hipMemsetAsync(op.err_dev(), 0xff, 4, s));
+  uint64_t n = 0;
+  if (mh->dev) {
+    const smh::DeviceSketch& S = *mh->dev;
+    n = S.n;
+    if (n >= 0xffffffffull) smh::throw_internal("angular: a sketch of 2^32 - 1 or more hashes");
+    if (n && !S.has_counts && !S.has_runs) smh::throw_internal("angular: the sketch's device state carries no abundances");
+    op.store = std::make_unique<CallBlock>(n * 4);
+    op.hashes = S.uniq.as<uint64_t>();
+    op.abunds = op.store->as<uint32_t>();
+    smh::launch_angular_narrow(S.has_counts ? S.counts.as<uint64_t>() : nullptr, S.has_counts ? nullptr : S.starts.as<uint32_t>(),
+                               (uint32_t)S.total, (uint32_t)n, op.store->as<uint32_t>(), op.err_dev(), 0, s);
+  } else {
+    n = mh->mins.size();
+    if (mh->abunds.size() != n)
+      throw Error(smh::kMsg, std::string("angular: the abundance vector of ") + what + " does not match its hashes (quirks Q5/Q6)");
+    if (n >= 0xffffffffull) smh::throw_internal("angular: a sketch of 2^32 - 1 or more hashes");
+    op.staged.resize(n);
+    for (uint64_t i = 0; i < n; i++) {
+      if (mh->abunds[i] >> 32) angular_throw_norm(what);
+      op.staged[i] = (uint32_t)mh->abunds[i];
+    }
+    op.store = std::make_unique<CallBlock>(n * 12);
+    if (n) {
+      HIP_CHECK(hipMemcpyAsync(op.store->ptr, mh->mins.data(), n * 8, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(op.store->as<uint64_t>() + n, op.staged.data(), n * 4, hipMemcpyHostToDevice, s));
+    }
+    op.hashes = op.store->as<uint64_t>();
+    op.abunds = reinterpret_cast<const uint32_t*>(op.store->as<uint64_t>() + n);
+  }
+  op.n = (uint32_t)n;
+  op.off[1] = n;
+  HIP_CHECK(hipMemcpyAsync(op.offsets_dev(), op.off, 16, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemsetAsync(op.norm2_dev(), 0, 8, s));
+  smh::launch_angular_norms(op.abunds, op.offsets_dev(), 1, op.norm2_dev(), op.err_dev(), s);
+  HIP_CHECK(hipMemcpyAsync(h_norm2, op.norm2_dev(), 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(h_err, op.err_dev(), 4, hipMemcpyDeviceToHost, s));
+}
+
+smh::AngularSet angular_set(const AngularOperand& op) {
+  smh::AngularSet a;
+  a.hashes = op.hashes; a.abunds = op.abunds; a.offsets = op.offsets_dev(); a.norm2 = op.norm2_dev(); a.n = 1;
+  return a;
+}
+
+// the first angular call on an index: abundances to HBM, norms computed and read back
+void angular_ensure_index(SmhIndex* index, const char* what, hipStream_t s) {
+  if (!index->angular_ready) {
+    const uint32_t n = index->n;
+    index->abunds_dev.ensure(index->h_abunds.size() * 4 + 4);
+    index->norm2_dev.ensure((size_t)n * 8 + 8);
+    index->h_norm2.assign(n, 0);
+    uint32_t err = smh::kAngularNoError;
+    if (n) {
+      CallBlock e(4);
+      HIP_CHECK(hipMemsetAsync(e.ptr, 0xff, 4, s));
+      if (!index->h_abunds.empty())
+        HIP_CHECK(hipMemcpyAsync(index->abunds_dev.ptr, index->h_abunds.data(), index->h_abunds.size() * 4, hipMemcpyHostToDevice, s));
+      smh::launch_angular_norms(index->abunds_dev.as<uint32_t>(), index->offsets.as<uint64_t>(), n, index->norm2_dev.as<uint64_t>(),
+                                e.as<uint32_t>(), s);
+      HIP_CHECK(hipMemcpyAsync(index->h_norm2.data(), index->norm2_dev.ptr, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(&err, e.ptr, 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      e.synced = true;
+    }
+    index->bad_node = std::min(index->wide_node, err);
+    std::vector<uint32_t>().swap(index->h_abunds);   // they live in HBM now
+    index->angular_ready = true;
+  }
+  if (index->bad_node != smh::kAngularNoError) angular_throw_norm(std::string(what) + " " + std::to_string(index->bad_node));
+}
+
+void angular_require_index(const SmhIndex* index, const char* what) {
+  if (!index->has_abunds)
+    throw Error(smh::kMsg, std::string("angular: ") + what + " holds a node that does not track abundances, or whose abundance "
+                "vector does not match its hashes (quirks Q5/Q6)");
+}
+
+smh::AngularSet angular_set(const SmhIndex* index) {
+  smh::AngularSet a;
+  a.hashes = index->hashes.as<uint64_t>(); a.abunds = index->abunds_dev.as<uint32_t>(); a.offsets = index->offsets.as<uint64_t>();
+  a.norm2 = index->norm2_dev.as<uint64_t>(); a.n = index->n;
+  return a;
+}
+
+// count_common of rows x cols into d_cc (np entries): the route smh_index_compare takes, the cached dictionary included
+void angular_count_common(SmhIndex* rows, SmhIndex* cols, uint64_t* d_cc, smh::Device& dev, hipStream_t s) {
+  const size_t np = (size_t)rows->n * cols->n;
+  smh::SketchSet R, C;
+  R.hashes = rows->hashes.as<uint64_t>(); R.offsets = rows->offsets.as<uint64_t>(); R.n = rows->n;
+  C.hashes = cols->hashes.as<uint64_t>(); C.offsets = cols->offsets.as<uint64_t>(); C.n = cols->n;
+  R.h_offsets = rows->h_offsets.data(); C.h_offsets = cols->h_offsets.data();
+  smh::CompareOut o;
+  o.count_common = d_cc;
+  bool uniform = true;
+  for (uint32_t v : rows->h_nums) uniform &= v == rows->h_nums[0];
+  const smh::CompareTuning tune = smh::compare_get_tuning();
+  const bool block_route = tune.route == smh::kRouteAuto ? (np >= 4096 && rows->n >= 16) : (tune.route == smh::kRouteComponents || tune.route == smh::kRouteTiled);
+  if (rows == cols && block_route && rows->h_offsets.back() > 0) {
+    if (rows->dict && rows->dict_split != tune.split_frequent) { smh::collection_free(rows->dict); rows->dict = nullptr; }
+    if (!rows->dict) {
+      rows->dict = smh::collection_begin(R.hashes, R.offsets, rows->h_offsets.data(), rows->n, 1, 0, dev, s);
+      smh::collection_finish(rows->dict, nullptr, dev, s);
+      rows->dict_split = tune.split_frequent;
+    }
+    smh::collection_compare(rows->dict, 0, rows->n, 0, rows->n, uniform ? rows->h_nums[0] : 0,
+                            uniform ? nullptr : rows->nums.as<uint32_t>(), 1, o, dev, s);
+  } else {
+    smh::launch_compare_block(R, C, uniform ? rows->h_nums[0] : 0, uniform ? nullptr : rows->nums.as<uint32_t>(), o, dev, s,
+                              rows->max_len, cols->max_len, rows->h_offsets.back(), cols->h_offsets.back(), rows == cols);
+  }
+}
+
+// runs the block kernel into pool memory and brings the wanted outputs and the two counters back; the stream is idle after
+void angular_run_host(const smh::AngularSet& R, const smh::AngularSet& C, const uint64_t* prune_dev, bool symmetric, uint64_t* dot,
+                      double* cosine, double* angular, smh::Device& dev, hipStream_t s) {
+  const size_t np = (size_t)R.n * C.n;
+  CallBlock d_dot(dot ? np * 8 : 0), d_cos(cosine ? np * 8 : 0), d_ang(angular ? np * 8 : 0), d_cnt(16);
+  smh::AngularOut o;
+  o.dot = dot ? d_dot.as<uint64_t>() : nullptr; o.cosine = cosine ? d_cos.as<double>() : nullptr;
+  o.angular = angular ? d_ang.as<double>() : nullptr;
+  smh::launch_angular_block(R, C, prune_dev, symmetric, o, d_cnt.as<unsigned long long>(), dev, s);
+  uint64_t cnt[2] = {0, 0};
+  if (dot) HIP_CHECK(hipMemcpyAsync(dot, d_dot.ptr, np * 8, hipMemcpyDeviceToHost, s));
+  if (cosine) HIP_CHECK(hipMemcpyAsync(cosine, d_cos.ptr, np * 8, hipMemcpyDeviceToHost, s));
+  if (angular) HIP_CHECK(hipMemcpyAsync(angular, d_ang.ptr, np * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.ptr, 16, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  d_dot.synced = d_cos.synced = d_ang.synced = d_cnt.synced = true;
+  g_angular_walked = cnt[0]; g_angular_skipped = cnt[1];
+}
+
+}  // namespace
+
+extern "C" {
+
+bool smh_index_has_abundances(const SmhIndex* index) { return index && index->has_abunds; }
+
+int smh_index_norms2(SmhIndex* index, uint64_t* out) {
+  return pad_code([&] {
+    require(index, "index");
+    angular_require_index(index, "the index");
+    if (index->n == 0) return;
+    require(out, "out");
+    auto& dev = smh::Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    angular_ensure_index(index, "node", dev.stream());
+    std::copy(index->h_norm2.begin(), index->h_norm2.end(), out);
+  });
+}
+
+int smh_index_angular(SmhIndex* rows, SmhIndex* cols, uint64_t* dot, double* cosine, double* angular) {
+  return pad_code([&] {
+    require(rows, "rows"); require(cols, "cols");
+    angular_require_index(rows, "the row index");
+    angular_require_index(cols, "the column index");
+    if (rows->n && cols->n) {
+      if (rows->uniform && cols->uniform) rows->params[0].check_compatible(cols->params[0]);
+      else for (auto& r : rows->params) for (auto& c : cols->params) r.check_compatible(c);
+    }
+    const size_t np = (size_t)rows->n * cols->n;
+    auto& dev = smh::Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.stream();
+    g_angular_walked = g_angular_skipped = 0;
+    angular_ensure_index(rows, rows == cols ? "node" : "row node", s);
+    if (rows != cols) angular_ensure_index(cols, "column node", s);
+    if (np == 0) return;
+    std::unique_ptr<CallBlock> cc;
+    if (np >= g_angular_prune_min_pairs) {
+      cc = std::make_unique<CallBlock>(np * 8);
+      angular_count_common(rows, cols, cc->as<uint64_t>(), dev, s);
+    }
+    angular_run_host(angular_set(rows), angular_set(cols), cc ? cc->as<uint64_t>() : nullptr, rows == cols, dot, cosine, angular, dev, s);
+    if (cc) cc->synced = true;
+  });
+}
+
+int smh_index_angular_query(SmhIndex* index, const KmerMinHash* query, uint64_t* dot, uint64_t* query_norm2, double* cosine,
+                            double* angular) {
+  return pad_code([&] {
+    require(index, "index"); require(query, "query");
+    angular_require_index(index, "the index");
+    angular_require_tracking(query, "the query");
+    angular_check_host_state(query, "the query");
+    if (index->n) {
+      if (index->uniform) index->params[0].check_compatible(*query);
+      else for (auto& p : index->params) p.check_compatible(*query);
+    }
+    auto& dev = smh::Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.stream();
+    g_angular_walked = g_angular_skipped = 0;
+    angular_ensure_index(index, "node", s);
+    AngularOperand q;
+    uint64_t n2 = 0;
+    uint32_t err = smh::kAngularNoError;
+    angular_prepare(q, query, "the query", &n2, &err, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (err != smh::kAngularNoError) { q.done(); angular_throw_norm("the query"); }
+    if (query_norm2) std::fill(query_norm2, query_norm2 + index->n, n2);
+    if (index->n) angular_run_host(angular_set(q), angular_set(index), nullptr, false, dot, cosine, angular, dev, s);
+    q.done();
+  });
+}
+
+int smh_angular_similarity(const KmerMinHash* a, const KmerMinHash* b, double* angular, double* cosine, uint64_t* dot,
+                           uint64_t* norm2_a, uint64_t* norm2_b) {
+  return pad_code([&] {
+    require(a, "a"); require(b, "b");
+    angular_require_tracking(a, "the first sketch");
+    angular_require_tracking(b, "the second sketch");
+    a->check_compatible(*b);
+    angular_check_host_state(a, "the first sketch");
+    angular_check_host_state(b, "the second sketch");
+    auto& dev = smh::Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.stream();
+    g_angular_walked = g_angular_skipped = 0;
+    AngularOperand A, B;
+    uint64_t n2[2] = {0, 0};
+    uint32_t err[2] = {smh::kAngularNoError, smh::kAngularNoError};
+    angular_prepare(A, a, "the first sketch", &n2[0], &err[0], s);
+    angular_prepare(B, b, "the second sketch", &n2[1], &err[1], s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (err[0] != smh::kAngularNoError || err[1] != smh::kAngularNoError) {
+      A.done(); B.done();
+      angular_throw_norm(err[0] != smh::kAngularNoError ? "the first sketch" : "the second sketch");
+    }
+    uint64_t d = 0;
+    double c = 0.0, an = 0.0;
+    angular_run_host(angular_set(A), angular_set(B), nullptr, false, &d, &c, &an, dev, s);
+    A.done(); B.done();
+    if (angular) *angular = an;
+    if (cosine) *cosine = c;
+    if (dot) *dot = d;
+    if (norm2_a) *norm2_a = n2[0];
+    if (norm2_b) *norm2_b = n2[1];
+  });
+}
+
+int smh_angular_block_dev(const uint64_t* row_hashes_dev, const uint32_t* row_abunds_dev, const uint64_t* row_offsets, uint32_t n_rows,
+                          const uint64_t* col_hashes_dev, const uint32_t* col_abunds_dev, const uint64_t* col_offsets, uint32_t n_cols,
+                          const uint64_t* count_common_dev, bool symmetric, uint64_t* dot_dev, uint64_t* row_norm2_dev,
+                          uint64_t* col_norm2_dev, double* cosine_dev, double* angular_dev, void* stream) {
+  return pad_code([&] {
+    require(row_offsets, "row_offsets"); require(col_offsets, "col_offsets");
+    if (symmetric && (n_rows != n_cols || std::memcmp(row_offsets, col_offsets, ((size_t)n_rows + 1) * 8) != 0))
+      throw Error(smh::kMsg, "angular: a symmetric block needs the same sketches as rows and as columns");
+    for (uint32_t i = 0; i < n_rows; i++)
+      if (row_offsets[i + 1] < row_offsets[i] || row_offsets[i + 1] - row_offsets[i] >= 0xffffffffull)
+        throw Error(smh::kMsg, "angular: row_offsets must ascend, with sketches shorter than 2^32 - 1");
+    for (uint32_t j = 0; j < n_cols; j++)
+      if (col_offsets[j + 1] < col_offsets[j] || col_offsets[j + 1] - col_offsets[j] >= 0xffffffffull)
+        throw Error(smh::kMsg, "angular: col_offsets must ascend, with sketches shorter than 2^32 - 1");
+    if (row_offsets[n_rows] > row_offsets[0]) { require(row_hashes_dev, "row_hashes_dev"); require(row_abunds_dev, "row_abunds_dev"); }
+    if (col_offsets[n_cols] > col_offsets[0]) { require(col_hashes_dev, "col_hashes_dev"); require(col_abunds_dev, "col_abunds_dev"); }
+    auto& dev = smh::Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.user_stream(stream);
+    g_angular_walked = g_angular_skipped = 0;
+    CallBlock offs(((size_t)n_rows + n_cols + 2) * 8), norms(((size_t)n_rows + n_cols) * 8), small(32);
+    uint64_t* d_ro = offs.as<uint64_t>();
+    uint64_t* d_co = d_ro + n_rows + 1;
+    uint64_t* d_rn = row_norm2_dev ? row_norm2_dev : norms.as<uint64_t>();
+    uint64_t* d_cn = col_norm2_dev ? col_norm2_dev : norms.as<uint64_t>() + n_rows;
+    unsigned long long* d_cnt = small.as<unsigned long long>();
+    uint32_t* d_err = reinterpret_cast<uint32_t*>(d_cnt + 2);
+    HIP_CHECK(hipMemcpyAsync(d_ro, row_offsets, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_co, col_offsets, ((size_t)n_cols + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(d_err, 0xff, 8, s));
+    smh::launch_angular_norms(row_abunds_dev, d_ro, n_rows, d_rn, d_err, s);
+    smh::launch_angular_norms(col_abunds_dev, d_co, n_cols, d_cn, d_err + 1, s);
+    uint32_t err[2] = {smh::kAngularNoError, smh::kAngularNoError};
+    HIP_CHECK(hipMemcpyAsync(err, d_err, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (err[0] != smh::kAngularNoError || err[1] != smh::kAngularNoError) {
+      offs.synced = norms.synced = small.synced = true;
+      if (err[0] != smh::kAngularNoError) angular_throw_norm("row sketch " + std::to_string(err[0]));
+      angular_throw_norm("column sketch " + std::to_string(err[1]));
+    }
+    smh::AngularSet R, C;
+    R.hashes = row_hashes_dev; R.abunds = row_abunds_dev; R.offsets = d_ro; R.norm2 = d_rn; R.n = n_rows;
+    C.hashes = col_hashes_dev; C.abunds = col_abunds_dev; C.offsets = d_co; C.norm2 = d_cn; C.n = n_cols;
+    smh::AngularOut o;
+    o.dot = dot_dev; o.cosine = cosine_dev; o.angular = angular_dev;
+    smh::launch_angular_block(R, C, count_common_dev, symmetric, o, d_cnt, dev, s);
+    uint64_t cnt[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(cnt, d_cnt, 16, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));   // the offsets and the counters live in blocks that go back to the pool now
+    offs.synced = norms.synced = small.synced = true;
+    g_angular_walked = cnt[0]; g_angular_skipped = cnt[1];
+  });
+}
+
+void smh_angular_last_stats(uint64_t* pairs_walked, uint64_t* pairs_skipped) {
+  if (pairs_walked) *pairs_walked = g_angular_walked;
+  if (pairs_skipped) *pairs_skipped = g_angular_skipped;
+}
+uint64_t smh_angular_prune_min_pairs(void) { return g_angular_prune_min_pairs; }
+void smh_angular_set_prune_min_pairs(uint64_t pairs) { g_angular_prune_min_pairs = pairs ? pairs : kAngularPruneMinPairs; }
 
 // ---- a scaled sketch's state as device arrays: the cross-rank union of partial sketches ----
 int smh_sketch_export_dev(KmerMinHash* ptr, uint64_t* mins_dev, uint64_t* abunds_dev, uint64_t capacity, uint64_t* n_out, void* stream) {

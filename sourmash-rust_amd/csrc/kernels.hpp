@@ -1,5 +1,5 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
-// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip).  Plain structs and pointers; no torch types anywhere.
+// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip).  Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -291,5 +291,35 @@ constexpr uint32_t kGatherRoundsPerSync = 32;   // rounds queued between two 8-b
 // block it took from the device pool is back there.
 uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q, uint32_t threshold, GatherRow* rows_host,
                     uint32_t capacity, uint32_t* assigned_host, Device& dev, hipStream_t s);
+
+// --- angular_kernels.hip ---------------------------------------------------------------
+// Angular similarity on abundances (the rules are in include/sourmash_amd.h).  Sketches as CSR with one
+// u32 abundance per hash; norm2[i] = sum of the squares of sketch i's abundances.
+struct AngularSet {
+  const uint64_t* hashes = nullptr;
+  const uint32_t* abunds = nullptr;
+  const uint64_t* offsets = nullptr;   // n+1 entries (device)
+  const uint64_t* norm2 = nullptr;     // n entries (device), from launch_angular_norms
+  uint32_t n = 0;
+};
+struct AngularOut {                    // row-major rows x cols, device memory, any may be null
+  uint64_t* dot = nullptr;
+  double* cosine = nullptr;
+  double* angular = nullptr;
+};
+constexpr uint32_t kAngularNoError = 0xffffffffu;   // what an error word holds before the launches that may lower it
+// abundances of a device-resident sketch -> u32: u64 counts, or differences of run starts (the two forms of DeviceSketch and
+// GatherQuery); a value of 2^32 or more lowers *err_dev to err_value
+void launch_angular_narrow(const uint64_t* counts, const uint32_t* starts, uint32_t total, uint32_t n, uint32_t* out,
+                           uint32_t* err_dev, uint32_t err_value, hipStream_t s);
+// norm2_dev[i] for every sketch; one that does not fit 64 bits lowers *err_dev to its index (the lowest one wins)
+void launch_angular_norms(const uint32_t* abunds, const uint64_t* offsets_dev, uint32_t n, uint64_t* norm2_dev, uint32_t* err_dev,
+                          hipStream_t s);
+// prune_dev (nullable): row-major u64 matrix, a pair whose entry is 0 is not walked and gets the zero outputs.  symmetric:
+// rows and cols are one set -- only col > row is walked and mirrored, the diagonal is dot = norm2, cosine = angular = 1
+// (0 for an empty sketch).  counters_dev: two u64 zeroed here, [0] pairs walked, [1] pairs given zeros without a walk.
+void launch_angular_block(const AngularSet& rows, const AngularSet& cols, const uint64_t* prune_dev, bool symmetric,
+                          const AngularOut& out, unsigned long long* counters_dev, Device& dev, hipStream_t s);
+uint32_t angular_chunk(uint32_t n_rows, uint32_t n_cols);   // columns per workgroup that launch_angular_block gives a block
 
 }  // namespace smh

@@ -28,6 +28,7 @@ GatherRecord = collections.namedtuple("GatherRecord", [
     "median_abund", "std_abund",   # numpy median / std over the abundances of the positions this row consumed
     "remaining_bp"])       # scaled * (query positions nobody has consumed after this row)
 GatherResult = collections.namedtuple("GatherResult", ["rows", "assigned"])
+AngularResult = collections.namedtuple("AngularResult", ["dot", "cosine", "angular"])
 
 
 def scaled_of_max_hash(max_hash):
@@ -128,6 +129,42 @@ class ResidentIndex:
                 0.0 if flat else float(np.std(mine)) if ab is not None else None,
                 scaled * left))
         return GatherResult(out, assigned)
+
+    @property
+    def has_abundances(self):
+        """every node tracked abundances when the index was built: the angular calls below can be served"""
+        return bool(self._L.smh_index_has_abundances(self._h))
+
+    def norms2(self):
+        """norm2 of every node (the sum of its squared abundances), uint64"""
+        out = np.zeros(len(self), dtype=np.uint64)
+        call(self._L.smh_index_norms2, self._h, out.ctypes.data_as(u64p))
+        return out
+
+    def angular(self, query):
+        """`query` against every node (smh_index_angular_query): AngularResult(dot, cosine, angular), numpy arrays of
+        len(self) entries.  A query that lives in HBM stays there."""
+        n = len(self)
+        dot, cos, ang = np.zeros(n, np.uint64), np.zeros(n, np.float64), np.zeros(n, np.float64)
+        f64p = C.POINTER(C.c_double)
+        call(self._L.smh_index_angular_query, self._h, query._p, dot.ctypes.data_as(u64p), None, cos.ctypes.data_as(f64p),
+             ang.ctypes.data_as(f64p))
+        return AngularResult(dot, cos, ang)
+
+    def angular_matrix(self, other=None, want=("angular",)):
+        """len(self) x len(other) matrix (other=None: the index against itself, symmetric) -> dict name -> array;
+        names: dot, cosine, angular (smh_index_angular)."""
+        other = self if other is None else other
+        kinds = {"dot": np.uint64, "cosine": np.float64, "angular": np.float64}
+        out = {k: np.zeros((len(self), len(other)), dtype=kinds[k]) for k in want}
+
+        def p(name):
+            if name not in out:
+                return None
+            return out[name].ctypes.data_as(C.POINTER(C.c_double) if out[name].dtype == np.float64 else u64p)
+
+        call(self._L.smh_index_angular, self._h, other._h, p("dot"), p("cosine"), p("angular"))
+        return out
 
     def compare(self, other, want=("jaccard",)):
         n, m = len(self), len(other)

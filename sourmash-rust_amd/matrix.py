@@ -94,6 +94,41 @@ def compare_block_dev(row_hashes, row_offsets, col_hashes, col_offsets, num, wan
     return outs
 
 
+def angular_block_dev(row_hashes, row_abunds, row_offsets, col_hashes, col_abunds, col_offsets, count_common=None, symmetric=False,
+                      want=("angular",), stream=None):
+    """Angular similarity of device-resident CSR sketches (smh_angular_block_dev): hashes are uint64/int64 CUDA tensors,
+    abundances uint32/int32 CUDA tensors, offsets host arrays.  count_common (optional CUDA int64/uint64 matrix) prunes the
+    pairs whose entry is 0.  Returns a dict of CUDA tensors; names: dot, cosine, angular, row_norm2, col_norm2."""
+    import torch
+    n, m = len(row_offsets) - 1, len(col_offsets) - 1
+    dev = row_hashes.device
+    kinds = {"dot": (torch.int64, (n, m)), "cosine": (torch.float64, (n, m)), "angular": (torch.float64, (n, m)),
+             "row_norm2": (torch.int64, (n,)), "col_norm2": (torch.int64, (m,))}
+    outs = {k: torch.empty(kinds[k][1], dtype=kinds[k][0], device=dev) for k in want}
+
+    def p(name):
+        return C.c_void_p(outs[name].data_ptr()) if name in outs else C.c_void_p(0)
+
+    ro = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+    co = np.ascontiguousarray(col_offsets, dtype=np.uint64)
+    if count_common is not None:
+        assert count_common.is_contiguous() and tuple(count_common.shape) == (n, m) and count_common.element_size() == 8
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    call(lib().smh_angular_block_dev, C.c_void_p(row_hashes.data_ptr()), C.c_void_p(row_abunds.data_ptr()), ro.ctypes.data_as(u64p), n,
+         C.c_void_p(col_hashes.data_ptr()), C.c_void_p(col_abunds.data_ptr()), co.ctypes.data_as(u64p), m,
+         C.c_void_p(count_common.data_ptr() if count_common is not None else 0), bool(symmetric),
+         p("dot"), p("row_norm2"), p("col_norm2"), p("cosine"), p("angular"), C.c_void_p(stream))
+    return outs
+
+
+def angular_last_stats():
+    """(pairs walked, pairs given zeros without a walk) of the last angular call"""
+    a, b = C.c_uint64(), C.c_uint64()
+    lib().smh_angular_last_stats(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
 OWN_ALL, OWN_TRIANGLE, OWN_CIRCULAR = 0, 1, 2
 
 

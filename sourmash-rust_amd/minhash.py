@@ -182,7 +182,24 @@ class KmerMinHash:
     def count_common(self, other): return call(self._L.kmerminhash_count_common, self._p, other._p)
     def compare(self, other): return call(self._L.kmerminhash_compare, self._p, other._p)
     def intersection(self, other): return call(self._L.kmerminhash_intersection, self._p, other._p)
-    similarity = compare
+
+    def angular_similarity(self, other):
+        """Angular similarity of the two abundance vectors (additive ABI smh_angular_similarity; the rules are in
+        include/sourmash_amd.h): both sketches must track abundances."""
+        return self.angular_parts(other)[0]
+
+    def angular_parts(self, other):
+        """(angular, cosine, dot, norm2 of self, norm2 of other) of one pair"""
+        ang, cos = C.c_double(), C.c_double()
+        dot, na, nb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        call(self._L.smh_angular_similarity, self._p, other._p, C.byref(ang), C.byref(cos), C.byref(dot), C.byref(na), C.byref(nb))
+        return ang.value, cos.value, dot.value, na.value, nb.value
+
+    def similarity(self, other, ignore_abundance=False):
+        """angular similarity when both sketches track abundances and ignore_abundance is false, else compare()"""
+        if not ignore_abundance and self.track_abundance and other.track_abundance:
+            return self.angular_similarity(other)
+        return self.compare(other)
 
     def check_compatible(self, other):
         """reference src/lib.rs:176-190: True, or SourmashError(101..104)."""
