@@ -368,12 +368,14 @@ uint64_t estimate_capacity(uint64_t span, uint64_t thr) {
 }  // namespace
 
 uint64_t Engine::run_chunk(HashSourceRef src_, uint64_t lo, uint64_t hi, uint64_t thr, bool want_pos,
-                           hipStream_t s) {
+                           hipStream_t s, uint64_t known) {
   HashSource& src = *static_cast<HashSource*>(src_);
   uint64_t cap = estimate_capacity(hi - lo, thr);
+  if (known > cap) cap = known;   // an earlier launch over the same range overflowed the estimate and counted on: exact size at once
   for (int attempt = 0; attempt < 2; attempt++) {
     if (cap >= (1ull << 31)) throw_internal("candidate set of one chunk exceeds 2^31 entries");
     if (cap == 0) cap = 1;
+    if (attempt) Device::get().count("chunk_rerun");   // (evidence for the tests, like the three small_fold* events of ingest)
     cand_hash[0].ensure(cap * 8);
     cand_hash[1].ensure(cap * 8);
     if (want_pos) { cand_pos[0].ensure(cap * 8); cand_pos[1].ensure(cap * 8); }
@@ -619,12 +621,14 @@ void ingest(KmerMinHash& mh, HashSource& src, hipStream_t s) {
         auto ds = std::make_shared<DeviceSketch>();
         uint64_t cap = 0;
         if (E.run_chunk_small(&src, lo, hi, mh.max_hash, (uint32_t)((long double)P * frac), s, ds.get(), &n, &cap)) {
+          dev.count("small_fold");
           if (n > 0) mh.dev = ds;
           return;
         }
         hashed = n <= cap;   // more than the small fold takes (repeats): the candidates are there for the general path
+        dev.count(hashed ? "small_fold_passed_on" : "small_fold_overflow");
       }
-      if (!hashed) n = E.run_chunk(&src, lo, hi, mh.max_hash, false, s);
+      if (!hashed) n = E.run_chunk(&src, lo, hi, mh.max_hash, false, s, n);
       Delta d;
       if (in_hbm) {
         if (n == 0) continue;
@@ -667,6 +671,7 @@ void ingest(KmerMinHash& mh, HashSource& src, hipStream_t s) {
           auto ds = std::make_shared<DeviceSketch>();
           uint64_t cap = 0;
           if (E.run_chunk_small(&src, 0, P, thr, (uint32_t)want, s, ds.get(), &n, &cap)) {
+            dev.count("small_fold");
             if (thr == natural || ds->n >= (uint64_t)mh.num) {
               if (ds->n > (uint64_t)mh.num) ds->n = mh.num;
               if (ds->n > 0) mh.dev = ds;
@@ -675,10 +680,11 @@ void ingest(KmerMinHash& mh, HashSource& src, hipStream_t s) {
             n = ~0ull;          // fewer than num distinct hashes: nothing applied, the growing-chunk loop takes over
           } else {
             hashed = n <= cap;  // too many candidates for the small fold (repeats): they wait in cand_hash[0]
+            dev.count(hashed ? "small_fold_passed_on" : "small_fold_overflow");
           }
         }
         if (n != ~0ull) {
-        if (!hashed) n = E.run_chunk(&src, 0, P, thr, track, s);
+        if (!hashed) n = E.run_chunk(&src, 0, P, thr, track, s, n);
         Delta d;
         E.reduce_chunk(n, mh.num, track, track, s, &d, nullptr, thr == UINT64_MAX ? 0 : thr);
         if (thr == natural || d.uniq.size() >= (size_t)mh.num) {
@@ -780,6 +786,7 @@ bool KmerMinHash::merge_on_device(const KmerMinHash& other) {
   mins.w().swap(nm);
   abunds.swap(na_sum);   // untracked inputs: Some(vec![]) like the reference
   has_abunds = true;
+  dev.count("merge_on_device");
   return true;
 }
 

@@ -329,7 +329,7 @@ __global__ __launch_bounds__(kBsThreads) void k_block_sort(const uint64_t* __res
 }
 
 // The whole fold of a small batch in one launch, without waiting for the candidate count: *count candidates (device) ->
-// distinct keys ascending + run starts + {candidates, runs} in result[0..1].  More than kBlockSortMax candidates (or more
+// distinct keys ascending + run starts + {candidates, runs} in result[0..1].  More than CAP candidates (or more
 // than the buffer holds): result[1] = ~0, nothing else touched -- the caller takes the general path.  This is the call
 // shape of one genome per sketch: 5 Mbp leave 5 000 candidates at scaled=1000 (10 000 through the protein arm).
 template <int CAP>

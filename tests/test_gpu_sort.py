@@ -1,7 +1,10 @@
 """The fold's sort on its own (smh_sort_u64) against numpy's stable sort: uniform hashes, scaled hashes, repeated keys
 (a k-mer a million times, every key thirty times, the pool of one family), keys that share their high bits, constant
-high bytes, short keys (passes skipped), the sizes around the one-workgroup sort."""
+high bytes, short keys (passes skipped), the sizes around the one-workgroup sort, and permutations large enough for the
+two forms of the generic scan over the per-tile digit counts."""
 import ctypes as C
+import math
+import time
 
 import numpy as np
 import pytest
@@ -102,3 +105,73 @@ def test_small_arrays_with_repeats(pkg):
         _check(pkg, np.full(n, 7, dtype=np.uint64))
         _check(pkg, np.full(n, 2**64 - 1, dtype=np.uint64))
         _check(pkg, rng.integers(2**63, 2**64, size=n, dtype=np.uint64))
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 2049, 16383, 16384, 16385])
+def test_sizes_around_one_tile_and_eight(pkg, n):
+    """2 048 keys are one tile of the radix passes, 16 384 are eight: uniform keys, and 300 values with long runs of ties"""
+    rng = np.random.default_rng(n)
+    _check(pkg, rng.integers(0, 2**64, size=n, dtype=np.uint64))
+    _check(pkg, rng.integers(0, 300, size=n, dtype=np.uint64))
+
+
+def _sort_in_place(pkg, keys, payload):
+    """smh_sort_u64 on the caller's arrays (no copies: the arrays of the large cases are hundreds of megabytes)"""
+    rc = pkg.lib().smh_sort_u64(keys.ctypes.data_as(C.c_void_p), None if payload is None else payload.ctypes.data_as(C.c_void_p), keys.size)
+    assert rc == 0
+
+
+def _coprime(n, start=1_000_003):
+    a = start
+    while math.gcd(a, n) != 1:
+        a += 2
+    return a
+
+
+# Above 16 384 tiles of 2 048 keys (n > 33 554 432) the offsets of a pass come from the generic scan of all 256 * tiles
+# counters instead of one row scan per digit, and above 32 768 tiles (n > 67 108 864) that scan has more than 1 024 chunks
+# and takes its three-launch form.  A scaled=100 sketch of 10 GB of sequence sorts 100 M candidates.
+@pytest.mark.parametrize("n", [33_554_432, 33_554_433, 67_108_865])
+def test_large_permutation(pkg, n):
+    """a permutation that needs no host sort to build or to verify: key_i = j * (2^64 // n) with j = i * A mod n and
+    gcd(A, n) = 1, so the sorted keys are arange(n) * (2^64 // n) and the key at sorted place j came from i = j * A^-1 mod n.
+    Keys only, then with the 32-bit payload."""
+    A = _coprime(n)
+    stride = np.uint64(2**64 // n)
+    t0 = time.perf_counter()
+    j = (np.arange(n, dtype=np.uint64) * np.uint64(A)) % np.uint64(n)        # i * A < 2^47: no wrap
+    keys = j * stride
+    del j
+    want = np.arange(n, dtype=np.uint64) * stride
+    t1 = time.perf_counter()
+    k = keys.copy()
+    _sort_in_place(pkg, k, None)
+    t2 = time.perf_counter()
+    assert np.array_equal(k, want), "keys only"
+    p = np.arange(n, dtype=np.uint32)
+    t3 = time.perf_counter()
+    _sort_in_place(pkg, keys, p)
+    t4 = time.perf_counter()
+    assert np.array_equal(keys, want), "keys with payload"
+    del keys, k
+    want //= stride                                                          # arange(n) again, in place
+    want *= np.uint64(pow(A, -1, n))                                         # j * A^-1 < 2^54
+    want %= np.uint64(n)
+    assert np.array_equal(p, want.astype(np.uint32)), "payload = where every key came from"
+    t5 = time.perf_counter()
+    print("n=%d: build %.2f s, sort keys %.2f s, sort keys+payload %.2f s, verify %.2f s"
+          % (n, t1 - t0, t2 - t1, t4 - t3, (t3 - t2) + (t5 - t4)))
+
+
+def test_large_sort_with_every_key_eight_times(pkg):
+    """33 554 433 keys, every value eight times and scattered over the whole array: stability across the tiles of the
+    generic-scan path, judged in O(n) by the checker of fold_restatement.py"""
+    import fold_restatement as FR
+    n = 33_554_433
+    A = _coprime(n)
+    stride = np.uint64(2**64 // n)
+    keys = (((np.arange(n, dtype=np.uint64) * np.uint64(A)) % np.uint64(n)) >> np.uint64(3)) * stride
+    k, p = keys.copy(), np.arange(n, dtype=np.uint32)
+    _sort_in_place(pkg, k, p)
+    assert FR.check_sorted_with_payload(keys, k, p) is None
+    assert k[0] == 0 and k[7] == 0 and k[8] == stride and int(k[-1]) == ((n - 1) >> 3) * int(stride)
