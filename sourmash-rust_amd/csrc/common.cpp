@@ -23,4 +23,6 @@ void throw_panic(const std::string& what) { throw Error(kPanic, "sourmash panick
 // reference src/errors.rs:6-7 ("internal error: {}")
 void throw_internal(const std::string& what) { throw Error(kInternal, "internal error: " + what); }
 
+void require(const void* p, const char* what) { if (!p) throw_panic(std::string("assertion failed: !") + what + ".is_null()"); }
+
 }  // namespace smh

@@ -40,6 +40,7 @@ struct Error : std::exception {
 [[noreturn]] void throw_mismatch(uint32_t code);          // 101..104 with the reference's text
 [[noreturn]] void throw_panic(const std::string& what);    // "sourmash panicked: ..."
 [[noreturn]] void throw_internal(const std::string& what); // "internal error: ..."
+void require(const void* p, const char* what);             // a null pointer argument panics: "assertion failed: !what.is_null()"
 
 struct LastError {
   bool set = false;

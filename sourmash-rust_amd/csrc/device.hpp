@@ -32,6 +32,17 @@ void device_pool_trim();   // hipFree everything the pool holds
 void device_pool_set_limit(size_t bytes);   // cap on the bytes parked in the pool (default 1 GiB, SOURMASH_AMD_POOL_MB)
 size_t device_pool_bytes();
 
+// a block of the device pool for the length of one call
+struct PoolBlock {
+  void* ptr = nullptr;
+  size_t cap = 0;
+  bool synced = false;   // the stream was waited for: nothing can still be using the block (else the free waits for the device)
+  explicit PoolBlock(size_t bytes) { ptr = device_pool_alloc(bytes ? bytes : 1, &cap); }
+  PoolBlock(const PoolBlock&) = delete; PoolBlock& operator=(const PoolBlock&) = delete;
+  ~PoolBlock() { device_pool_free(ptr, cap, !synced); }
+  template <class T> T* as() const { return reinterpret_cast<T*>(ptr); }
+};
+
 // grow-only device allocation (never shrinks; released with the context or explicitly)
 struct DeviceBuffer {
   void* ptr = nullptr;

@@ -6,15 +6,15 @@
 #include <cstring>
 #include <memory>
 #include <string>
-#include <set>
 #include <vector>
 
 #include "../../include/sourmash_amd.h"
-#include "minhash.hpp"
+#include "index.hpp"
 #include "sbt.hpp"
 #include "signature.hpp"
 
 using smh::Error;
+using smh::require;
 
 struct KmerMinHash : smh::KmerMinHash {
   using smh::KmerMinHash::KmerMinHash;
@@ -74,10 +74,6 @@ int pad_code(F&& f) {
     slot.set = true; slot.code = smh::kPanic; slot.message = std::string("sourmash panicked: ") + e.what();
     return (int)smh::kPanic;
   }
-}
-
-void require(const void* p, const char* what) {
-  if (!p) smh::throw_panic(std::string("assertion failed: !") + what + ".is_null()");
 }
 
 SourmashStr str_from_string(const std::string& s) {  // utils.rs:201-210 from_string: owned copy
@@ -464,127 +460,28 @@ int smh_add_sequences_grouped_dev(KmerMinHash* const* sketches, uint32_t n_sketc
   });
 }
 
-// ------------------------------------------------------------------ records parsed on the device
+// ------------------------------------------------------------------ records parsed on the device (records.cpp)
 
-}  // extern "C"
+struct SmhRecords : smh::Records {};
 
-// The records of one FASTA / FASTQ text: the compacted sequence bytes and the name spans in HBM, the offsets on the host
-// (page-locked: the sketching paths walk them and upload them again).  Holds no reference to the text.
-struct SmhRecords {
-  void* seq = nullptr; size_t seq_cap = 0;          // total + 64 bytes, from the block pool
-  void* names = nullptr; size_t names_cap = 0;      // name_start[n], name_end[n]
-  uint64_t* offsets = nullptr;                      // n + 1, hipHostMalloc
-  uint32_t n = 0;
-  uint64_t total = 0;
-  int format = 0;
-  ~SmhRecords() {
-    if (seq) smh::device_pool_free(seq, seq_cap, true);
-    if (names) smh::device_pool_free(names, names_cap, true);
-    if (offsets) (void)hipHostFree(offsets);
-  }
-};
-
-namespace {
-
-struct PoolBlock {      // a transient device block
-  void* ptr = nullptr; size_t cap = 0;
-  explicit PoolBlock(size_t need) { ptr = smh::device_pool_alloc(need, &cap); }
-  ~PoolBlock() { if (ptr) smh::device_pool_free(ptr, cap, true); }
-  PoolBlock(const PoolBlock&) = delete;
-  PoolBlock& operator=(const PoolBlock&) = delete;
-};
-
-SmhRecords* parse_records(const uint8_t* text, uint64_t len, int format, hipStream_t s) {
-  if (format != smh::kFormatAuto && format != smh::kFormatFasta && format != smh::kFormatFastq)
-    throw Error(smh::kMsg, "unknown sequence file format " + std::to_string(format));
-  auto rec = std::make_unique<SmhRecords>();
-  PoolBlock small(256);
-  auto* totals_dev = static_cast<smh::ParseTotals*>(small.ptr);
-  if (format == smh::kFormatAuto) {
-    uint64_t first = ~0ull;
-    if (len) {
-      auto* first_dev = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(small.ptr) + 128);
-      smh::launch_first_content(text, len, first_dev, s);
-      HIP_CHECK(hipMemcpyAsync(&first, first_dev, 8, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-    }
-    if (first == ~0ull || first == '>') format = smh::kFormatFasta;      // a text without content holds no records
-    else if (first == '@') format = smh::kFormatFastq;
-    else throw Error(smh::kMsg, "neither FASTA nor FASTQ: the first non-empty line starts with byte " + std::to_string(first));
-  }
-  rec->format = format;
-  smh::ParseTotals tot{0, 0, 0, 0, ~0ull};
-  if (len) {
-    PoolBlock ws(smh::parse_workspace_bytes(text, len));
-    const smh::ParseTileIn first{0, 0, 0, 0, 0};
+static SmhRecords* records_parse(const void* text, const char* what, bool on_host, uint64_t len, int format, void* stream) {
+  return pad<SmhRecords*>([&] {
     auto& dev = smh::Device::get();
-    dev.prof_begin(s);
-    smh::launch_parse_scan(format, text, len, first, ws.ptr, totals_dev, s);
-    dev.prof_end("parse_scan", s);
-    HIP_CHECK(hipMemcpyAsync(&tot, totals_dev, sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (tot.n_records > 0xffffffffull) throw Error(smh::kMsg, "more than 2^32 - 1 records in one text");
-    if (tot.total > len) smh::throw_internal("parse: more sequence bytes than text");
-    const uint64_t n = tot.n_records;
-    rec->seq = smh::device_pool_alloc(tot.total + 64, &rec->seq_cap);
-    rec->names = smh::device_pool_alloc(n * 16 + 16, &rec->names_cap);
-    PoolBlock offs(n * 8 + 8);
-    auto* names = static_cast<uint64_t*>(rec->names);
-    if (n) HIP_CHECK(hipMemsetAsync(rec->names, 0, n * 16, s));
-    dev.prof_begin(s);
-    smh::launch_parse_compact(format, text, len, ws.ptr, tot, static_cast<uint8_t*>(rec->seq), static_cast<uint64_t*>(offs.ptr),
-                              names, names + n, totals_dev, s);
-    dev.prof_end("parse_compact", s);
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&rec->offsets), (n + 1) * 8, hipHostMallocDefault));
-    if (n) HIP_CHECK(hipMemcpyAsync(rec->offsets, offs.ptr, n * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(&tot.err, &totals_dev->err, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    rec->offsets[n] = tot.total;
-  } else {
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&rec->offsets), 8, hipHostMallocDefault));
-    rec->offsets[0] = 0;
-  }
-  if (tot.err != ~0ull) {
-    if (format == smh::kFormatFasta)
-      throw Error(smh::kMsg, "FASTA: sequence data in front of the first header at byte " + std::to_string(tot.err));
-    throw Error(smh::kMsg, "FASTQ: malformed record " + std::to_string(tot.err) +
-                               " (no '@', no '+', quality and sequence lengths differ, or the record is cut short)");
-  }
-  rec->n = (uint32_t)tot.n_records;
-  rec->total = tot.total;
-  return rec.release();
+    if (len) require(text, what);
+    auto rec = std::make_unique<SmhRecords>();
+    smh::parse_records(rec.get(), text, on_host, len, format, stream, dev);
+    return rec.release();
+  });
 }
-
-}  // namespace
-
-extern "C" {
-
 SmhRecords* smh_records_parse_dev(const void* text_dev, uint64_t len, int format, void* stream) {
-  return pad<SmhRecords*>([&] {
-    auto& dev = smh::Device::get();
-    if (len) require(text_dev, "text_dev");
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    return parse_records(static_cast<const uint8_t*>(text_dev), len, format, dev.user_stream(stream));
-  });
+  return records_parse(text_dev, "text_dev", false, len, format, stream);
 }
-
-SmhRecords* smh_records_parse(const char* text, uint64_t len, int format) {
-  return pad<SmhRecords*>([&] {
-    auto& dev = smh::Device::get();
-    if (len) require(text, "text");
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.stream();
-    PoolBlock up(len + 64);
-    if (len) HIP_CHECK(hipMemcpyAsync(up.ptr, text, len, hipMemcpyHostToDevice, s));
-    return parse_records(static_cast<const uint8_t*>(up.ptr), len, format, s);
-  });
-}
-
+SmhRecords* smh_records_parse(const char* text, uint64_t len, int format) { return records_parse(text, "text", true, len, format, nullptr); }
 void smh_records_free(SmhRecords* r) { delete r; }
 uint32_t smh_records_len(const SmhRecords* r) { return r ? r->n : 0; }
 uint64_t smh_records_total(const SmhRecords* r) { return r ? r->total : 0; }
 int smh_records_format(const SmhRecords* r) { return r ? r->format : 0; }
-const void* smh_records_seq_dev(const SmhRecords* r) { return r ? r->seq : nullptr; }
+const void* smh_records_seq_dev(const SmhRecords* r) { return r ? r->seq_dev() : nullptr; }
 const uint64_t* smh_records_offsets(const SmhRecords* r) { return r ? r->offsets : nullptr; }
 uint32_t smh_records_tile_bytes(void) { return smh::kParseTileBytes; }
 
@@ -593,26 +490,14 @@ int smh_records_names(const SmhRecords* r, uint64_t* start_out, uint32_t* len_ou
     require(r, "r");
     if (r->n == 0) return;
     require(start_out, "start_out"); require(len_out, "len_out");
-    auto& dev = smh::Device::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.stream();
-    std::vector<uint64_t> ends(r->n);
-    const uint64_t* names = static_cast<const uint64_t*>(r->names);
-    HIP_CHECK(hipMemcpyAsync(start_out, names, (size_t)r->n * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(ends.data(), names + r->n, (size_t)r->n * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    for (uint32_t i = 0; i < r->n; i++) {
-      const uint64_t l = ends[i] >= start_out[i] ? ends[i] - start_out[i] : 0;
-      if (l > 0xffffffffull) throw Error(smh::kMsg, "a record name longer than 2^32 - 1 bytes");
-      len_out[i] = (uint32_t)l;
-    }
+    r->name_spans(start_out, len_out);
   });
 }
 
 int smh_add_records(KmerMinHash* ptr, const SmhRecords* r, bool force) {
   return pad_code([&] {
     require(ptr, "ptr"); require(r, "r");
-    ptr->add_sequences_device(static_cast<const uint8_t*>(r->seq), r->total, r->offsets, r->n, force,
+    ptr->add_sequences_device(r->seq_dev(), r->total, r->offsets, r->n, force,
                               smh::Device::get().user_stream(nullptr), nullptr);
   });
 }
@@ -632,7 +517,7 @@ int smh_add_records_grouped(KmerMinHash* const* sketches, uint32_t n_sketches, c
       groups = own.data();
     }
     std::vector<smh::KmerMinHash*> mhs(sketches, sketches + n_sketches);
-    smh::add_sequences_grouped(mhs.data(), n_sketches, static_cast<const uint8_t*>(r->seq), r->total, r->offsets, groups, r->n,
+    smh::add_sequences_grouped(mhs.data(), n_sketches, r->seq_dev(), r->total, r->offsets, groups, r->n,
                                force, smh::Device::get().user_stream(nullptr), nullptr);
   });
 }
@@ -698,28 +583,8 @@ int smh_compare_block_dev(const uint64_t* row_hashes_dev, const uint64_t* row_of
   return pad_code([&] {
     if (n_rows == 0 || n_cols == 0) return;
     require(row_offsets, "row_offsets"); require(col_offsets, "col_offsets");
-    auto& dev = smh::Device::get();
-    auto& E = smh::Engine::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.user_stream(stream);
-    uint32_t mr = 0, mc = 0;
-    for (uint32_t i = 0; i < n_rows; i++) mr = std::max<uint32_t>(mr, (uint32_t)(row_offsets[i + 1] - row_offsets[i]));
-    for (uint32_t j = 0; j < n_cols; j++) mc = std::max<uint32_t>(mc, (uint32_t)(col_offsets[j + 1] - col_offsets[j]));
-    E.cmp_oa.ensure((size_t)(n_rows + 1) * 8);
-    E.cmp_ob.ensure((size_t)(n_cols + 1) * 8);
-    HIP_CHECK(hipMemcpyAsync(E.cmp_oa.ptr, row_offsets, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(E.cmp_ob.ptr, col_offsets, (size_t)(n_cols + 1) * 8, hipMemcpyHostToDevice, s));
-    smh::SketchSet R, C;
-    R.hashes = row_hashes_dev; R.offsets = E.cmp_oa.as<uint64_t>(); R.n = n_rows; R.h_offsets = row_offsets;
-    C.hashes = col_hashes_dev; C.offsets = E.cmp_ob.as<uint64_t>(); C.n = n_cols; C.h_offsets = col_offsets;
-    smh::CompareOut o;
-    o.jaccard = jaccard_dev; o.common = common_dev; o.size = size_dev; o.count_common = count_common_dev;
-    o.containment = containment_dev;
-    const bool same_sets = row_hashes_dev == col_hashes_dev && n_rows == n_cols &&
-                           std::memcmp(row_offsets, col_offsets, (size_t)(n_rows + 1) * 8) == 0;
-    smh::launch_compare_block(R, C, num, nullptr, o, dev, s, mr, mc, row_offsets[n_rows] - row_offsets[0],
-                              col_offsets[n_cols] - col_offsets[0], same_sets);
-    HIP_CHECK(hipStreamSynchronize(s));  // the offset staging buffers are reused by the next call
+    smh::Engine::get().compare_block_dev(row_hashes_dev, row_offsets, n_rows, col_hashes_dev, col_offsets, n_cols, num,
+                                         {common_dev, size_dev, jaccard_dev, count_common_dev, containment_dev}, stream);
   });
 }
 
@@ -740,10 +605,7 @@ int smh_find(KmerMinHash* const* nodes, uint32_t n_nodes, const KmerMinHash* que
     std::vector<double> val(n_nodes);
     if (containment) smh::Engine::get().compare_host(R, C, nums.data(), 0, nullptr, nullptr, nullptr, nullptr, val.data());
     else smh::Engine::get().compare_host(R, C, nums.data(), 0, nullptr, nullptr, val.data(), nullptr, nullptr);
-    uint32_t k = 0;
-    for (uint32_t i = 0; i < n_nodes; i++)
-      if (val[i] > threshold) out_indices[k++] = i;   // NaN (empty node, containment) is never > threshold
-    *out_count = k;
+    *out_count = smh::indices_above(val.data(), n_nodes, threshold, out_indices);
   });
 }
 
@@ -758,139 +620,27 @@ int smh_most_common(const KmerMinHash* leaf, KmerMinHash* const* candidates, uin
     for (uint32_t j = 0; j < n; j++) { require(candidates[j], "candidates[j]"); C[j] = candidates[j]; leaf->check_compatible(*C[j]); }
     std::vector<uint64_t> cc(n);
     smh::Engine::get().compare_host(R, C, nullptr, leaf->num, nullptr, nullptr, nullptr, cc.data(), nullptr);
-    uint32_t pos = 0;
-    uint64_t mx = 0;
-    for (uint32_t j = 0; j < n; j++)
-      if (cc[j] > mx) { mx = cc[j]; pos = j; }
-    if (best_pos) *best_pos = pos;
-    if (best_common) *best_common = mx;
+    smh::arg_max(cc.data(), n, best_pos, best_common);
   });
 }
 
-// ------------------------------------------------------------------ resident index
+// ------------------------------------------------------------------ resident index (index.cpp, angular.cpp)
 
-struct SmhIndex {
-  smh::DeviceBuffer hashes, offsets, nums;
-  std::vector<uint64_t> h_offsets;
-  std::vector<uint32_t> h_nums;
-  std::vector<smh::KmerMinHash> params;   // parameters only (mins cleared): check_compatible per node
-  uint32_t max_len = 0;
-  uint32_t n = 0;
-  // what gather asks of the whole set, decided once: every node has the parameters of node 0 (the query is then checked
-  // against that one block), and whether any node is a bottom-`num` sketch
-  bool uniform = true;
-  bool any_num = false;
-  // the dictionary of the resident set (dense ranks, components, frequent hashes), built by the first all-vs-all compare
-  // of the index with itself and kept: later ones skip the pre-pass (the nodes of an index never change)
-  smh::CollectionDict* dict = nullptr;
-  uint32_t dict_split = 0;      // the frequent-hash setting the dictionary was built under
-  // angular similarity.  has_abunds: EVERY node tracks abundances and every abundance vector matches its
-  // hashes; h_abunds then holds them narrowed to u32 (a copy, like the hashes) until the first angular call uploads them
-  // and computes the norms -- an index nobody asks pays no HBM.  bad_node: the lowest node whose norm2 does not fit 64 bits.
-  bool has_abunds = false;
-  std::vector<uint32_t> h_abunds;
-  uint32_t wide_node = smh::kAngularNoError;   // the first node holding an abundance of 2^32 or more
-  bool angular_ready = false;
-  uint32_t bad_node = smh::kAngularNoError;
-  smh::DeviceBuffer abunds_dev, norm2_dev;
-  std::vector<uint64_t> h_norm2;
-  SmhIndex() { std::lock_guard<std::mutex> g(registry_mu()); registry().insert(this); }
-  ~SmhIndex() {
-    { std::lock_guard<std::mutex> g(registry_mu()); registry().erase(this); }
-    if (dict) smh::collection_free(dict);
-  }
-  void drop_dict() { if (dict) { smh::collection_free(dict); dict = nullptr; } }
-  // the live indexes: smh_release_workspace() drops their cached dictionaries (memory no other allocator can see)
-  static std::set<SmhIndex*>& registry() { static auto* r = new std::set<SmhIndex*>(); return *r; }
-  static std::mutex& registry_mu() { static auto* m = new std::mutex(); return *m; }
-};
+struct SmhIndex : smh::ResidentIndex { using smh::ResidentIndex::ResidentIndex; };
 
 SmhIndex* smh_index_new(KmerMinHash* const* nodes, uint32_t n_nodes) {
   return pad<SmhIndex*>([&] {
     if (n_nodes) require(nodes, "nodes");
-    auto idx = std::make_unique<SmhIndex>();
-    idx->n = n_nodes;
-    idx->h_nums.resize(n_nodes);
     std::vector<const smh::KmerMinHash*> v(n_nodes);
-    for (uint32_t i = 0; i < n_nodes; i++) {
-      require(nodes[i], "nodes[i]");
-      v[i] = nodes[i];
-      idx->h_nums[i] = nodes[i]->num;
-      smh::KmerMinHash p(nodes[i]->num, nodes[i]->ksize, nodes[i]->is_protein, nodes[i]->seed, nodes[i]->max_hash, false);
-      idx->params.push_back(p);
-      const smh::KmerMinHash& p0 = idx->params[0];
-      idx->uniform &= p.ksize == p0.ksize && p.is_protein == p0.is_protein && p.max_hash == p0.max_hash && p.seed == p0.seed;
-      idx->any_num |= p.num != 0;
-    }
-    auto& dev = smh::Device::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.stream();
-    smh::SketchSet set;
-    smh::Engine::get().pack_sketches(v, idx->hashes, idx->offsets, &set, &idx->max_len, &idx->h_offsets, s);
-    // (pack_sketches has brought every node to the host)
-    idx->has_abunds = true;
-    for (uint32_t i = 0; i < n_nodes; i++) idx->has_abunds &= v[i]->has_abunds && v[i]->abunds.size() == v[i]->mins.size();
-    if (idx->has_abunds) {
-      idx->h_abunds.reserve(idx->h_offsets.back());
-      for (uint32_t i = 0; i < n_nodes; i++)
-        for (uint64_t a : v[i]->abunds) {
-          if (a >> 32) { idx->wide_node = std::min(idx->wide_node, i); a = 0xffffffffull; }
-          idx->h_abunds.push_back((uint32_t)a);
-        }
-    }
-    idx->nums.ensure((size_t)n_nodes * 4 + 4);
-    if (n_nodes) HIP_CHECK(hipMemcpyAsync(idx->nums.ptr, idx->h_nums.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return idx.release();
+    for (uint32_t i = 0; i < n_nodes; i++) { require(nodes[i], "nodes[i]"); v[i] = nodes[i]; }
+    return new SmhIndex(v);
   });
 }
-
 void smh_index_free(SmhIndex* index) { delete index; }
 void smh_index_drop_dictionary(SmhIndex* index) {
-  if (!index) return;
-  (void)pad_code([&] {
-    std::lock_guard<std::recursive_mutex> lock(smh::Device::get().mutex());
-    index->drop_dict();
-  });
+  if (index) (void)pad_code([&] { std::lock_guard<std::recursive_mutex> lock(smh::Device::get().mutex()); index->drop_dict(); });
 }
 uint32_t smh_index_len(const SmhIndex* index) { return index ? index->n : 0; }
-
-namespace {
-// rows = resident index, cols = one host sketch: N x 1 block on the device, values back on the host
-void index_vs_one(SmhIndex* index, const smh::KmerMinHash* q, bool q_is_row, double* jac, double* cont, uint64_t* cc) {
-  auto& dev = smh::Device::get();
-  auto& E = smh::Engine::get();
-  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-  hipStream_t s = dev.stream();
-  q->materialize();
-  const uint32_t n = index->n;
-  const uint64_t qoff[2] = {0, (uint64_t)q->mins.size()};
-  E.cmp_b.ensure(q->mins.size() * 8 + 8);
-  E.cmp_ob.ensure(16);
-  E.cmp_out.ensure((size_t)n * 8 * 3 + 64);
-  if (!q->mins.empty())
-    HIP_CHECK(hipMemcpyAsync(E.cmp_b.ptr, q->mins.data(), q->mins.size() * 8, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(E.cmp_ob.ptr, qoff, 16, hipMemcpyHostToDevice, s));
-  smh::SketchSet I, Q;
-  I.hashes = index->hashes.as<uint64_t>(); I.offsets = index->offsets.as<uint64_t>(); I.n = n;
-  Q.hashes = E.cmp_b.as<uint64_t>(); Q.offsets = E.cmp_ob.as<uint64_t>(); Q.n = 1;
-  double* d_j = E.cmp_out.as<double>();
-  double* d_c = d_j + n;
-  uint64_t* d_cc = reinterpret_cast<uint64_t*>(d_c + n);
-  smh::CompareOut o;
-  o.jaccard = jac ? d_j : nullptr; o.containment = cont ? d_c : nullptr; o.count_common = cc ? d_cc : nullptr;
-  if (!q_is_row)
-    smh::launch_compare_block(I, Q, 0, index->nums.as<uint32_t>(), o, dev, s, index->max_len, (uint32_t)q->mins.size(),
-                              index->h_offsets.back(), q->mins.size());
-  else
-    smh::launch_compare_block(Q, I, q->num, nullptr, o, dev, s, (uint32_t)q->mins.size(), index->max_len, q->mins.size(),
-                              index->h_offsets.back());
-  if (jac) HIP_CHECK(hipMemcpyAsync(jac, d_j, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  if (cont) HIP_CHECK(hipMemcpyAsync(cont, d_c, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  if (cc) HIP_CHECK(hipMemcpyAsync(cc, d_cc, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-}
-}  // namespace
 
 int smh_index_find(SmhIndex* index, const KmerMinHash* query, double threshold, bool containment, uint32_t* out_indices,
                    uint32_t* out_count) {
@@ -899,32 +649,18 @@ int smh_index_find(SmhIndex* index, const KmerMinHash* query, double threshold, 
     *out_count = 0;
     if (index->n == 0) return;
     require(out_indices, "out_indices");
-    for (auto& p : index->params) p.check_compatible(*query);
-    std::vector<double> val(index->n);
-    index_vs_one(index, query, false, containment ? nullptr : val.data(), containment ? val.data() : nullptr, nullptr);
-    uint32_t k = 0;
-    for (uint32_t i = 0; i < index->n; i++)
-      if (val[i] > threshold) out_indices[k++] = i;
-    *out_count = k;
+    *out_count = index->find(*query, threshold, containment, out_indices);
   });
 }
-
 int smh_index_most_common(SmhIndex* index, const KmerMinHash* leaf, uint32_t* best_pos, uint64_t* best_common) {
   return pad_code([&] {
     require(index, "index"); require(leaf, "leaf");
     if (best_pos) *best_pos = 0;
     if (best_common) *best_common = 0;
     if (index->n == 0) return;
-    for (auto& p : index->params) leaf->check_compatible(p);
-    std::vector<uint64_t> cc(index->n);
-    index_vs_one(index, leaf, true, nullptr, nullptr, cc.data());
-    uint32_t pos = 0; uint64_t mx = 0;
-    for (uint32_t j = 0; j < index->n; j++) if (cc[j] > mx) { mx = cc[j]; pos = j; }
-    if (best_pos) *best_pos = pos;
-    if (best_common) *best_common = mx;
+    index->most_common(*leaf, best_pos, best_common);
   });
 }
-
 static_assert(sizeof(SmhGatherRow) == 24 && sizeof(smh::GatherRow) == 24, "SmhGatherRow is 24 bytes");
 static_assert(offsetof(SmhGatherRow, abund_sum) == 16 && offsetof(smh::GatherRow, abund_sum) == 16, "SmhGatherRow layout");
 
@@ -935,465 +671,49 @@ int smh_index_gather(SmhIndex* index, const KmerMinHash* query, uint32_t thresho
     require(index, "index"); require(query, "query"); require(n_rows, "n_rows");
     *n_rows = 0;
     if (rows_capacity) require(rows, "rows");
-    if (query->num != 0) throw Error(smh::kMsg, "gather: the query is a num sketch; only scaled sketches (num == 0) can be gathered");
-    if (index->any_num) throw Error(smh::kMsg, "gather: the index holds a num sketch; only scaled sketches (num == 0) can be gathered");
-    if (index->n) {
-      if (index->uniform) index->params[0].check_compatible(*query);
-      else for (auto& p : index->params) p.check_compatible(*query);   // nodes that differ: one of them refuses the query
-    }
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.stream();
-    query->flush_pending();
-    // the query where it lives: a state in HBM is read there (uniq + counts or run starts), a host state is uploaded once
-    smh::GatherQuery q;
-    smh::DeviceBuffer up;
-    uint64_t lq = 0;
-    if (query->dev) {
-      const smh::DeviceSketch& S = *query->dev;
-      lq = S.n;
-      q.hashes = S.uniq.as<uint64_t>();
-      if (query->has_abunds) {
-        if (S.has_counts) q.counts = S.counts.as<uint64_t>();
-        else if (S.has_runs) { q.starts = S.starts.as<uint32_t>(); q.total = (uint32_t)S.total; }
-        else smh::throw_internal("gather: the query's device state carries no abundances");
-      }
-    } else {
-      lq = query->mins.size();
-      if (query->has_abunds && query->abunds.size() != lq)
-        smh::throw_internal("gather: the query's abundance vector does not match its hashes (quirks Q5/Q6)");
-      if (lq) {
-        up.ensure(lq * 8 * (query->has_abunds ? 2 : 1));
-        HIP_CHECK(hipMemcpyAsync(up.ptr, query->mins.data(), lq * 8, hipMemcpyHostToDevice, s));
-        q.hashes = up.as<uint64_t>();
-        if (query->has_abunds) {
-          HIP_CHECK(hipMemcpyAsync(up.as<uint64_t>() + lq, query->abunds.data(), lq * 8, hipMemcpyHostToDevice, s));
-          q.counts = up.as<uint64_t>() + lq;
-        }
-      }
-    }
-    if (lq >= 0xffffffffull) smh::throw_internal("gather: a query of 2^32 - 1 or more hashes");
-    q.n = (uint32_t)lq;
-    if (index->n == 0 || lq == 0) {
-      if (assigned && lq) std::fill(assigned, assigned + lq, 0xffffffffu);
-      return;
-    }
-    smh::SketchSet I;
-    I.hashes = index->hashes.as<uint64_t>(); I.offsets = index->offsets.as<uint64_t>(); I.n = index->n;
-    I.h_offsets = index->h_offsets.data();
-    *n_rows = smh::gather_run(I, index->max_len, q, threshold_common, reinterpret_cast<smh::GatherRow*>(rows), rows_capacity,
-                              assigned, dev, s);
-    up.release_after_sync();   // gather_run returns with the stream idle
+    *n_rows = index->gather(*query, threshold_common, reinterpret_cast<smh::GatherRow*>(rows), rows_capacity, assigned, dev);
   });
 }
 uint32_t smh_gather_rounds_per_sync(void) { return smh::kGatherRoundsPerSync; }
 
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {
-  return pad_code([&] {
-    require(rows, "rows"); require(cols, "cols");
-    const size_t np = (size_t)rows->n * cols->n;
-    if (np == 0) return;
-    for (auto& r : rows->params) for (auto& c : cols->params) r.check_compatible(c);
-    auto& dev = smh::Device::get();
-    auto& E = smh::Engine::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.stream();
-    E.cmp_out.ensure(np * 8 * 5 + 64);
-    uint64_t* d_common = E.cmp_out.as<uint64_t>();
-    uint64_t* d_size = d_common + np;
-    double* d_jac = reinterpret_cast<double*>(d_size + np);
-    uint64_t* d_cc = reinterpret_cast<uint64_t*>(d_jac + np);
-    double* d_cont = reinterpret_cast<double*>(d_cc + np);
-    smh::SketchSet R, C;
-    R.hashes = rows->hashes.as<uint64_t>(); R.offsets = rows->offsets.as<uint64_t>(); R.n = rows->n;
-    C.hashes = cols->hashes.as<uint64_t>(); C.offsets = cols->offsets.as<uint64_t>(); C.n = cols->n;
-    R.h_offsets = rows->h_offsets.data(); C.h_offsets = cols->h_offsets.data();
-    smh::CompareOut o;
-    o.common = common ? d_common : nullptr; o.size = size ? d_size : nullptr; o.jaccard = jaccard ? d_jac : nullptr;
-    o.count_common = count_common ? d_cc : nullptr; o.containment = containment ? d_cont : nullptr;
-    // one num for every row: pass it as the launch-wide value (lets an index against itself use symmetry)
-    bool uniform = true;
-    for (uint32_t v : rows->h_nums) uniform &= v == rows->h_nums[0];
-    const smh::CompareTuning tune = smh::compare_get_tuning();
-    const bool block_route = tune.route == smh::kRouteAuto ? (np >= 4096 && rows->n >= 16) : (tune.route == smh::kRouteComponents || tune.route == smh::kRouteTiled);
-    if (rows == cols && block_route && rows->h_offsets.back() > 0) {
-      // an index against itself: its dictionary is built once and reused (the pre-pass is most of a sparse matrix's time)
-      if (rows->dict && rows->dict_split != tune.split_frequent) { smh::collection_free(rows->dict); rows->dict = nullptr; }
-      if (!rows->dict) {
-        rows->dict = smh::collection_begin(R.hashes, R.offsets, rows->h_offsets.data(), rows->n, 1, 0, dev, s);
-        smh::collection_finish(rows->dict, nullptr, dev, s);
-        rows->dict_split = tune.split_frequent;
-      }
-      smh::collection_compare(rows->dict, 0, rows->n, 0, rows->n, uniform ? rows->h_nums[0] : 0,
-                              uniform ? nullptr : rows->nums.as<uint32_t>(), 1, o, dev, s);
-    } else
-    smh::launch_compare_block(R, C, uniform ? rows->h_nums[0] : 0, uniform ? nullptr : rows->nums.as<uint32_t>(), o, dev, s,
-                              rows->max_len, cols->max_len, rows->h_offsets.back(), cols->h_offsets.back(), rows == cols);
-    if (common) HIP_CHECK(hipMemcpyAsync(common, d_common, np * 8, hipMemcpyDeviceToHost, s));
-    if (size) HIP_CHECK(hipMemcpyAsync(size, d_size, np * 8, hipMemcpyDeviceToHost, s));
-    if (jaccard) HIP_CHECK(hipMemcpyAsync(jaccard, d_jac, np * 8, hipMemcpyDeviceToHost, s));
-    if (count_common) HIP_CHECK(hipMemcpyAsync(count_common, d_cc, np * 8, hipMemcpyDeviceToHost, s));
-    if (containment) HIP_CHECK(hipMemcpyAsync(containment, d_cont, np * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  });
+  return pad_code([&] { require(rows, "rows"); require(cols, "cols"); rows->compare(*cols, jaccard, common, size, count_common, containment); });
 }
 
 // ------------------------------------------------------------------ angular similarity on abundances
 
-}  // extern "C" (the helpers below hold templates)
-
-namespace {
-
-// a block of the device pool for the length of one call
-struct CallBlock {
-  void* ptr = nullptr;
-  size_t cap = 0;
-  bool synced = false;   // the stream was waited for: nothing can still be using the block
-  explicit CallBlock(size_t bytes) { ptr = smh::device_pool_alloc(bytes ? bytes : 1, &cap); }
-  CallBlock(const CallBlock&) = delete;
-  CallBlock& operator=(const CallBlock&) = delete;
-  ~CallBlock() { smh::device_pool_free(ptr, cap, !synced); }
-  template <class T> T* as() const { return reinterpret_cast<T*>(ptr); }
-};
-
-// From this many pairs on smh_index_angular first runs the block compare for count_common and walks only the pairs that
-// share a hash.  Chosen from tools/bench_angular.py's sweep ("The prune threshold").
-constexpr uint64_t kAngularPruneMinPairs = 4096;
-uint64_t g_angular_prune_min_pairs = kAngularPruneMinPairs;
-uint64_t g_angular_walked = 0, g_angular_skipped = 0;
-
-void angular_require_tracking(const smh::KmerMinHash* mh, const char* what) {
-  if (!mh->has_abunds) throw Error(smh::kMsg, std::string("angular: ") + what + " does not track abundances");
-}
-[[noreturn]] void angular_throw_norm(const std::string& who) {
-  throw Error(smh::kMsg, "angular: norm2 of " + who + " does not fit 64 bits (an abundance of 2^32 or more, or too many large ones)");
-}
-// what can be said about a sketch without the device: a host state whose abundance vector does not match its hashes
-void angular_check_host_state(const smh::KmerMinHash* mh, const char* what) {
-  if (!mh->dev && mh->pend_seq.empty() && mh->pend_words.empty() && mh->abunds.size() != mh->mins.size())
-    throw Error(smh::kMsg, std::string("angular: the abundance vector of ") + what + " does not match its hashes (quirks Q5/Q6)");
-}
-
-// One sketch in the form the kernels read: hashes and u32 abundances in device memory, offsets {0, n}, its norm2.  A state
-// that lives in HBM is read there (its abundances are narrowed by a kernel); a host state is uploaded.
-struct AngularOperand {
-  const uint64_t* hashes = nullptr;
-  const uint32_t* abunds = nullptr;
-  uint32_t n = 0;
-  std::unique_ptr<CallBlock> store, small;   // small: offsets (2 x u64), norm2 (u64), error word (u32)
-  std::vector<uint32_t> staged;
-  uint64_t off[2] = {0, 0};
-  uint64_t* offsets_dev() const { return small->as<uint64_t>(); }
-  uint64_t* norm2_dev() const { return small->as<uint64_t>() + 2; }
-  uint32_t* err_dev() const { return reinterpret_cast<uint32_t*>(small->as<uint64_t>() + 3); }
-  void done() { if (store) store->synced = true; if (small) small->synced = true; }
-};
-
-// queues the operand's upload / narrowing and its norm; the caller synchronises and then reads h_norm2 / h_err
-void angular_prepare(AngularOperand& op, const smh::KmerMinHash* mh, const char* what, uint64_t* h_norm2, uint32_t* h_err, hipStream_t s) {
-  mh->flush_pending();
-  op.small = std::make_unique<CallBlock>(32);
-  HIP_CHECK(hipMemsetAsync(op.err_dev(), 0xff, 4, s));
-  uint64_t n = 0;
-  if (mh->dev) {
-    const smh::DeviceSketch& S = *mh->dev;
-    n = S.n;
-    if (n >= 0xffffffffull) smh::throw_internal("angular: a sketch of 2^32 - 1 or more hashes");
-    if (n && !S.has_counts && !S.has_runs) smh::throw_internal("angular: the sketch's device state carries no abundances");
-    op.store = std::make_unique<CallBlock>(n * 4);
-    op.hashes = S.uniq.as<uint64_t>();
-    op.abunds = op.store->as<uint32_t>();
-    smh::launch_angular_narrow(S.has_counts ? S.counts.as<uint64_t>() : nullptr, S.has_counts ? nullptr : S.starts.as<uint32_t>(),
-                               (uint32_t)S.total, (uint32_t)n, op.store->as<uint32_t>(), op.err_dev(), 0, s);
-  } else {
-    n = mh->mins.size();
-    if (mh->abunds.size() != n)
-      throw Error(smh::kMsg, std::string("angular: the abundance vector of ") + what + " does not match its hashes (quirks Q5/Q6)");
-    if (n >= 0xffffffffull) smh::throw_internal("angular: a sketch of 2^32 - 1 or more hashes");
-    op.staged.resize(n);
-    for (uint64_t i = 0; i < n; i++) {
-      if (mh->abunds[i] >> 32) angular_throw_norm(what);
-      op.staged[i] = (uint32_t)mh->abunds[i];
-    }
-    op.store = std::make_unique<CallBlock>(n * 12);
-    if (n) {
-      HIP_CHECK(hipMemcpyAsync(op.store->ptr, mh->mins.data(), n * 8, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(op.store->as<uint64_t>() + n, op.staged.data(), n * 4, hipMemcpyHostToDevice, s));
-    }
-    op.hashes = op.store->as<uint64_t>();
-    op.abunds = reinterpret_cast<const uint32_t*>(op.store->as<uint64_t>() + n);
-  }
-  op.n = (uint32_t)n;
-  op.off[1] = n;
-  HIP_CHECK(hipMemcpyAsync(op.offsets_dev(), op.off, 16, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemsetAsync(op.norm2_dev(), 0, 8, s));
-  smh::launch_angular_norms(op.abunds, op.offsets_dev(), 1, op.norm2_dev(), op.err_dev(), s);
-  HIP_CHECK(hipMemcpyAsync(h_norm2, op.norm2_dev(), 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(h_err, op.err_dev(), 4, hipMemcpyDeviceToHost, s));
-}
-
-smh::AngularSet angular_set(const AngularOperand& op) {
-  smh::AngularSet a;
-  a.hashes = op.hashes; a.abunds = op.abunds; a.offsets = op.offsets_dev(); a.norm2 = op.norm2_dev(); a.n = 1;
-  return a;
-}
-
-// the first angular call on an index: abundances to HBM, norms computed and read back
-void angular_ensure_index(SmhIndex* index, const char* what, hipStream_t s) {
-  if (!index->angular_ready) {
-    const uint32_t n = index->n;
-    index->abunds_dev.ensure(index->h_abunds.size() * 4 + 4);
-    index->norm2_dev.ensure((size_t)n * 8 + 8);
-    index->h_norm2.assign(n, 0);
-    uint32_t err = smh::kAngularNoError;
-    if (n) {
-      CallBlock e(4);
-      HIP_CHECK(hipMemsetAsync(e.ptr, 0xff, 4, s));
-      if (!index->h_abunds.empty())
-        HIP_CHECK(hipMemcpyAsync(index->abunds_dev.ptr, index->h_abunds.data(), index->h_abunds.size() * 4, hipMemcpyHostToDevice, s));
-      smh::launch_angular_norms(index->abunds_dev.as<uint32_t>(), index->offsets.as<uint64_t>(), n, index->norm2_dev.as<uint64_t>(),
-                                e.as<uint32_t>(), s);
-      HIP_CHECK(hipMemcpyAsync(index->h_norm2.data(), index->norm2_dev.ptr, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(&err, e.ptr, 4, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      e.synced = true;
-    }
-    index->bad_node = std::min(index->wide_node, err);
-    std::vector<uint32_t>().swap(index->h_abunds);   // they live in HBM now
-    index->angular_ready = true;
-  }
-  if (index->bad_node != smh::kAngularNoError) angular_throw_norm(std::string(what) + " " + std::to_string(index->bad_node));
-}
-
-void angular_require_index(const SmhIndex* index, const char* what) {
-  if (!index->has_abunds)
-    throw Error(smh::kMsg, std::string("angular: ") + what + " holds a node that does not track abundances, or whose abundance "
-                "vector does not match its hashes (quirks Q5/Q6)");
-}
-
-smh::AngularSet angular_set(const SmhIndex* index) {
-  smh::AngularSet a;
-  a.hashes = index->hashes.as<uint64_t>(); a.abunds = index->abunds_dev.as<uint32_t>(); a.offsets = index->offsets.as<uint64_t>();
-  a.norm2 = index->norm2_dev.as<uint64_t>(); a.n = index->n;
-  return a;
-}
-
-// count_common of rows x cols into d_cc (np entries): the route smh_index_compare takes, the cached dictionary included
-void angular_count_common(SmhIndex* rows, SmhIndex* cols, uint64_t* d_cc, smh::Device& dev, hipStream_t s) {
-  const size_t np = (size_t)rows->n * cols->n;
-  smh::SketchSet R, C;
-  R.hashes = rows->hashes.as<uint64_t>(); R.offsets = rows->offsets.as<uint64_t>(); R.n = rows->n;
-  C.hashes = cols->hashes.as<uint64_t>(); C.offsets = cols->offsets.as<uint64_t>(); C.n = cols->n;
-  R.h_offsets = rows->h_offsets.data(); C.h_offsets = cols->h_offsets.data();
-  smh::CompareOut o;
-  o.count_common = d_cc;
-  bool uniform = true;
-  for (uint32_t v : rows->h_nums) uniform &= v == rows->h_nums[0];
-  const smh::CompareTuning tune = smh::compare_get_tuning();
-  const bool block_route = tune.route == smh::kRouteAuto ? (np >= 4096 && rows->n >= 16) : (tune.route == smh::kRouteComponents || tune.route == smh::kRouteTiled);
-  if (rows == cols && block_route && rows->h_offsets.back() > 0) {
-    if (rows->dict && rows->dict_split != tune.split_frequent) { smh::collection_free(rows->dict); rows->dict = nullptr; }
-    if (!rows->dict) {
-      rows->dict = smh::collection_begin(R.hashes, R.offsets, rows->h_offsets.data(), rows->n, 1, 0, dev, s);
-      smh::collection_finish(rows->dict, nullptr, dev, s);
-      rows->dict_split = tune.split_frequent;
-    }
-    smh::collection_compare(rows->dict, 0, rows->n, 0, rows->n, uniform ? rows->h_nums[0] : 0,
-                            uniform ? nullptr : rows->nums.as<uint32_t>(), 1, o, dev, s);
-  } else {
-    smh::launch_compare_block(R, C, uniform ? rows->h_nums[0] : 0, uniform ? nullptr : rows->nums.as<uint32_t>(), o, dev, s,
-                              rows->max_len, cols->max_len, rows->h_offsets.back(), cols->h_offsets.back(), rows == cols);
-  }
-}
-
-// runs the block kernel into pool memory and brings the wanted outputs and the two counters back; the stream is idle after
-void angular_run_host(const smh::AngularSet& R, const smh::AngularSet& C, const uint64_t* prune_dev, bool symmetric, uint64_t* dot,
-                      double* cosine, double* angular, smh::Device& dev, hipStream_t s) {
-  const size_t np = (size_t)R.n * C.n;
-  CallBlock d_dot(dot ? np * 8 : 0), d_cos(cosine ? np * 8 : 0), d_ang(angular ? np * 8 : 0), d_cnt(16);
-  smh::AngularOut o;
-  o.dot = dot ? d_dot.as<uint64_t>() : nullptr; o.cosine = cosine ? d_cos.as<double>() : nullptr;
-  o.angular = angular ? d_ang.as<double>() : nullptr;
-  smh::launch_angular_block(R, C, prune_dev, symmetric, o, d_cnt.as<unsigned long long>(), dev, s);
-  uint64_t cnt[2] = {0, 0};
-  if (dot) HIP_CHECK(hipMemcpyAsync(dot, d_dot.ptr, np * 8, hipMemcpyDeviceToHost, s));
-  if (cosine) HIP_CHECK(hipMemcpyAsync(cosine, d_cos.ptr, np * 8, hipMemcpyDeviceToHost, s));
-  if (angular) HIP_CHECK(hipMemcpyAsync(angular, d_ang.ptr, np * 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.ptr, 16, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  d_dot.synced = d_cos.synced = d_ang.synced = d_cnt.synced = true;
-  g_angular_walked = cnt[0]; g_angular_skipped = cnt[1];
-}
-
-}  // namespace
-
-extern "C" {
-
 bool smh_index_has_abundances(const SmhIndex* index) { return index && index->has_abunds; }
 
-int smh_index_norms2(SmhIndex* index, uint64_t* out) {
-  return pad_code([&] {
-    require(index, "index");
-    angular_require_index(index, "the index");
-    if (index->n == 0) return;
-    require(out, "out");
-    auto& dev = smh::Device::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    angular_ensure_index(index, "node", dev.stream());
-    std::copy(index->h_norm2.begin(), index->h_norm2.end(), out);
-  });
-}
-
+int smh_index_norms2(SmhIndex* index, uint64_t* out) { return pad_code([&] { require(index, "index"); index->norms2(out); }); }
 int smh_index_angular(SmhIndex* rows, SmhIndex* cols, uint64_t* dot, double* cosine, double* angular) {
-  return pad_code([&] {
-    require(rows, "rows"); require(cols, "cols");
-    angular_require_index(rows, "the row index");
-    angular_require_index(cols, "the column index");
-    if (rows->n && cols->n) {
-      if (rows->uniform && cols->uniform) rows->params[0].check_compatible(cols->params[0]);
-      else for (auto& r : rows->params) for (auto& c : cols->params) r.check_compatible(c);
-    }
-    const size_t np = (size_t)rows->n * cols->n;
-    auto& dev = smh::Device::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.stream();
-    g_angular_walked = g_angular_skipped = 0;
-    angular_ensure_index(rows, rows == cols ? "node" : "row node", s);
-    if (rows != cols) angular_ensure_index(cols, "column node", s);
-    if (np == 0) return;
-    std::unique_ptr<CallBlock> cc;
-    if (np >= g_angular_prune_min_pairs) {
-      cc = std::make_unique<CallBlock>(np * 8);
-      angular_count_common(rows, cols, cc->as<uint64_t>(), dev, s);
-    }
-    angular_run_host(angular_set(rows), angular_set(cols), cc ? cc->as<uint64_t>() : nullptr, rows == cols, dot, cosine, angular, dev, s);
-    if (cc) cc->synced = true;
-  });
+  return pad_code([&] { require(rows, "rows"); require(cols, "cols"); rows->angular(*cols, dot, cosine, angular); });
 }
-
 int smh_index_angular_query(SmhIndex* index, const KmerMinHash* query, uint64_t* dot, uint64_t* query_norm2, double* cosine,
                             double* angular) {
-  return pad_code([&] {
-    require(index, "index"); require(query, "query");
-    angular_require_index(index, "the index");
-    angular_require_tracking(query, "the query");
-    angular_check_host_state(query, "the query");
-    if (index->n) {
-      if (index->uniform) index->params[0].check_compatible(*query);
-      else for (auto& p : index->params) p.check_compatible(*query);
-    }
-    auto& dev = smh::Device::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.stream();
-    g_angular_walked = g_angular_skipped = 0;
-    angular_ensure_index(index, "node", s);
-    AngularOperand q;
-    uint64_t n2 = 0;
-    uint32_t err = smh::kAngularNoError;
-    angular_prepare(q, query, "the query", &n2, &err, s);
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (err != smh::kAngularNoError) { q.done(); angular_throw_norm("the query"); }
-    if (query_norm2) std::fill(query_norm2, query_norm2 + index->n, n2);
-    if (index->n) angular_run_host(angular_set(q), angular_set(index), nullptr, false, dot, cosine, angular, dev, s);
-    q.done();
-  });
+  return pad_code([&] { require(index, "index"); require(query, "query"); index->angular_query(*query, dot, query_norm2, cosine, angular); });
 }
-
 int smh_angular_similarity(const KmerMinHash* a, const KmerMinHash* b, double* angular, double* cosine, uint64_t* dot,
                            uint64_t* norm2_a, uint64_t* norm2_b) {
-  return pad_code([&] {
-    require(a, "a"); require(b, "b");
-    angular_require_tracking(a, "the first sketch");
-    angular_require_tracking(b, "the second sketch");
-    a->check_compatible(*b);
-    angular_check_host_state(a, "the first sketch");
-    angular_check_host_state(b, "the second sketch");
-    auto& dev = smh::Device::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.stream();
-    g_angular_walked = g_angular_skipped = 0;
-    AngularOperand A, B;
-    uint64_t n2[2] = {0, 0};
-    uint32_t err[2] = {smh::kAngularNoError, smh::kAngularNoError};
-    angular_prepare(A, a, "the first sketch", &n2[0], &err[0], s);
-    angular_prepare(B, b, "the second sketch", &n2[1], &err[1], s);
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (err[0] != smh::kAngularNoError || err[1] != smh::kAngularNoError) {
-      A.done(); B.done();
-      angular_throw_norm(err[0] != smh::kAngularNoError ? "the first sketch" : "the second sketch");
-    }
-    uint64_t d = 0;
-    double c = 0.0, an = 0.0;
-    angular_run_host(angular_set(A), angular_set(B), nullptr, false, &d, &c, &an, dev, s);
-    A.done(); B.done();
-    if (angular) *angular = an;
-    if (cosine) *cosine = c;
-    if (dot) *dot = d;
-    if (norm2_a) *norm2_a = n2[0];
-    if (norm2_b) *norm2_b = n2[1];
-  });
+  return pad_code([&] { require(a, "a"); require(b, "b"); smh::angular_similarity(*a, *b, angular, cosine, dot, norm2_a, norm2_b); });
 }
-
 int smh_angular_block_dev(const uint64_t* row_hashes_dev, const uint32_t* row_abunds_dev, const uint64_t* row_offsets, uint32_t n_rows,
                           const uint64_t* col_hashes_dev, const uint32_t* col_abunds_dev, const uint64_t* col_offsets, uint32_t n_cols,
                           const uint64_t* count_common_dev, bool symmetric, uint64_t* dot_dev, uint64_t* row_norm2_dev,
                           uint64_t* col_norm2_dev, double* cosine_dev, double* angular_dev, void* stream) {
   return pad_code([&] {
     require(row_offsets, "row_offsets"); require(col_offsets, "col_offsets");
-    if (symmetric && (n_rows != n_cols || std::memcmp(row_offsets, col_offsets, ((size_t)n_rows + 1) * 8) != 0))
-      throw Error(smh::kMsg, "angular: a symmetric block needs the same sketches as rows and as columns");
-    for (uint32_t i = 0; i < n_rows; i++)
-      if (row_offsets[i + 1] < row_offsets[i] || row_offsets[i + 1] - row_offsets[i] >= 0xffffffffull)
-        throw Error(smh::kMsg, "angular: row_offsets must ascend, with sketches shorter than 2^32 - 1");
-    for (uint32_t j = 0; j < n_cols; j++)
-      if (col_offsets[j + 1] < col_offsets[j] || col_offsets[j + 1] - col_offsets[j] >= 0xffffffffull)
-        throw Error(smh::kMsg, "angular: col_offsets must ascend, with sketches shorter than 2^32 - 1");
-    if (row_offsets[n_rows] > row_offsets[0]) { require(row_hashes_dev, "row_hashes_dev"); require(row_abunds_dev, "row_abunds_dev"); }
-    if (col_offsets[n_cols] > col_offsets[0]) { require(col_hashes_dev, "col_hashes_dev"); require(col_abunds_dev, "col_abunds_dev"); }
-    auto& dev = smh::Device::get();
-    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-    hipStream_t s = dev.user_stream(stream);
-    g_angular_walked = g_angular_skipped = 0;
-    CallBlock offs(((size_t)n_rows + n_cols + 2) * 8), norms(((size_t)n_rows + n_cols) * 8), small(32);
-    uint64_t* d_ro = offs.as<uint64_t>();
-    uint64_t* d_co = d_ro + n_rows + 1;
-    uint64_t* d_rn = row_norm2_dev ? row_norm2_dev : norms.as<uint64_t>();
-    uint64_t* d_cn = col_norm2_dev ? col_norm2_dev : norms.as<uint64_t>() + n_rows;
-    unsigned long long* d_cnt = small.as<unsigned long long>();
-    uint32_t* d_err = reinterpret_cast<uint32_t*>(d_cnt + 2);
-    HIP_CHECK(hipMemcpyAsync(d_ro, row_offsets, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_co, col_offsets, ((size_t)n_cols + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemsetAsync(d_err, 0xff, 8, s));
-    smh::launch_angular_norms(row_abunds_dev, d_ro, n_rows, d_rn, d_err, s);
-    smh::launch_angular_norms(col_abunds_dev, d_co, n_cols, d_cn, d_err + 1, s);
-    uint32_t err[2] = {smh::kAngularNoError, smh::kAngularNoError};
-    HIP_CHECK(hipMemcpyAsync(err, d_err, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (err[0] != smh::kAngularNoError || err[1] != smh::kAngularNoError) {
-      offs.synced = norms.synced = small.synced = true;
-      if (err[0] != smh::kAngularNoError) angular_throw_norm("row sketch " + std::to_string(err[0]));
-      angular_throw_norm("column sketch " + std::to_string(err[1]));
-    }
-    smh::AngularSet R, C;
-    R.hashes = row_hashes_dev; R.abunds = row_abunds_dev; R.offsets = d_ro; R.norm2 = d_rn; R.n = n_rows;
-    C.hashes = col_hashes_dev; C.abunds = col_abunds_dev; C.offsets = d_co; C.norm2 = d_cn; C.n = n_cols;
-    smh::AngularOut o;
-    o.dot = dot_dev; o.cosine = cosine_dev; o.angular = angular_dev;
-    smh::launch_angular_block(R, C, count_common_dev, symmetric, o, d_cnt, dev, s);
-    uint64_t cnt[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(cnt, d_cnt, 16, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));   // the offsets and the counters live in blocks that go back to the pool now
-    offs.synced = norms.synced = small.synced = true;
-    g_angular_walked = cnt[0]; g_angular_skipped = cnt[1];
+    smh::angular_block_dev({row_hashes_dev, row_abunds_dev, nullptr, nullptr, n_rows}, row_offsets,
+                           {col_hashes_dev, col_abunds_dev, nullptr, nullptr, n_cols}, col_offsets, count_common_dev, symmetric,
+                           {dot_dev, cosine_dev, angular_dev}, row_norm2_dev, col_norm2_dev, stream);
   });
 }
-
 void smh_angular_last_stats(uint64_t* pairs_walked, uint64_t* pairs_skipped) {
-  if (pairs_walked) *pairs_walked = g_angular_walked;
-  if (pairs_skipped) *pairs_skipped = g_angular_skipped;
+  if (pairs_walked) *pairs_walked = smh::g_angular_walked;
+  if (pairs_skipped) *pairs_skipped = smh::g_angular_skipped;
 }
-uint64_t smh_angular_prune_min_pairs(void) { return g_angular_prune_min_pairs; }
-void smh_angular_set_prune_min_pairs(uint64_t pairs) { g_angular_prune_min_pairs = pairs ? pairs : kAngularPruneMinPairs; }
+uint64_t smh_angular_prune_min_pairs(void) { return smh::g_angular_prune_min_pairs; }
+void smh_angular_set_prune_min_pairs(uint64_t pairs) { smh::g_angular_prune_min_pairs = pairs ? pairs : smh::kAngularPruneMinPairs; }
 
 // ---- a scaled sketch's state as device arrays: the cross-rank union of partial sketches ----
 int smh_sketch_export_dev(KmerMinHash* ptr, uint64_t* mins_dev, uint64_t* abunds_dev, uint64_t capacity, uint64_t* n_out, void* stream) {
@@ -1614,16 +934,11 @@ int smh_compare_set_tuning(const SmhCompareTuning* in) {
   });
 }
 
-// test hook (host only, no device): the compare block's tile planning
 int smh_release_workspace(void) {
   return pad_code([&] {
-    {
-      // the dictionaries resident indexes cached for their all-vs-all compares (ranks, roots, the partition table: up to
-      // hundreds of MB for 10 000 long sketches); the next smh_index_compare of an index with itself rebuilds its own
-      std::lock_guard<std::recursive_mutex> lock(smh::Device::get().mutex());
-      std::lock_guard<std::mutex> g(SmhIndex::registry_mu());
-      for (SmhIndex* i : SmhIndex::registry()) i->drop_dict();
-    }
+    // the dictionaries resident indexes cached for their all-vs-all compares (ranks, roots, the partition table: up to
+    // hundreds of MB for 10 000 long sketches); the next block of an index with itself rebuilds its own
+    smh::ResidentIndex::drop_all_dictionaries();
     smh::Engine::get().release_workspace();
   });
 }

@@ -192,18 +192,6 @@ __global__ __launch_bounds__(256) void k_gather_subtract(const uint64_t* __restr
   if (lane == 0 && wsum) atomicAdd((unsigned long long*)&rows[r].abund_sum, (unsigned long long)wsum);
 }
 
-// a block of the device pool for the length of one call
-struct PoolBlock {
-  void* ptr = nullptr;
-  size_t cap = 0;
-  bool synced = false;   // the stream was waited for: nothing can still be using the block
-  explicit PoolBlock(size_t bytes) { ptr = device_pool_alloc(bytes ? bytes : 1, &cap); }
-  PoolBlock(const PoolBlock&) = delete;
-  PoolBlock& operator=(const PoolBlock&) = delete;
-  ~PoolBlock() { device_pool_free(ptr, cap, !synced); }
-  template <class T> T* as() const { return reinterpret_cast<T*>(ptr); }
-};
-
 }  // namespace
 
 uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q, uint32_t threshold, GatherRow* rows_host,

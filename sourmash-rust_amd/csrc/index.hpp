@@ -1,0 +1,87 @@
+// index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
+// similarity on abundances (angular.cpp).  The C boundary (ffi.cpp) only checks pointers and calls in here.
+#pragma once
+#include "minhash.hpp"
+
+namespace smh {
+
+struct ResidentIndex {
+  DeviceBuffer hashes, offsets, nums;
+  std::vector<uint64_t> h_offsets;
+  std::vector<uint32_t> h_nums;
+  std::vector<KmerMinHash> params;   // parameters only (mins cleared): check_compatible per node
+  uint32_t max_len = 0, n = 0;
+  // decided once for the whole set: every node has the parameters of node 0 (a sketch is then checked against that one
+  // block), and whether any node is a bottom-`num` sketch
+  bool uniform = true, any_num = false;
+  // the dictionary of the resident set (dense ranks, components, frequent hashes), built by the first all-vs-all block of
+  // the index with itself and kept: later ones skip the pre-pass (the nodes of an index never change)
+  CollectionDict* dict = nullptr;
+  uint32_t dict_split = 0;      // the frequent-hash setting the dictionary was built under
+  // angular similarity.  has_abunds: EVERY node tracks abundances and every abundance vector matches its
+  // hashes; h_abunds then holds them narrowed to u32 (a copy, like the hashes) until the first angular call uploads them
+  // and computes the norms -- an index nobody asks pays no HBM.  bad_node: the lowest node whose norm2 does not fit 64 bits.
+  bool has_abunds = false;
+  std::vector<uint32_t> h_abunds;
+  uint32_t wide_node = kAngularNoError;   // the first node holding an abundance of 2^32 or more
+  bool angular_ready = false;
+  uint32_t bad_node = kAngularNoError;
+  DeviceBuffer abunds_dev, norm2_dev;
+  std::vector<uint64_t> h_norm2;
+  explicit ResidentIndex(const std::vector<const KmerMinHash*>& nodes);   // uploads the nodes
+  ~ResidentIndex();
+  SketchSet set() const { return {hashes.as<uint64_t>(), offsets.as<uint64_t>(), n, h_offsets.data()}; }
+  AngularSet angular_set() const {   // after angular_ensure
+    return {hashes.as<uint64_t>(), abunds_dev.as<uint32_t>(), offsets.as<uint64_t>(), norm2_dev.as<uint64_t>(), n};
+  }
+  // check_compatible of every node with a sketch / with every node of another index.  A uniform index answers for all its
+  // nodes with params[0]: the error depends only on the parameters, so its code and message are those of the full loop.
+  void check_sketch(const KmerMinHash& mh, bool sketch_is_receiver = false) const;
+  void check_index(const ResidentIndex& cols) const;
+  // The one index-vs-index route: rows x cols into device memory.  An index against itself on the block route goes through
+  // its cached dictionary (built here when missing or stale), everything else through launch_compare_block.
+  static void compare_block(ResidentIndex& rows, ResidentIndex& cols, const CompareOut& dev_out, Device& dev, hipStream_t s);
+  void drop_dict() { if (dict) { collection_free(dict); dict = nullptr; } }
+  static void drop_all_dictionaries();   // of every live index (memory no other allocator can see)
+  // outputs on the host, row-major; null = not wanted
+  void compare(ResidentIndex& cols, double* jaccard, uint64_t* common, uint64_t* size, uint64_t* count_common, double* containment);
+  // the index against one host sketch (n values each); q_is_row: the sketch is the row, its num cuts the union
+  void vs_one(const KmerMinHash& q, bool q_is_row, double* jaccard, double* containment, uint64_t* count_common);
+  uint32_t find(const KmerMinHash& query, double threshold, bool containment, uint32_t* out_indices);   // returns how many
+  void most_common(const KmerMinHash& leaf, uint32_t* best_pos, uint64_t* best_common);
+  uint32_t gather(const KmerMinHash& query, uint32_t threshold_common, GatherRow* rows, uint32_t rows_capacity, uint32_t* assigned,
+                  Device& dev);
+  void angular_ensure(const char* what, hipStream_t s);   // (angular.cpp from here) the first angular call: abundances to HBM, norms
+  void norms2(uint64_t* out);
+  void angular(ResidentIndex& cols, uint64_t* dot, double* cosine, double* angular);
+  void angular_query(const KmerMinHash& query, uint64_t* dot, uint64_t* query_norm2, double* cosine, double* angular);
+};
+
+// the loops of find and most_common, shared with their host-sketch forms
+inline uint32_t indices_above(const double* val, uint32_t n, double threshold, uint32_t* out_indices) {
+  uint32_t k = 0;
+  for (uint32_t i = 0; i < n; i++)
+    if (val[i] > threshold) out_indices[k++] = i;   // NaN (empty node, containment) is never > threshold
+  return k;
+}
+inline void arg_max(const uint64_t* v, uint32_t n, uint32_t* best_pos, uint64_t* best) {   // null outputs are skipped
+  uint32_t pos = 0;
+  uint64_t mx = 0;
+  for (uint32_t j = 0; j < n; j++)
+    if (v[j] > mx) { mx = v[j]; pos = j; }
+  if (best_pos) *best_pos = pos;
+  if (best) *best = mx;
+}
+
+// angular.cpp: the calls that need no index.  rows / cols of angular_block_dev: hashes, abunds and n; offsets on the host
+void angular_similarity(const KmerMinHash& a, const KmerMinHash& b, double* angular, double* cosine, uint64_t* dot, uint64_t* norm2_a,
+                        uint64_t* norm2_b);
+void angular_block_dev(AngularSet rows, const uint64_t* row_offsets, AngularSet cols, const uint64_t* col_offsets,
+                       const uint64_t* count_common_dev, bool symmetric, const AngularOut& out, uint64_t* row_norm2_dev,
+                       uint64_t* col_norm2_dev, void* stream);
+// From g_angular_prune_min_pairs pairs on ResidentIndex::angular first runs the block compare for count_common and walks only the pairs
+// that share a hash (default: tools/bench_angular.py's sweep, DESIGN.md 3.10 "The prune threshold").  walked / skipped: of the last call.
+constexpr uint64_t kAngularPruneMinPairs = 4096;
+extern uint64_t g_angular_prune_min_pairs, g_angular_walked, g_angular_skipped;
+
+}  // namespace smh

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 
 #include "device.hpp"
 
@@ -125,6 +126,20 @@ void launch_parse_scan(int format, const uint8_t* text, uint64_t len, const Pars
 void launch_parse_compact(int format, const uint8_t* text, uint64_t len, const void* workspace, const ParseTotals& totals,
                           uint8_t* out, uint64_t* offsets_dev, uint64_t* name_start_dev, uint64_t* name_end_dev,
                           ParseTotals* totals_dev, hipStream_t s);
+// records.cpp.  The records of one text: the compacted sequence bytes and the name spans in HBM, the offsets on the host
+// (page-locked: the sketching paths walk them and upload them again).  Holds no reference to the text.
+struct Records {
+  std::unique_ptr<PoolBlock> seq, names;            // total + 64 bytes; name_start[n], name_end[n] (they wait for the device when freed)
+  uint64_t* offsets = nullptr;                      // n + 1, hipHostMalloc
+  uint32_t n = 0;
+  uint64_t total = 0;
+  int format = 0;
+  ~Records() { if (offsets) (void)hipHostFree(offsets); }
+  const uint8_t* seq_dev() const { return seq ? seq->as<uint8_t>() : nullptr; }
+  void name_spans(uint64_t* start_out, uint32_t* len_out) const;   // n entries each, read back from `names`
+};
+// fills a new *rec from a text in device memory (on the caller's `stream`) or in host memory (uploaded first, own stream)
+void parse_records(Records* rec, const void* text, bool text_on_host, uint64_t len, int format, void* stream, Device& dev);
 
 // --- sort.hip -----------------------------------------------------------------------
 // LSD radix sort, ping-pong between (k0,v0) and (k1,v1); returns which pair holds the result.
@@ -200,6 +215,25 @@ struct CompareOut {
   double* jaccard = nullptr;   // common / max(1, size)        (reference src/lib.rs:501-508)
   uint64_t* count_common = nullptr;  // |A ^ B| untruncated     (reference src/lib.rs:428-436)
   double* containment = nullptr;     // |A ^ B| / |A|           (reference src/index.rs:146-154)
+};
+// The outputs of an np-pair block for a caller that wants them on the host: five device slots of np entries carved from
+// `buf` (room for tail_bytes more behind them, at tail()); dev_out() points only at the slots whose host pointer is set --
+// without count_common / containment the kernels may stop at the cut -- and fetch() queues those slots' copies back.
+struct HostCompareOut {
+  void* host[5];   // in CompareOut's order
+  uint64_t* dev;
+  size_t np;
+  HostCompareOut(DeviceBuffer& buf, size_t np_, uint64_t* common, uint64_t* size, double* jaccard, uint64_t* count_common,
+                 double* containment, size_t tail_bytes = 0) : host{common, size, jaccard, count_common, containment}, np(np_) {
+    buf.ensure(np * 8 * 5 + tail_bytes + 64);
+    dev = buf.as<uint64_t>();
+  }
+  template <class T> T* slot(int k) const { return host[k] ? reinterpret_cast<T*>(dev + k * np) : nullptr; }
+  CompareOut dev_out() const { return {slot<uint64_t>(0), slot<uint64_t>(1), slot<double>(2), slot<uint64_t>(3), slot<double>(4)}; }
+  void* tail() const { return dev + 5 * np; }
+  void fetch(hipStream_t s) const {
+    for (int k = 0; k < 5; k++) if (host[k]) HIP_CHECK(hipMemcpyAsync(host[k], dev + k * np, np * 8, hipMemcpyDeviceToHost, s));
+  }
 };
 // rows x cols block; num = truncation length of the union walk (row's `num`; 0 = unbounded),
 // row_nums (device, nullable) overrides it per row.

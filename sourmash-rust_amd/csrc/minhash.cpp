@@ -1529,7 +1529,7 @@ void Engine::pack_sketches(const std::vector<const KmerMinHash*>& v, DeviceBuffe
   out->hashes = data.as<uint64_t>();
   out->offsets = offs.as<uint64_t>();
   out->n = (uint32_t)v.size();
-  if (h_off) h_off->swap(off);
+  if (h_off) { h_off->swap(off); out->h_offsets = h_off->data(); }
 }
 
 void Engine::compare_host(const std::vector<const KmerMinHash*>& rows, const std::vector<const KmerMinHash*>& cols,
@@ -1554,21 +1554,13 @@ void Engine::compare_host(const std::vector<const KmerMinHash*>& rows, const std
   const bool same_sets = rows.size() == cols.size() && std::equal(rows.begin(), rows.end(), cols.begin());
   std::vector<uint64_t> h_off_r, h_off_c;
   pack_sketches(rows, cmp_a, cmp_oa, &R, &mr, &h_off_r, s);
-  R.h_offsets = h_off_r.data();
   if (same_sets) { C = R; mc = mr; }
-  else { pack_sketches(cols, cmp_b, cmp_ob, &C, &mc, &h_off_c, s); C.h_offsets = h_off_c.data(); }
-  uint64_t row_total = 0, col_total = 0;
-  for (auto* m : rows) row_total += m->mins.size();
-  for (auto* m : cols) col_total += m->mins.size();
+  else pack_sketches(cols, cmp_b, cmp_ob, &C, &mc, &h_off_c, s);
+  const uint64_t row_total = R.h_offsets[R.n], col_total = C.h_offsets[C.n];
   const size_t np = rows.size() * cols.size();
   if (np == 0) return;
-  cmp_out.ensure(np * 8 * 5 + rows.size() * 4 + 64);
-  uint64_t* d_common = cmp_out.as<uint64_t>();
-  uint64_t* d_size = d_common + np;
-  double* d_jac = reinterpret_cast<double*>(d_size + np);
-  uint64_t* d_cc = reinterpret_cast<uint64_t*>(d_jac + np);
-  double* d_cont = reinterpret_cast<double*>(d_cc + np);
-  uint32_t* d_rownum = reinterpret_cast<uint32_t*>(d_cont + np);
+  const HostCompareOut out(cmp_out, np, common, size, jaccard, count_common, containment, rows.size() * 4);
+  uint32_t* d_rownum = static_cast<uint32_t*>(out.tail());
   // one num for every row: pass it as the launch-wide value
   if (row_nums_host) {
     bool uniform = true;
@@ -1577,17 +1569,30 @@ void Engine::compare_host(const std::vector<const KmerMinHash*>& rows, const std
   }
   if (row_nums_host)
     HIP_CHECK(hipMemcpyAsync(d_rownum, row_nums_host, rows.size() * 4, hipMemcpyHostToDevice, s));
-  CompareOut o;
-  // only what the caller asked for: without count_common / containment the kernels may stop at the cut
-  o.common = common ? d_common : nullptr; o.size = size ? d_size : nullptr; o.jaccard = jaccard ? d_jac : nullptr;
-  o.count_common = count_common ? d_cc : nullptr; o.containment = containment ? d_cont : nullptr;
-  launch_compare_block(R, C, num, row_nums_host ? d_rownum : nullptr, o, dev, s, mr, mc, row_total, col_total, same_sets);
-  if (common) HIP_CHECK(hipMemcpyAsync(common, d_common, np * 8, hipMemcpyDeviceToHost, s));
-  if (size) HIP_CHECK(hipMemcpyAsync(size, d_size, np * 8, hipMemcpyDeviceToHost, s));
-  if (jaccard) HIP_CHECK(hipMemcpyAsync(jaccard, d_jac, np * 8, hipMemcpyDeviceToHost, s));
-  if (count_common) HIP_CHECK(hipMemcpyAsync(count_common, d_cc, np * 8, hipMemcpyDeviceToHost, s));
-  if (containment) HIP_CHECK(hipMemcpyAsync(containment, d_cont, np * 8, hipMemcpyDeviceToHost, s));
+  launch_compare_block(R, C, num, row_nums_host ? d_rownum : nullptr, out.dev_out(), dev, s, mr, mc, row_total, col_total, same_sets);
+  out.fetch(s);
   HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void Engine::compare_block_dev(const uint64_t* row_hashes_dev, const uint64_t* row_offsets, uint32_t n_rows,
+                               const uint64_t* col_hashes_dev, const uint64_t* col_offsets, uint32_t n_cols, uint32_t num,
+                               const CompareOut& o, void* stream) {
+  Device& dev = Device::get();
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  hipStream_t s = dev.user_stream(stream);
+  uint32_t mr = 0, mc = 0;
+  for (uint32_t i = 0; i < n_rows; i++) mr = std::max<uint32_t>(mr, (uint32_t)(row_offsets[i + 1] - row_offsets[i]));
+  for (uint32_t j = 0; j < n_cols; j++) mc = std::max<uint32_t>(mc, (uint32_t)(col_offsets[j + 1] - col_offsets[j]));
+  cmp_oa.ensure((size_t)(n_rows + 1) * 8);
+  cmp_ob.ensure((size_t)(n_cols + 1) * 8);
+  HIP_CHECK(hipMemcpyAsync(cmp_oa.ptr, row_offsets, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(cmp_ob.ptr, col_offsets, (size_t)(n_cols + 1) * 8, hipMemcpyHostToDevice, s));
+  const SketchSet R{row_hashes_dev, cmp_oa.as<uint64_t>(), n_rows, row_offsets}, C{col_hashes_dev, cmp_ob.as<uint64_t>(), n_cols, col_offsets};
+  const bool same_sets = row_hashes_dev == col_hashes_dev && n_rows == n_cols &&
+                         std::memcmp(row_offsets, col_offsets, (size_t)(n_rows + 1) * 8) == 0;
+  launch_compare_block(R, C, num, nullptr, o, dev, s, mr, mc, row_offsets[n_rows] - row_offsets[0],
+                       col_offsets[n_cols] - col_offsets[0], same_sets);
+  HIP_CHECK(hipStreamSynchronize(s));  // the offset staging buffers are reused by the next call
 }
 
 // The sketch's hashes in device memory.  A sketch whose state lives in HBM is compared where it is (nothing is brought to

@@ -189,6 +189,9 @@ class Engine {
   void compare_host(const std::vector<const KmerMinHash*>& rows, const std::vector<const KmerMinHash*>& cols,
                     const uint32_t* row_nums_host, uint32_t num, uint64_t* common, uint64_t* size,
                     double* jaccard, uint64_t* count_common, double* containment);
+  // the same for CSR sets already in device memory (offsets on the host), outputs in device memory too
+  void compare_block_dev(const uint64_t* row_hashes_dev, const uint64_t* row_offsets, uint32_t n_rows, const uint64_t* col_hashes_dev,
+                         const uint64_t* col_offsets, uint32_t n_cols, uint32_t num, const CompareOut& out, void* stream);
 
   // frees every grow-only workspace buffer (they are re-created on demand)
   void release_workspace();

@@ -384,3 +384,41 @@ def test_pool_bytes_return(pkg, fx):
         matrix(fx.index, fx.other)
         fx.index.angular(fx.nodes[1])
         assert L.smh_pool_bytes() == before
+
+
+def test_angular_prune_and_compare_share_one_dictionary(pkg, coracle):
+    """The prune pass of an index against itself and smh_index_compare go through one route and one cached dictionary:
+    "index_dictionary_built" counts the builds.  72 scaled sketches in 6 families of 12: members share most of their ~50
+    hashes, families share none (pairs for the prune to skip); 72 x 72 pairs take the prune and, with 72 rows, the block route."""
+    rng = np.random.default_rng(72)
+    pools = [sorted({int(x) + (f << 44) for x in rng.integers(1, 1 << 40, 80, dtype=np.uint64)})[:60] for f in range(6)]
+    assert all(len(p) == 60 for p in pools)
+    S = [subset(rng, pools[i // 12], 50) for i in range(72)]
+    assert 72 * 72 >= pkg.lib().smh_angular_prune_min_pairs()
+    idx = pkg.index.ResidentIndex([mk(pkg, s) for s in S])
+    exp = AR.block(S, S, symmetric=True)
+    hashes = [np.array(sorted(s), dtype=np.uint64) for s in S]
+    o_common, o_size, o_jac = coracle.compare_matrix(hashes, hashes, 0, 21, M64)
+    assert int((o_common == 0).sum()) == 72 * 72 - 6 * 12 * 12
+
+    def angular(delta, what):
+        before = count(pkg, "index_dictionary_built")
+        same(*matrix(idx), exp, what)
+        assert pkg.matrix.angular_last_stats()[1] > 0, what
+        assert count(pkg, "index_dictionary_built") - before == delta, what
+
+    def compare(delta, what):
+        before = count(pkg, "index_dictionary_built")
+        out = idx.compare(idx, want=("jaccard", "common", "size", "count_common"))
+        assert np.array_equal(out["common"], o_common) and np.array_equal(out["size"], o_size), what
+        assert np.array_equal(out["jaccard"].view(np.uint64), o_jac.view(np.uint64)), what
+        assert np.array_equal(out["count_common"], o_common), what            # num = 0: nothing cuts the union
+        assert count(pkg, "index_dictionary_built") - before == delta, what
+
+    angular(1, "the prune builds the dictionary")
+    compare(0, "compare finds it")
+    with pkg.matrix.tuning(split_frequent=False):          # (restores the default tuning in a finally)
+        angular(1, "built under another split_frequent: stale")
+        compare(0, "compare finds the rebuilt one")
+        idx.drop_dictionary()
+        compare(1, "dropped: compare builds it")
