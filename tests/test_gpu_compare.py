@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 # smh_compare_set_tuning; the choice must never change a result): the shape-based default, the
 # per-component pair kernel, the tiled matrix kernel over the tiles that can hold sharing pairs, and
 # the tiled kernel over EVERY tile.  `expect` = the route smh_compare_last_stats must report.
-ROUTES = [
+BLOCK_ROUTES = [
     pytest.param(dict(), None, id="auto"),
     pytest.param(dict(route="components"), "components", id="components"),
     pytest.param(dict(route="tiled"), "tiled", id="tiled"),
@@ -29,6 +29,13 @@ ROUTES = [
     # the tiled kernel walking every pair from the first range on, instead of from where the range masks say its cut lies
     pytest.param(dict(route="tiled", range_masks=False), "tiled", id="tiled-no-range-masks"),
     pytest.param(dict(route="tiled", visit_all_tiles=True, range_masks=False), "tiled", id="tiled-all-tiles-no-range-masks"),
+]
+# ... and the two routes of small blocks at any size: one wavefront per pair, and the side with fewer sketches held in LDS
+# while the other streams (test_gpu_compare_small_routes.py goes through their branches).  Tests that assert statistics
+# only the block routes produce keep BLOCK_ROUTES.
+ROUTES = BLOCK_ROUTES + [
+    pytest.param(dict(route="wave"), "wave", id="wave"),
+    pytest.param(dict(route="few"), "few", id="few"),
 ]
 
 
@@ -824,7 +831,7 @@ def test_pairwise_calls_see_every_mutation(pkg, coracle):
         assert gc.compare(ga) == oc.compare(oa)
 
 
-@pytest.mark.parametrize("tune,expect", ROUTES)
+@pytest.mark.parametrize("tune,expect", BLOCK_ROUTES)          # (asserts the frequent hashes the dictionary set aside)
 def test_row_block_that_is_a_slice_of_the_columns(tune, expect, pkg, coracle):
     """One rank's row block passed as a VIEW of the gathered signature set: the tiled pre-pass encodes
     the columns only and takes the rows' ranks from the same array."""
