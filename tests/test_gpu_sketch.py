@@ -256,11 +256,15 @@ def _profile(pkg, name):
 @pytest.mark.parametrize("ksize", [21, 27, 28, 29, 30, 32])
 def test_protein_fused_kernel(ksize, pkg, coracle):
     """The one-pass protein kernel (translation + hashing, no residue buffer; window lengths 7, 9, 10)
-    against the oracle on what it has to get right by itself: many records per launch with lengths
-    around ksize and around the tile geometry, lower case, runs of N that splice residues together
-    (quirk Q8), N at record ends, every sketch mode with abundance (positions = the reference's frame
-    order, quirk Q3), and bytes >= 0x80, for which the launch is discarded and repeated on the
-    two-pass path."""
+    against the oracle on seeded random records: many records per launch with lengths around ksize
+    and around 128 and 65536, lower case, runs of N that splice residues together (quirk Q8), N at
+    record ends, every sketch mode with abundance (positions = the reference's frame order, quirk
+    Q3), and bytes >= 0x80, for which the launch is discarded and repeated on the two-pass path.
+    Every input here is far below cu_count * 1024 * 64 bases, so the kernel walks runs of 32 window
+    starts only (tiles of 16384 bases), and where the random N's and record ends fall within a run
+    is left to chance.  The run edges, at runs of 32, 64 and 128, are placed deliberately in
+    tests/test_gpu_protein_fused_edges.py; the fall-backs and the two-pass path in
+    tests/test_gpu_protein_routes.py."""
     rng = random.Random(ksize)
     L = pkg.lib()
 
