@@ -93,6 +93,41 @@ int smh_add_records(KmerMinHash *ptr, const SmhRecords *r, bool force);
 int smh_add_records_grouped(KmerMinHash *const *sketches, uint32_t n_sketches, const SmhRecords *r, const uint32_t *groups,
                             bool force);
 
+/* Alphabets and amino-acid input.  The reference revision sketches protein only out of translated DNA
+ * and in the 20-letter alphabet only; this library fixes the rest:
+ *   Molecule   a sketch has one of DNA, protein, dayhoff, hp.  kmerminhash_new(prot = false / true) gives DNA / protein;
+ *              kmerminhash_is_protein is true for the last three.  ksize stays in nucleotides: the window is
+ *              W = ksize / 3 residues (dayhoff k = 9 is ksize 27).  Sketches of different molecules are incompatible
+ *              (code 102) wherever check_compatible applies; the signature JSON's "molecule" is "DNA", "protein",
+ *              "dayhoff" or "hp", the last two are read back as such (any other string still reads as DNA), and the
+ *              moltype filter of the load calls matches them case-insensitively.
+ *   Maps       applied to the upper-cased byte (a-z become A-Z, nothing else changes).
+ *              protein  every byte is itself
+ *              dayhoff  C -> a;  A G P S T -> b;  D E N Q -> c;  H K R -> d;  I L M V -> e;  F W Y -> f;  * -> *;
+ *                       every other byte -> X
+ *              hp       A F G I L M P V W Y -> h;  N C S T D E R H K Q -> p;  * -> *;  every other byte -> X
+ *   Amino-acid input (smh_add_protein*)   for each record in order, for each start i with i + W <= len ascending:
+ *              add_hash(murmur64(map(record[i .. i + W)), seed)).  No strand, no translation, no validity check, no
+ *              `force`: content never raises an error, and NUL, 0xFF and bytes >= 0x80 are residues like any other.  A
+ *              record shorter than W adds nothing; W == 0 raises add_sequence's panic; a DNA sketch is refused with code 3
+ *              before the device is touched.  Calls take effect in call order with add_sequence / add_word / add_hash
+ *              on the same sketch.  Without a usable device: code 2 and the sketch is unchanged.
+ *   Translated input   add_sequence and its batch / device / grouped / records forms on a dayhoff or hp sketch behave
+ *              exactly as on a protein sketch (six frames in the reference's order, unknown codons dropped, the UTF-8
+ *              panic, `force` ignored); each residue is mapped before hashing ('*' stays '*').
+ * smh_add_proteins* follow smh_add_sequences*: offsets has n_records + 1 host entries, seq_dev may have any alignment.
+ * smh_add_records_protein feeds a parsed protein FASTA (the parser passes sequence bytes on untouched).
+ * smh_amino_geometry: window starts per workgroup tile and per lane of the hashing launch for that input (tests, tools). */
+enum { SMH_MOLECULE_DNA = 0, SMH_MOLECULE_PROTEIN = 1, SMH_MOLECULE_DAYHOFF = 2, SMH_MOLECULE_HP = 3 };
+KmerMinHash *smh_kmerminhash_new_molecule(uint32_t n, uint32_t k, int molecule, uint64_t seed, uint64_t mx, bool track_abundance);
+int smh_kmerminhash_molecule(const KmerMinHash *ptr);
+int smh_add_protein(KmerMinHash *ptr, const char *seq, uint64_t len);
+int smh_add_proteins(KmerMinHash *ptr, const char *seq, const uint64_t *offsets, uint32_t n_records);
+int smh_add_proteins_dev(KmerMinHash *ptr, const void *seq_dev, uint64_t total_len, const uint64_t *offsets, uint32_t n_records,
+                         void *stream);
+int smh_add_records_protein(KmerMinHash *ptr, const SmhRecords *r);
+void smh_amino_geometry(uint64_t total_len, uint32_t win, uint32_t *tile_positions, uint32_t *run);
+
 /* add_hash over an array (reference src/lib.rs:412-417 add_many) */
 int smh_add_many(KmerMinHash *ptr, const uint64_t *hashes, uint64_t n);
 

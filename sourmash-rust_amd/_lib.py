@@ -112,6 +112,13 @@ _SIGS = {
     "smh_records_offsets": (u64p, [C.c_void_p]),
     "smh_records_names": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_uint32)]),
     "smh_records_tile_bytes": (C.c_uint32, []),
+    "smh_kmerminhash_new_molecule": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_bool]),
+    "smh_kmerminhash_molecule": (C.c_int, [C.c_void_p]),
+    "smh_add_protein": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "smh_add_proteins": (C.c_int, [C.c_void_p, C.c_char_p, u64p, C.c_uint32]),
+    "smh_add_proteins_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint32, C.c_void_p]),
+    "smh_add_records_protein": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "smh_amino_geometry": (None, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smh_add_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_bool]),
     "smh_add_records_grouped": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_bool]),
     "smh_add_many": (C.c_int, [C.c_void_p, u64p, C.c_uint64]),

@@ -134,6 +134,14 @@ KmerMinHash* kmerminhash_new(uint32_t n, uint32_t k, bool prot, uint64_t seed, u
 
 void kmerminhash_free(KmerMinHash* ptr) { delete ptr; }
 
+KmerMinHash* smh_kmerminhash_new_molecule(uint32_t n, uint32_t k, int molecule, uint64_t seed, uint64_t mx, bool track_abundance) {
+  return pad<KmerMinHash*>([&] {
+    if (molecule < SMH_MOLECULE_DNA || molecule > SMH_MOLECULE_HP) throw Error(smh::kMsg, "unknown molecule");
+    return new KmerMinHash(n, k, (smh::Molecule)molecule, seed, mx, track_abundance);
+  });
+}
+int smh_kmerminhash_molecule(const KmerMinHash* ptr) { return pad<int>([&] { require(ptr, "ptr"); return (int)ptr->molecule; }); }
+
 void kmerminhash_add_sequence(KmerMinHash* ptr, const char* sequence, bool force) {
   pad_void([&] {
     require(ptr, "ptr");
@@ -427,6 +435,47 @@ int smh_add_sequences_dev(KmerMinHash* ptr, const void* seq_dev, uint64_t total_
   });
 }
 
+// ------------------------------------------------------------------ amino-acid input
+
+int smh_add_protein(KmerMinHash* ptr, const char* seq, uint64_t len) {
+  return pad_code([&] {
+    require(ptr, "ptr");
+    ptr->check_amino_input();
+    if (len) require(seq, "seq");
+    const uint64_t off[2] = {0, len};
+    ptr->add_proteins_host((const uint8_t*)seq, len, off, 1);
+  });
+}
+
+int smh_add_proteins(KmerMinHash* ptr, const char* seq, const uint64_t* offsets, uint32_t n_records) {
+  return pad_code([&] {
+    require(ptr, "ptr");
+    ptr->check_amino_input();
+    require(offsets, "offsets");
+    if (n_records == 0) { (void)smh::Device::get(); return; }
+    const uint64_t base = offsets[0], total = offsets[n_records] - base;
+    if (total) require(seq, "seq");
+    std::vector<uint64_t> rel(n_records + 1);
+    for (uint32_t i = 0; i <= n_records; i++) rel[i] = offsets[i] - base;
+    ptr->add_proteins_host((const uint8_t*)seq + base, total, rel.data(), n_records);
+  });
+}
+
+int smh_add_proteins_dev(KmerMinHash* ptr, const void* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n_records,
+                         void* stream) {
+  return pad_code([&] {
+    require(ptr, "ptr");
+    ptr->check_amino_input();
+    require(offsets, "offsets");
+    if (total_len) require(seq_dev, "seq_dev");
+    ptr->add_proteins_device((const uint8_t*)seq_dev, total_len, offsets, n_records, smh::Device::get().user_stream(stream));
+  });
+}
+
+void smh_amino_geometry(uint64_t total_len, uint32_t win, uint32_t* tile_positions, uint32_t* run) {
+  smh::amino_geometry(total_len, win, tile_positions, run);
+}
+
 int smh_add_sequences_grouped(KmerMinHash* const* sketches, uint32_t n_sketches, const char* seq, const uint64_t* offsets,
                               const uint32_t* groups, uint32_t n_records, bool force) {
   return pad_code([&] {
@@ -499,6 +548,15 @@ int smh_add_records(KmerMinHash* ptr, const SmhRecords* r, bool force) {
     require(ptr, "ptr"); require(r, "r");
     ptr->add_sequences_device(r->seq_dev(), r->total, r->offsets, r->n, force,
                               smh::Device::get().user_stream(nullptr), nullptr);
+  });
+}
+
+int smh_add_records_protein(KmerMinHash* ptr, const SmhRecords* r) {
+  return pad_code([&] {
+    require(ptr, "ptr");
+    ptr->check_amino_input();
+    require(r, "r");
+    ptr->add_proteins_device(r->seq_dev(), r->total, r->offsets, r->n, smh::Device::get().user_stream(nullptr));
   });
 }
 

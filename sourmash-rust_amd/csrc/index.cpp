@@ -18,10 +18,10 @@ ResidentIndex::ResidentIndex(const std::vector<const KmerMinHash*>& v) {
   h_nums.resize(n);
   for (uint32_t i = 0; i < n; i++) {
     h_nums[i] = v[i]->num;
-    KmerMinHash p(v[i]->num, v[i]->ksize, v[i]->is_protein, v[i]->seed, v[i]->max_hash, false);
+    KmerMinHash p(v[i]->num, v[i]->ksize, (Molecule)v[i]->molecule, v[i]->seed, v[i]->max_hash, false);
     params.push_back(p);
     const KmerMinHash& p0 = params[0];
-    uniform &= p.ksize == p0.ksize && p.is_protein == p0.is_protein && p.max_hash == p0.max_hash && p.seed == p0.seed;
+    uniform &= p.ksize == p0.ksize && p.molecule == p0.molecule && p.max_hash == p0.max_hash && p.seed == p0.seed;
     any_num |= p.num != 0;
   }
   {

@@ -43,6 +43,7 @@ struct TileRec {
 
 struct HashParams {
   uint32_t ksize = 31;
+  uint32_t alphabet = 0;              // protein arm and amino-acid input: the sketch's Molecule (0 / 1: residues as they are)
   uint64_t seed = 42;
   const uint64_t* thr_rec = nullptr;  // DNA arm: per-record thresholds (device, nrec entries) or null
   uint64_t thr = ~0ull;               // the threshold when thr_rec is null (and the LDS stage estimate)
@@ -77,7 +78,7 @@ void launch_hash_windows(const uint8_t* bytes, uint64_t total, const uint64_t* s
 // entries, nseg = 6*nrec) gives where each (record, frame, strand) segment lives in `residues`;
 // unknown codons are written as 0xFF and skipped by launch_hash_windows; bad_utf8[seg] is set when
 // a codon chunk is not valid UTF-8 (the reference panics there).
-void launch_translate(const SeqBatch& b, const uint64_t* seg_offsets, uint32_t nseg, uint64_t total, uint32_t ksize,
+void launch_translate(const SeqBatch& b, const uint64_t* seg_offsets, uint32_t nseg, uint64_t total, uint32_t ksize, uint32_t alphabet,
                       uint8_t* residues, uint32_t* bad_utf8, hipStream_t s);
 
 // Protein arm in ONE pass over the DNA (translation + hashing, no residue buffer): every window of
@@ -89,6 +90,13 @@ void launch_translate(const SeqBatch& b, const uint64_t* seg_offsets, uint32_t n
 // Returns false (nothing launched) for window lengths it has no instantiation for.
 bool launch_protein_fused(const SeqBatch& b, const uint64_t* seg_offsets, uint32_t win, const HashParams& p,
                           const CandSink& sink, uint32_t* high_flag, Device& dev, hipStream_t s);
+
+// Amino-acid input: every window of `win` bytes that lies inside one record and starts in [p.range_lo, p.range_hi), each
+// byte upper-cased and mapped through p.alphabet; a candidate's position is p.pos_base + the byte offset of its window
+// start.  win <= 64: k_amino_tiled (profile name amino_tiled), else k_amino_generic (amino_generic).  b.vends is not used.
+void launch_amino_hash(const SeqBatch& b, uint32_t win, const HashParams& p, const CandSink& sink, Device& dev, hipStream_t s);
+// window starts per workgroup tile and per lane of such a launch (one geometry; 256 / 1 for the generic kernel)
+void amino_geometry(uint64_t total_len, uint32_t win, uint32_t* tile_positions, uint32_t* run);
 
 // hashes[lo..hi) that are <= thr go to the sink with their index as stream position
 // (bulk add_many, reference src/lib.rs:412-417)

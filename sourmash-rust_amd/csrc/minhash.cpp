@@ -20,13 +20,20 @@ namespace smh {
 // scalar host methods
 
 KmerMinHash::KmerMinHash(uint32_t n, uint32_t k, bool prot, uint64_t seed_, uint64_t mx, bool track)
-    : num(n), ksize(k), is_protein(prot), seed(seed_), max_hash(mx), has_abunds(track) {
+    : KmerMinHash(n, k, prot ? kMoleculeProtein : kMoleculeDNA, seed_, mx, track) {}
+
+KmerMinHash::KmerMinHash(uint32_t n, uint32_t k, Molecule mol, uint64_t seed_, uint64_t mx, bool track)
+    : num(n), ksize(k), is_protein(mol != kMoleculeDNA), molecule(mol), seed(seed_), max_hash(mx), has_abunds(track) {
   mins.w().reserve(n > 0 ? n : 1000);
   if (track) abunds.reserve(mins.capacity());
 }
 
+const char* molecule_name(uint8_t m) {
+  return m == kMoleculeProtein ? "protein" : m == kMoleculeDayhoff ? "dayhoff" : m == kMoleculeHp ? "hp" : "DNA";
+}
+
 KmerMinHash::KmerMinHash(const KmerMinHash& o)
-    : num(o.num), ksize(o.ksize), is_protein(o.is_protein), seed(o.seed), max_hash(o.max_hash),
+    : num(o.num), ksize(o.ksize), is_protein(o.is_protein), molecule(o.molecule), seed(o.seed), max_hash(o.max_hash),
       has_abunds(o.has_abunds) {
   o.materialize();   // also drains o's queued sequences
   mins = o.mins;
@@ -37,7 +44,7 @@ KmerMinHash& KmerMinHash::operator=(const KmerMinHash& o) {
   if (this == &o) return *this;
   o.materialize();
   pend_seq.clear(); pend_off.clear(); pend_words.clear(); pend_woff.clear();
-  num = o.num; ksize = o.ksize; is_protein = o.is_protein; seed = o.seed; max_hash = o.max_hash;
+  num = o.num; ksize = o.ksize; is_protein = o.is_protein; molecule = o.molecule; seed = o.seed; max_hash = o.max_hash;
   has_abunds = o.has_abunds; mins = o.mins; abunds = o.abunds; dev.reset(); mirror.reset();
   return *this;
 }
@@ -115,7 +122,7 @@ void KmerMinHash::materialize() const {
 
 void KmerMinHash::check_compatible(const KmerMinHash& o) const {
   if (ksize != o.ksize) throw_mismatch(kMismatchKSizes);
-  if (is_protein != o.is_protein) throw_mismatch(kMismatchDNAProt);
+  if (molecule != o.molecule) throw_mismatch(kMismatchDNAProt);
   if (max_hash != o.max_hash) throw_mismatch(kMismatchMaxHash);
   if (seed != o.seed) throw_mismatch(kMismatchSeed);
 }
@@ -289,6 +296,7 @@ struct ProteinSource : HashSource {
   void ensure_segments(hipStream_t s);
   uint64_t total = 0;
   uint32_t win = 0, ksize = 0;
+  uint32_t alphabet = 0;               // the sketch's Molecule: every codon look-up of the three kernels goes through it
   uint64_t seed = 0;
   Device* dev = nullptr;
   Engine* eng = nullptr;
@@ -301,7 +309,7 @@ struct ProteinSource : HashSource {
   const uint32_t* launch_optimistic(uint64_t lo, uint64_t hi, uint64_t thr, const CandSink& sink, hipStream_t s) override {
     if (translated || lo != 0 || hi != total || sink.pos) { launch(lo, hi, thr, sink, s); return nullptr; }
     HashParams p;
-    p.seed = seed; p.thr = thr; p.ksize = ksize;
+    p.seed = seed; p.thr = thr; p.ksize = ksize; p.alphabet = alphabet;
     p.range_lo = 0; p.range_hi = ~0ull;
     eng->badbuf.ensure(8);
     uint32_t* flag = eng->badbuf.as<uint32_t>();
@@ -317,7 +325,7 @@ struct ProteinSource : HashSource {
   }
   void launch(uint64_t lo, uint64_t hi, uint64_t thr, const CandSink& sink, hipStream_t s) override {
     HashParams p;
-    p.seed = seed; p.thr = thr; p.ksize = ksize;
+    p.seed = seed; p.thr = thr; p.ksize = ksize; p.alphabet = alphabet;
     if (!translated && lo == 0 && hi == total) {
       p.range_lo = 0; p.range_hi = ~0ull;
       eng->badbuf.ensure(8);
@@ -343,6 +351,20 @@ struct ProteinSource : HashSource {
     dev->prof_begin(s);
     launch_hash_windows(eng->resbuf.as<uint8_t>(), total, seg_off, nseg, win, p, sink, s);
     dev->prof_end("hash_windows", s);
+  }
+};
+
+// Amino-acid records: the position space is the batch's bytes, a candidate's position the byte offset of its window start.
+struct AminoSource : HashSource {
+  SeqBatch b;
+  uint32_t win = 0, alphabet = 0;
+  uint64_t seed = 0;
+  Device* dev = nullptr;
+  uint64_t positions() const override { return b.len; }
+  void launch(uint64_t lo, uint64_t hi, uint64_t thr, const CandSink& sink, hipStream_t s) override {
+    HashParams p;
+    p.seed = seed; p.thr = thr; p.ksize = 3 * win; p.alphabet = alphabet; p.range_lo = lo; p.range_hi = hi;
+    launch_amino_hash(b, win, p, sink, *dev, s);
   }
 };
 
@@ -867,7 +889,7 @@ void dna_validate(SeqBatch& b, const uint8_t* d_seq, const uint64_t* h_offsets, 
 }
 // Protein arm set-up (reference src/lib.rs:277-301): the segment table (6 frames per record) of the
 // six-frame layout that defines the arm's position space.  Returns false when there is nothing to hash.
-bool prepare_protein(const SeqBatch& b, const uint64_t* h_offsets, uint32_t nrec, uint32_t ksize, uint64_t seed, Engine& E,
+bool prepare_protein(const SeqBatch& b, const uint64_t* h_offsets, uint32_t nrec, uint32_t ksize, uint32_t alphabet, uint64_t seed, Engine& E,
                      Device& dev, hipStream_t s, ProteinSource* src, bool* have_error, Error* err,
                      const uint64_t* known_total = nullptr) {
   (void)s;
@@ -889,7 +911,7 @@ bool prepare_protein(const SeqBatch& b, const uint64_t* h_offsets, uint32_t nrec
   src->b = b;
   if (nrec == 1) src->b.vend0 = (h_offsets[1] - h_offsets[0]) >= ksize ? b.len : 0;
   src->seg.clear(); src->seg_off = nullptr; src->h_offsets = h_offsets; src->nseg = 6 * nrec;
-  src->total = total; src->win = aa_k; src->ksize = ksize; src->seed = seed; src->dev = &dev; src->eng = &E;
+  src->total = total; src->win = aa_k; src->ksize = ksize; src->alphabet = alphabet; src->seed = seed; src->dev = &dev; src->eng = &E;
   src->have_error = have_error; src->err = err; src->translated = false;
   return true;
 }
@@ -924,7 +946,7 @@ void ProteinSource::translate(hipStream_t s) {
   SeqBatch tb = b;
   tb.vend0 = b.len;
   dev->prof_begin(s);
-  launch_translate(tb, seg_off, nseg, total, ksize, E.resbuf.as<uint8_t>(), E.badbuf.as<uint32_t>(), s);
+  launch_translate(tb, seg_off, nseg, total, ksize, alphabet, E.resbuf.as<uint8_t>(), E.badbuf.as<uint32_t>(), s);
   dev->prof_end("translate", s);
   std::vector<uint32_t> bad(nseg);
   HIP_CHECK(hipMemcpyAsync(bad.data(), E.badbuf.ptr, (size_t)nseg * 4, hipMemcpyDeviceToHost, s));
@@ -1000,7 +1022,7 @@ void KmerMinHash::add_sequences_device(const uint8_t* d_seq, uint64_t total_len,
     ingest(*this, src, s);
   } else {
     ProteinSource src;
-    if (!prepare_protein(b, h_offsets, nrec, ksize, seed, E, dev, s, &src, &have_error, &err, &protein_total)) return;
+    if (!prepare_protein(b, h_offsets, nrec, ksize, molecule, seed, E, dev, s, &src, &have_error, &err, &protein_total)) return;
     ingest(*this, src, s);
   }
 
@@ -1008,6 +1030,50 @@ void KmerMinHash::add_sequences_device(const uint8_t* d_seq, uint64_t total_len,
     if (first_error) *first_error = err;
     else throw err;
   }
+}
+
+// ------------------------------------------------------------------------------------
+// amino-acid input (include/sourmash_amd.h "amino-acid input")
+
+void KmerMinHash::check_amino_input() const {
+  if (molecule == kMoleculeDNA) throw Error(kMsg, "amino-acid input needs a protein, dayhoff or hp sketch");
+  if (ksize / 3 == 0) throw_panic("window size must be non-zero");   // as add_sequence on a protein sketch
+}
+
+void KmerMinHash::add_proteins_device(const uint8_t* d_seq, uint64_t total_len, const uint64_t* h_offsets, uint32_t nrec,
+                                      hipStream_t stream) {
+  check_amino_input();
+  Device& dev = Device::get();
+  if (nrec == 0 || total_len == 0) return;
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  Engine& E = Engine::get();
+  hipStream_t s = stream ? stream : dev.stream();
+  if (pend_woff.size() > 1) flush_words();
+  flush_pending();
+  if (!(num == 0 && max_hash > 0)) materialize();
+  AminoSource src;
+  src.b.seq = d_seq; src.b.len = total_len; src.b.nrec = nrec; src.b.vend0 = total_len;
+  if (nrec > 1) {
+    E.offbuf.ensure((size_t)(nrec + 1) * 8);
+    HIP_CHECK(hipMemcpyAsync(E.offbuf.ptr, h_offsets, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, s));
+    src.b.starts = E.offbuf.as<uint64_t>();
+  }
+  src.win = ksize / 3; src.alphabet = molecule; src.seed = seed; src.dev = &dev;
+  ingest(*this, src, s);
+}
+
+void KmerMinHash::add_proteins_host(const uint8_t* h_seq, uint64_t total, const uint64_t* h_offsets, uint32_t nrec) {
+  check_amino_input();
+  Device& dev = Device::get();
+  if (nrec == 0 || total == 0) return;
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  Engine& E = Engine::get();
+  hipStream_t s = dev.stream();
+  if (pend_woff.size() > 1) flush_words();
+  flush_pending();                  // (the queue's own flush uploads through seqbuf too: drain it before the buffer is reused)
+  E.seqbuf.ensure(total + 64);
+  HIP_CHECK(hipMemcpyAsync(E.seqbuf.ptr, h_seq, total, hipMemcpyHostToDevice, s));
+  add_proteins_device(E.seqbuf.as<uint8_t>(), total, h_offsets, nrec, s);
 }
 
 void KmerMinHash::add_sequences_host(const uint8_t* h_seq, uint64_t total, const uint64_t* h_offsets, uint32_t nrec,
@@ -1140,7 +1206,7 @@ void add_sequences_grouped(KmerMinHash* const* mhs, uint32_t n_mh, const uint8_t
     for (uint32_t g = 0; g < n_mh && same; g++) {
       mhs[g]->materialize();
       const KmerMinHash& m = *mhs[g];
-      same = m.is_protein == m0.is_protein && m.ksize == m0.ksize && m.seed == m0.seed;
+      same = m.molecule == m0.molecule && m.ksize == m0.ksize && m.seed == m0.seed;
       const int mode = mode_of(m);
       all_scaled &= mode == kScaled && m.max_hash == m0.max_hash;
       all_num &= mode == kNum;
@@ -1183,7 +1249,7 @@ void add_sequences_grouped(KmerMinHash* const* mhs, uint32_t n_mh, const uint8_t
     if (!force) dna_validate(b, d_seq, h_offsets, nrec, ksize, E, s, &have_error, &err);
     dna.b = b; dna.ksize = ksize; dna.seed = m0.seed; dna.dev = &dev;
   } else {
-    if (!prepare_protein(b, h_offsets, nrec, ksize, m0.seed, E, dev, s, &prot, &have_error, &err)) return;
+    if (!prepare_protein(b, h_offsets, nrec, ksize, m0.molecule, m0.seed, E, dev, s, &prot, &have_error, &err)) return;
     srcp = &prot;
     std::vector<uint32_t> g6((size_t)nrec * 6);
     for (uint32_t r = 0; r < nrec; r++) for (int f = 0; f < 6; f++) g6[(size_t)6 * r + f] = grp[r];

@@ -83,10 +83,16 @@ struct DeviceMirror {
   ~DeviceMirror();
 };
 
+// The alphabet of a sketch.  DNA / protein are the reference's two; dayhoff and hp hash every residue through a reduced
+// alphabet (kernels.hpp aa_map_host).  Sketches of different molecules are incompatible (102).
+enum Molecule : uint8_t { kMoleculeDNA = 0, kMoleculeProtein = 1, kMoleculeDayhoff = 2, kMoleculeHp = 3 };
+const char* molecule_name(uint8_t m);                 // "DNA" / "protein" / "dayhoff" / "hp" (signature JSON)
+
 struct KmerMinHash {
   uint32_t num = 1000;
   uint32_t ksize = 21;
-  bool is_protein = false;
+  bool is_protein = false;          // molecule != kMoleculeDNA (the reference's flag)
+  uint8_t molecule = 0;             // Molecule: which alphabet the residues are hashed in (include/sourmash_amd.h)
   uint64_t seed = 42;
   uint64_t max_hash = 0;
   mutable TrackedMins mins;
@@ -109,6 +115,7 @@ struct KmerMinHash {
 
   KmerMinHash() { mins.w().reserve(1000); }  // Default, src/lib.rs:48-60
   KmerMinHash(uint32_t n, uint32_t k, bool prot, uint64_t seed_, uint64_t mx, bool track);  // 142-174
+  KmerMinHash(uint32_t n, uint32_t k, Molecule mol, uint64_t seed_, uint64_t mx, bool track);
   KmerMinHash(const KmerMinHash& o);             // Clone: brings a device-resident state to the host first
   KmerMinHash& operator=(const KmerMinHash& o);
   void materialize() const;                      // device-resident state -> mins / abunds
@@ -140,6 +147,11 @@ struct KmerMinHash {
   // above; large scaled-DNA batches with force=true are uploaded in chunks on a second stream while
   // the chunks already there are being hashed.
   void add_sequences_host(const uint8_t* h_seq, uint64_t total_len, const uint64_t* h_offsets, uint32_t nrec, bool force);
+  // Amino-acid records (additive C ABI smh_add_protein*): every window of ksize / 3 bytes of every record, each byte
+  // through the sketch's alphabet -- no strand, no translation, no validity check.  Refused on a DNA sketch.
+  void add_proteins_device(const uint8_t* d_seq, uint64_t total_len, const uint64_t* h_offsets, uint32_t nrec, hipStream_t stream);
+  void add_proteins_host(const uint8_t* h_seq, uint64_t total_len, const uint64_t* h_offsets, uint32_t nrec);
+  void check_amino_input() const;   // the two refusals that need no device: DNA sketch (kMsg), ksize / 3 == 0 (panic)
 };
 
 // Many sketches from one batch (additive C ABI smh_add_sequences_grouped): record r feeds

@@ -540,7 +540,7 @@ void Sbt::find_many(const std::vector<const KmerMinHash*>& queries, double thres
     uint32_t c = 0;
     for (; c < classes.size(); c++) {
       const KmerMinHash& b = *classes[c];
-      if (a.ksize == b.ksize && a.is_protein == b.is_protein && a.max_hash == b.max_hash && a.seed == b.seed) break;
+      if (a.ksize == b.ksize && a.molecule == b.molecule && a.max_hash == b.max_hash && a.seed == b.seed) break;
     }
     if (c == classes.size()) classes.push_back(&a);
     leaf_class[i] = c;

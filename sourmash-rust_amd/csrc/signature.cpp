@@ -292,7 +292,9 @@ KmerMinHash sketch_from_json(const JVal& v) {
   if (ab && ab->kind != JVal::Null) { mh.has_abunds = true; mh.abunds = want_u64_array(ab, "abundances"); }
   else { mh.has_abunds = false; mh.abunds.clear(); }
   const std::string& mol = want_str(v.get("molecule"), "molecule");
-  mh.is_protein = mol == "protein";            // anything else reads as DNA (Q9)
+  // anything else reads as DNA (Q9); dayhoff / hp are this library's own (include/sourmash_amd.h "alphabets")
+  mh.molecule = mol == "protein" ? kMoleculeProtein : mol == "dayhoff" ? kMoleculeDayhoff : mol == "hp" ? kMoleculeHp : kMoleculeDNA;
+  mh.is_protein = mh.molecule != kMoleculeDNA;
   mh.num = mh.max_hash != 0 ? 0 : num;          // Q9
   return mh;
 }
@@ -372,7 +374,7 @@ void sketch_to_json(std::string& out, const KmerMinHash& mh) {
   u64_array(out, mh.mins);
   out += ",\"md5sum\":\"" + sketch_md5(mh) + "\"";
   if (mh.has_abunds) { out += ",\"abundances\":"; u64_array(out, mh.abunds); }
-  out += std::string(",\"molecule\":\"") + (mh.is_protein ? "protein" : "DNA") + "\"}";
+  out += std::string(",\"molecule\":\"") + molecule_name(mh.molecule) + "\"}";
 }
 
 }  // namespace
@@ -380,7 +382,7 @@ void sketch_to_json(std::string& out, const KmerMinHash& mh) {
 bool sketch_equal(const KmerMinHash& a, const KmerMinHash& b) {
   a.materialize();
   b.materialize();
-  return a.num == b.num && a.ksize == b.ksize && a.is_protein == b.is_protein && a.seed == b.seed &&
+  return a.num == b.num && a.ksize == b.ksize && a.molecule == b.molecule && a.seed == b.seed &&
          a.max_hash == b.max_hash && a.mins.get() == b.mins.get() && a.has_abunds == b.has_abunds &&
          (!a.has_abunds || a.abunds == b.abunds);
 }
@@ -434,7 +436,8 @@ std::vector<Signature> load_signatures(const char* data, size_t len, size_t ksiz
   for (auto& s : orig) {
     for (auto& mh : s.signatures) {
       if (!(ksize == 0 || ksize == (size_t)mh.ksize)) continue;
-      if (moltype && !((mt == "dna" && !mh.is_protein) || (mt == "protein" && mh.is_protein))) continue;
+      if (moltype && !((mt == "dna" && mh.molecule == kMoleculeDNA) || (mt == "protein" && mh.molecule == kMoleculeProtein) ||
+                        (mt == "dayhoff" && mh.molecule == kMoleculeDayhoff) || (mt == "hp" && mh.molecule == kMoleculeHp))) continue;
       Signature one = s;
       one.signatures.clear();
       one.signatures.push_back(mh);

@@ -430,7 +430,7 @@ def union_across_ranks(mh, group=None, parts=None):
     `parts` (tests): a list of sketches standing in for the other ranks' (no process group needed)."""
     import torch
     from .errors import SourmashError
-    from .minhash import KmerMinHash
+    from .minhash import KmerMinHash, MOLECULES
     assert mh.num == 0 and mh.max_hash > 0, "the device union is for scaled sketches"
     comm = _Comm(group)
     track = mh.track_abundance
@@ -440,7 +440,7 @@ def union_across_ranks(mh, group=None, parts=None):
         # what check_compatible looks at (reference src/lib.rs:176-190), + whether abundances are tracked (it decides
         # whether a rank takes part in the second all-gather: a mismatch there would hang the job, not fail it)
         mx = p.max_hash
-        return [p.export_dev(), p.ksize, 1 if p.is_protein else 0, p.seed & 0xFFFFFFFF, p.seed >> 32,
+        return [p.export_dev(), p.ksize, MOLECULES.index(p.molecule), p.seed & 0xFFFFFFFF, p.seed >> 32,
                 mx & 0xFFFFFFFF, mx >> 32, 1 if p.track_abundance else 0]
 
     table = [params(p) for p in locals_]
@@ -450,7 +450,7 @@ def union_across_ranks(mh, group=None, parts=None):
     # every rank sees the same table, so every rank raises the same error -- before any data collective
     mine = params(mh)
     for r, row in enumerate(table):
-        for col, code, what in ((1, 101, "ksize"), (2, 102, "DNA/protein"), (5, 103, "max_hash"), (6, 103, "max_hash"),
+        for col, code, what in ((1, 101, "ksize"), (2, 102, "molecule"), (5, 103, "max_hash"), (6, 103, "max_hash"),
                                 (3, 104, "seed"), (4, 104, "seed")):
             if row[col] != mine[col]:
                 raise SourmashError(code, "union_across_ranks: part %d differs in %s" % (r, what))
@@ -473,7 +473,8 @@ def union_across_ranks(mh, group=None, parts=None):
         pairs = [padded(p, track) for p in parts]
         gm = torch.cat([x[0] for x in pairs])
         ga = torch.cat([x[1] for x in pairs]) if track else None
-    out = KmerMinHash(0, mh.ksize, mh.is_protein, mh.seed, mh.max_hash, track)
+    out = KmerMinHash(0, mh.ksize, mh.is_protein, mh.seed, mh.max_hash, track,
+                      alphabet=mh.molecule if mh.is_protein else None)
     out.absorb_dev(gm, ga, [r * cap for r in range(len(sizes))], sizes)
     return out
 

@@ -2,6 +2,7 @@
 
     recs = fastx.Records.parse(fastx.read_text("reads.fastq.gz"))
     mh.add_records(recs)
+    prot.add_records_protein(fastx.Records.parse(fastx.read_text("proteome.faa")))     # amino acids: a protein / dayhoff / hp sketch
 
 The text may be host bytes (uploaded, then parsed) or a CUDA uint8 tensor already in HBM.  The handle owns the
 compacted sequence bytes and the offsets; it keeps no reference to the text.  Names are spans into the text: the

@@ -25,11 +25,22 @@ def hash_words(words, seed=42):
     return out
 
 
+MOLECULES = ("DNA", "protein", "dayhoff", "hp")      # SMH_MOLECULE_* of include/sourmash_amd.h, and the signature JSON's strings
+
+
 class KmerMinHash:
-    def __init__(self, num, ksize, is_protein=False, seed=42, max_hash=0, track_abundance=False, _ptr=None):
+    def __init__(self, num, ksize, is_protein=False, seed=42, max_hash=0, track_abundance=False, _ptr=None, *, alphabet=None):
+        """alphabet: None (DNA, or protein when is_protein), "protein", "dayhoff" or "hp" -- the last three imply is_protein."""
         self._L = lib()
-        self._p = _ptr if _ptr is not None else self._L.kmerminhash_new(
-            num, ksize, bool(is_protein), seed, max_hash, bool(track_abundance))
+        if _ptr is not None:
+            self._p = _ptr
+        elif alphabet is None:
+            self._p = self._L.kmerminhash_new(num, ksize, bool(is_protein), seed, max_hash, bool(track_abundance))
+        else:
+            if alphabet not in MOLECULES[1:]:
+                raise ValueError("alphabet must be one of %s" % ", ".join(MOLECULES[1:]))
+            self._p = call(self._L.smh_kmerminhash_new_molecule, num, ksize, MOLECULES.index(alphabet), seed, max_hash,
+                           bool(track_abundance))
 
     def __del__(self):
         try:
@@ -44,6 +55,8 @@ class KmerMinHash:
     def ksize(self): return self._L.kmerminhash_ksize(self._p)
     @property
     def is_protein(self): return self._L.kmerminhash_is_protein(self._p)
+    @property
+    def molecule(self): return MOLECULES[self._L.smh_kmerminhash_molecule(self._p)]
     @property
     def seed(self): return self._L.kmerminhash_seed(self._p)
     @property
@@ -139,6 +152,30 @@ class KmerMinHash:
         arr = (C.c_void_p * len(sketches))(*[m._p for m in sketches])
         call(L.smh_add_sequences_grouped_dev, arr, len(sketches), C.c_void_p(dev_ptr), total_len, off.ctypes.data_as(u64p),
              grp.ctypes.data_as(C.POINTER(C.c_uint32)), off.size - 1, bool(force), C.c_void_p(stream or 0))
+
+    # --- amino-acid input (additive ABI smh_add_protein*; the rules are in include/sourmash_amd.h)
+    def add_protein(self, seq):
+        """Every window of ksize // 3 residues of one amino-acid record, through the sketch's alphabet."""
+        seq = bytes(seq)
+        call(self._L.smh_add_protein, self._p, seq, len(seq))
+
+    def add_proteins(self, records):
+        """Many amino-acid records in one device pass, as add_protein on each in order."""
+        records = [bytes(r) for r in records]
+        off = np.zeros(len(records) + 1, dtype=np.uint64)
+        for i, r in enumerate(records):
+            off[i + 1] = off[i] + len(r)
+        call(self._L.smh_add_proteins, self._p, b"".join(records), off.ctypes.data_as(u64p), len(records))
+
+    def add_proteins_dev(self, dev_ptr, total_len, offsets, stream=None):
+        """Amino-acid records already resident in HBM (any alignment of dev_ptr)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        call(self._L.smh_add_proteins_dev, self._p, C.c_void_p(dev_ptr), total_len, off.ctypes.data_as(u64p), off.size - 1,
+             C.c_void_p(stream or 0))
+
+    def add_records_protein(self, records):
+        """Every record of a fastx.Records handle parsed from a protein FASTA, as add_proteins on the same records."""
+        call(self._L.smh_add_records_protein, self._p, records._p)
 
     def add_records(self, records, force=False):
         """Every record of a fastx.Records handle (parsed on the device), as add_sequences on the same records."""

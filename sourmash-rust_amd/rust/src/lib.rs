@@ -81,6 +81,20 @@ extern "C" {
     fn free(p: *mut c_void);
 }
 
+// Alphabets and amino-acid input (include/sourmash_amd.h); link-checked by tests/c_amino_symbols.c.
+#[allow(dead_code)]
+extern "C" {
+    fn smh_kmerminhash_new_molecule(n: u32, k: u32, molecule: i32, seed: u64, mx: u64, track_abundance: bool) -> *mut RawKmerMinHash;
+    fn smh_kmerminhash_molecule(ptr: *const RawKmerMinHash) -> i32;
+    fn smh_add_protein(ptr: *mut RawKmerMinHash, seq: *const c_char, len: u64) -> i32;
+    fn smh_add_proteins(ptr: *mut RawKmerMinHash, seq: *const c_char, offsets: *const u64, n_records: u32) -> i32;
+    fn smh_add_proteins_dev(
+        ptr: *mut RawKmerMinHash, seq_dev: *const c_void, total_len: u64, offsets: *const u64, n_records: u32, stream: *mut c_void,
+    ) -> i32;
+    fn smh_add_records_protein(ptr: *mut RawKmerMinHash, records: *const c_void) -> i32;
+    fn smh_amino_geometry(total_len: u64, win: u32, tile_positions: *mut u32, run: *mut u32);
+}
+
 /// Error of the library's thread-local slot (codes of reference `src/errors.rs:28-50`).  Stands where
 /// the reference has `failure::Error`.
 #[derive(Debug, Clone, PartialEq)]
@@ -124,12 +138,24 @@ pub fn _hash_murmur(kmer: &[u8], seed: u64) -> u64 {
     out
 }
 
-/// Same public fields as the reference struct (`src/lib.rs:37-46`).
+/// The alphabet residues are hashed in (`SMH_MOLECULE_*` of `include/sourmash_amd.h`).
+#[derive(Debug, Clone, Copy, PartialEq)]
+#[repr(i32)]
+pub enum Molecule {
+    Dna = 0,
+    Protein = 1,
+    Dayhoff = 2,
+    Hp = 3,
+}
+
+/// The public fields of the reference struct (`src/lib.rs:37-46`), plus the molecule: `is_protein` is
+/// `molecule != Molecule::Dna`, and `new` keeps the two in step.
 #[derive(Debug, Clone, PartialEq)]
 pub struct KmerMinHash {
     pub num: u32,
     pub ksize: u32,
     pub is_protein: bool,
+    pub molecule: Molecule,
     pub seed: u64,
     pub max_hash: u64,
     pub mins: Vec<u64>,
@@ -139,7 +165,7 @@ pub struct KmerMinHash {
 impl Default for KmerMinHash {
     /// reference `src/lib.rs:48-60`
     fn default() -> KmerMinHash {
-        KmerMinHash { num: 1000, ksize: 21, is_protein: false, seed: 42, max_hash: 0, mins: Vec::with_capacity(1000), abunds: None }
+        KmerMinHash { num: 1000, ksize: 21, is_protein: false, molecule: Molecule::Dna, seed: 42, max_hash: 0, mins: Vec::with_capacity(1000), abunds: None }
     }
 }
 
@@ -153,9 +179,14 @@ impl Drop for Handle {
 impl KmerMinHash {
     /// reference `src/lib.rs:142-174`
     pub fn new(num: u32, ksize: u32, is_protein: bool, seed: u64, max_hash: u64, track_abundance: bool) -> KmerMinHash {
+        Self::new_molecule(num, ksize, if is_protein { Molecule::Protein } else { Molecule::Dna }, seed, max_hash, track_abundance)
+    }
+
+    /// A sketch in any of the four alphabets (`smh_kmerminhash_new_molecule`).
+    pub fn new_molecule(num: u32, ksize: u32, molecule: Molecule, seed: u64, max_hash: u64, track_abundance: bool) -> KmerMinHash {
         let cap = if num > 0 { num as usize } else { 1000 };
         KmerMinHash {
-            num, ksize, is_protein, seed, max_hash,
+            num, ksize, is_protein: molecule != Molecule::Dna, molecule, seed, max_hash,
             mins: Vec::with_capacity(cap),
             abunds: if track_abundance { Some(Vec::with_capacity(cap)) } else { None },
         }
@@ -164,7 +195,9 @@ impl KmerMinHash {
     /// Library-side copy of the current state (raw pushes: no ordering check, like the reference ABI).
     fn to_handle(&self) -> Handle {
         unsafe {
-            let h = kmerminhash_new(self.num, self.ksize, self.is_protein, self.seed, self.max_hash, self.abunds.is_some());
+            // (a struct filled by hand may say is_protein without a molecule: that is the 20-letter alphabet)
+            let mol = if self.molecule == Molecule::Dna && self.is_protein { Molecule::Protein } else { self.molecule };
+            let h = smh_kmerminhash_new_molecule(self.num, self.ksize, mol as i32, self.seed, self.max_hash, self.abunds.is_some());
             for &m in &self.mins {
                 kmerminhash_mins_push(h, m);
             }
@@ -229,6 +262,17 @@ impl KmerMinHash {
     /// exactly as there.
     pub fn add_sequence(&mut self, seq: &[u8], force: bool) -> Result<(), Error> {
         self.mutate(|h| unsafe { smh_add_sequence_len(h, seq.as_ptr() as *const c_char, seq.len() as u64, force) })
+    }
+
+    /// Amino-acid input (`smh_add_protein`): every window of `ksize / 3` residues, through the sketch's alphabet.
+    pub fn add_protein(&mut self, seq: &[u8]) -> Result<(), Error> {
+        self.mutate(|h| unsafe { smh_add_protein(h, seq.as_ptr() as *const c_char, seq.len() as u64) })
+    }
+
+    /// Many amino-acid records in one device pass (`smh_add_proteins`); `offsets` has one entry more than there are records.
+    pub fn add_proteins(&mut self, seq: &[u8], offsets: &[u64]) -> Result<(), Error> {
+        let n = offsets.len().saturating_sub(1) as u32;
+        self.mutate(|h| unsafe { smh_add_proteins(h, seq.as_ptr() as *const c_char, offsets.as_ptr(), n) })
     }
 
     /// reference `src/lib.rs:307-403`
