@@ -350,6 +350,55 @@ void smh_angular_last_stats(uint64_t *pairs_walked, uint64_t *pairs_skipped);
 uint64_t smh_angular_prune_min_pairs(void);
 void smh_angular_set_prune_min_pairs(uint64_t pairs);
 
+/* Downsampling: cutting scaled sketches and resident indexes at a coarser resolution, so that operands sketched at
+ * different `scaled` can meet (every search route refuses operands whose max_hash differ, 103).  The reference crate has
+ * no downsampling, so the rules are fixed here -- DESIGN.md 3.12, restated in tests/downsample_restatement.py.
+ *   Scaled sketch   num == 0 and max_hash != 0 (the test gather applies).
+ *   max_hash cut    keeps the hashes h <= new max_hash (unsigned, inclusive: the comparison add_hash makes) and their
+ *                   abundances when tracked; every other parameter is kept; the result has max_hash = new.  A scaled sketch
+ *                   is the ascending set of its hashes <= max_hash, so the cut is an exact prefix: nothing is hashed again.
+ *                   new == max_hash gives an equal, independent copy.
+ *   Refused         with SOURMASH_ERROR_CODE_MSG and a message naming the values: new == 0; new > max_hash (a sketch cannot
+ *                   be made finer); a sketch that is not a scaled sketch.
+ *   num cut         keeps the first `num` hashes (and abundances) of a sketch with num != 0 and max_hash == 0; the result has
+ *                   num = new.  Refused (MSG) for new == 0, new > num, and a sketch with max_hash != 0.  Host only.
+ *   Meeting         two scaled operands that differ in max_hash meet at the smaller of the two; ksize, seed and molecule
+ *                   still have to agree and raise what they raise today.
+ * The ABI speaks max_hash only (max_hash = min(2^64 / scaled, 2^64 - 1)).
+ *
+ * smh_kmerminhash_downsample_max_hash  a new sketch.  A host-resident sketch is cut on the host (no device needed).  A sketch
+ *                           whose state lives in HBM is cut there: the bound is found by a kernel, the prefixes of its arrays
+ *                           are copied device to device into a state of the new sketch's own, and 16 bytes come back (the
+ *                           cut and the new total).  Neither sketch is brought to the host.  NULL on failure.
+ * smh_kmerminhash_downsample_num       a new sketch, cut on the host.  NULL on failure.
+ * smh_index_downsample      a new, owned index holding the parent's nodes cut at max_hash, in the parent's order, built from
+ *                           the parent's device arrays: a bounds pass (one wave per node), the kept lengths to the host
+ *                           (4 B per node), then a copy balanced over the output.  Refused (MSG) when a node is not a
+ *                           scaled sketch, when max_hash is 0, and when it exceeds the smallest max_hash of a node.  A parent
+ *                           whose nodes differ in max_hash is thereby brought to one resolution.  The child has abundances
+ *                           exactly when the parent has, keeps no reference to the parent and builds its own dictionary.
+ *                           An abundance of 2^32 or more (see the angular rules) counts only at a position the cut kept.
+ *                           NULL on failure.
+ * smh_index_max_hash_range  the smallest and the largest max_hash over the nodes; 0, 0 for an empty index.
+ * smh_index_all_scaled      true when every node was a scaled sketch when the index was built (also for an empty index):
+ *                           what smh_index_downsample requires.  Decided once, at construction.
+ * smh_downsample_block_dev  the CSR / device form, next to smh_compare_block_dev: hashes (u64) and optional abundances (u32)
+ *                           in device memory, offsets (n + 1) on the host.  The kept prefixes are written densely to
+ *                           out_hashes_dev / out_abunds_dev, out_offsets (host, n + 1 entries) start at 0.  capacity counts
+ *                           elements: when the kept total exceeds it the call fails with MSG before it writes anything (a
+ *                           capacity equal to the input total always suffices).  Outputs must not alias inputs.
+ * smh_downsample_geometry   output elements per workgroup of the copy, and its threads (tests, tools).
+ * Timers under smh_profile_get: "downsample_bounds", "downsample_copy"; event counter: "index_downsampled". */
+KmerMinHash *smh_kmerminhash_downsample_max_hash(const KmerMinHash *ptr, uint64_t max_hash);
+KmerMinHash *smh_kmerminhash_downsample_num(const KmerMinHash *ptr, uint32_t num);
+SmhIndex *smh_index_downsample(SmhIndex *index, uint64_t max_hash);
+int smh_index_max_hash_range(const SmhIndex *index, uint64_t *lo, uint64_t *hi);
+bool smh_index_all_scaled(const SmhIndex *index);
+int smh_downsample_block_dev(const uint64_t *hashes_dev, const uint32_t *abunds_dev, const uint64_t *offsets, uint32_t n,
+                             uint64_t max_hash, uint64_t *out_hashes_dev, uint32_t *out_abunds_dev, uint64_t capacity,
+                             uint64_t *out_offsets, void *stream);
+void smh_downsample_geometry(uint32_t *tile_elems, uint32_t *threads);
+
 /* deterministic synthetic DNA of SURVEY.md 8d written to device memory (benchmark input) */
 int smh_synth_dna_dev(void *out_dev, uint64_t start, uint64_t len, uint64_t seed, uint64_t n_every,
                       void *stream);

@@ -163,6 +163,14 @@ _SIGS = {
     "smh_angular_last_stats": (None, [u64p, u64p]),
     "smh_angular_prune_min_pairs": (C.c_uint64, []),
     "smh_angular_set_prune_min_pairs": (None, [C.c_uint64]),
+    "smh_kmerminhash_downsample_max_hash": (C.c_void_p, [C.c_void_p, C.c_uint64]),
+    "smh_kmerminhash_downsample_num": (C.c_void_p, [C.c_void_p, C.c_uint32]),
+    "smh_index_downsample": (C.c_void_p, [C.c_void_p, C.c_uint64]),
+    "smh_index_max_hash_range": (C.c_int, [C.c_void_p, u64p, u64p]),
+    "smh_index_all_scaled": (C.c_bool, [C.c_void_p]),
+    "smh_downsample_block_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                           u64p, C.c_void_p]),
+    "smh_downsample_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smh_release_workspace": (C.c_int, []),
     "smh_pool_set_limit": (None, [C.c_uint64]),
     "smh_pool_bytes": (C.c_uint64, []),

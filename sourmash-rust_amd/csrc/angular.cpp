@@ -116,14 +116,15 @@ void run_host(const AngularSet& R, const AngularSet& C, const uint64_t* prune_de
 
 void ResidentIndex::angular_ensure(const char* what, hipStream_t s) {
   if (!angular_ready) {
-    abunds_dev.ensure(h_abunds.size() * 4 + 4);
+    // (a cut made from a parent whose abundances were in HBM holds them in abunds_dev already: nothing to allocate or upload)
+    if (!abunds_resident) abunds_dev.ensure(h_abunds.size() * 4 + 4);
     norm2_dev.ensure((size_t)n * 8 + 8);
     h_norm2.assign(n, 0);
     uint32_t err = kAngularNoError;
     if (n) {
       PoolBlock e(4);
       HIP_CHECK(hipMemsetAsync(e.ptr, 0xff, 4, s));
-      if (!h_abunds.empty())
+      if (!abunds_resident && !h_abunds.empty())
         HIP_CHECK(hipMemcpyAsync(abunds_dev.ptr, h_abunds.data(), h_abunds.size() * 4, hipMemcpyHostToDevice, s));
       launch_angular_norms(abunds_dev.as<uint32_t>(), offsets.as<uint64_t>(), n, norm2_dev.as<uint64_t>(), e.as<uint32_t>(), s);
       HIP_CHECK(hipMemcpyAsync(h_norm2.data(), norm2_dev.ptr, (size_t)n * 8, hipMemcpyDeviceToHost, s));

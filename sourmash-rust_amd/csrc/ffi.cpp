@@ -773,6 +773,39 @@ void smh_angular_last_stats(uint64_t* pairs_walked, uint64_t* pairs_skipped) {
 uint64_t smh_angular_prune_min_pairs(void) { return smh::g_angular_prune_min_pairs; }
 void smh_angular_set_prune_min_pairs(uint64_t pairs) { smh::g_angular_prune_min_pairs = pairs ? pairs : smh::kAngularPruneMinPairs; }
 
+// ------------------------------------------------------------------ downsampling (downsample.cpp, index.cpp)
+
+KmerMinHash* smh_kmerminhash_downsample_max_hash(const KmerMinHash* ptr, uint64_t max_hash) {
+  return pad<KmerMinHash*>([&] {
+    require(ptr, "ptr");
+    std::unique_ptr<KmerMinHash> out(new KmerMinHash());
+    smh::downsample_max_hash(*ptr, max_hash, *out);
+    return out.release();
+  });
+}
+KmerMinHash* smh_kmerminhash_downsample_num(const KmerMinHash* ptr, uint32_t num) {
+  return pad<KmerMinHash*>([&] {
+    require(ptr, "ptr");
+    std::unique_ptr<KmerMinHash> out(new KmerMinHash());
+    smh::downsample_num(*ptr, num, *out);
+    return out.release();
+  });
+}
+SmhIndex* smh_index_downsample(SmhIndex* index, uint64_t max_hash) {
+  return pad<SmhIndex*>([&] { require(index, "index"); return new SmhIndex(*index, max_hash); });
+}
+int smh_index_max_hash_range(const SmhIndex* index, uint64_t* lo, uint64_t* hi) {
+  return pad_code([&] { require(index, "index"); index->max_hash_range(lo, hi); });
+}
+int smh_downsample_block_dev(const uint64_t* hashes_dev, const uint32_t* abunds_dev, const uint64_t* offsets, uint32_t n, uint64_t max_hash,
+                             uint64_t* out_hashes_dev, uint32_t* out_abunds_dev, uint64_t capacity, uint64_t* out_offsets, void* stream) {
+  return pad_code([&] {
+    smh::downsample_block_dev(hashes_dev, abunds_dev, offsets, n, max_hash, out_hashes_dev, out_abunds_dev, capacity, out_offsets, stream);
+  });
+}
+bool smh_index_all_scaled(const SmhIndex* index) { return index && index->all_scaled; }
+void smh_downsample_geometry(uint32_t* tile_elems, uint32_t* threads) { smh::downsample_geometry(tile_elems, threads); }
+
 // ---- a scaled sketch's state as device arrays: the cross-rank union of partial sketches ----
 int smh_sketch_export_dev(KmerMinHash* ptr, uint64_t* mins_dev, uint64_t* abunds_dev, uint64_t capacity, uint64_t* n_out, void* stream) {
   return pad_code([&] {

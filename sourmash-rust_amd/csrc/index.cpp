@@ -1,9 +1,11 @@
-// index.cpp -- smh::ResidentIndex: construction, parameter checks, the block route and its cached dictionary, one sketch, gather.
+// index.cpp -- smh::ResidentIndex: construction (from host nodes, or as the cut of a parent made on the device), parameter
+// checks, the block route and its cached dictionary, one sketch, gather.
 #include "index.hpp"
 
 #include <algorithm>
 #include <memory>
 #include <set>
+#include <string>
 
 namespace smh {
 
@@ -23,6 +25,7 @@ ResidentIndex::ResidentIndex(const std::vector<const KmerMinHash*>& v) {
     const KmerMinHash& p0 = params[0];
     uniform &= p.ksize == p0.ksize && p.molecule == p0.molecule && p.max_hash == p0.max_hash && p.seed == p0.seed;
     any_num |= p.num != 0;
+    all_scaled &= p.num == 0 && p.max_hash != 0;
   }
   {
     auto& dev = Device::get();
@@ -37,7 +40,7 @@ ResidentIndex::ResidentIndex(const std::vector<const KmerMinHash*>& v) {
       h_abunds.reserve(h_offsets.back());
       for (uint32_t i = 0; i < n; i++)
         for (uint64_t a : v[i]->abunds) {
-          if (a >> 32) { wide_node = std::min(wide_node, i); a = 0xffffffffull; }
+          if (a >> 32) { wide_node = std::min(wide_node, i); wide_pos.push_back(h_abunds.size()); a = 0xffffffffull; }
           h_abunds.push_back((uint32_t)a);
         }
     }
@@ -47,6 +50,74 @@ ResidentIndex::ResidentIndex(const std::vector<const KmerMinHash*>& v) {
   }
   std::lock_guard<std::mutex> g(registry_mu());   // last: nothing above may leave a half-built index registered
   registry().insert(this);
+}
+
+ResidentIndex::ResidentIndex(ResidentIndex& parent, uint64_t mx) {
+  uint64_t lo = 0, hi = 0;
+  parent.max_hash_range(&lo, &hi);
+  for (uint32_t i = 0; i < parent.n; i++)
+    if (!(parent.params[i].num == 0 && parent.params[i].max_hash != 0))
+      throw Error(kMsg, "downsample: node " + std::to_string(i) + " is not a scaled sketch (num = " + std::to_string(parent.params[i].num) +
+                        ", max_hash = " + std::to_string(parent.params[i].max_hash) + ")");
+  if (mx == 0) throw Error(kMsg, "downsample: the new max_hash is 0");
+  if (parent.n && mx > lo)
+    throw Error(kMsg, "downsample: the new max_hash " + std::to_string(mx) + " exceeds the smallest max_hash of a node, " +
+                      std::to_string(lo) + " (a sketch cannot be made finer)");
+  n = parent.n;
+  h_nums.assign(n, 0);
+  params = parent.params;
+  for (uint32_t i = 0; i < n; i++) {
+    params[i].max_hash = mx;
+    const KmerMinHash &p = params[i], &p0 = params[0];
+    uniform &= p.ksize == p0.ksize && p.molecule == p0.molecule && p.seed == p0.seed;
+  }
+  {
+    auto& dev = Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    hipStream_t s = dev.stream();
+    // bounds, the kept lengths to the host, the offsets, then the copy
+    max_len = downsample_bounds_host(parent.hashes.as<uint64_t>(), parent.offsets.as<uint64_t>(), n, mx, &h_offsets, dev, s);
+    const uint64_t total = h_offsets.back();
+    hashes.ensure(total * 8 + 8);   // (the padding of pack_sketches: the compare kernels read a little past the end)
+    offsets.ensure(h_offsets.size() * 8);
+    HIP_CHECK(hipMemcpyAsync(offsets.ptr, h_offsets.data(), h_offsets.size() * 8, hipMemcpyHostToDevice, s));
+    has_abunds = parent.has_abunds;
+    // the parent's abundances live in HBM already: the copy cuts them too (angular_ensure then finds nothing to upload)
+    const bool on_device = has_abunds && (parent.angular_ready || parent.abunds_resident);
+    if (on_device) { abunds_dev.ensure(total * 4 + 4); abunds_resident = true; }
+    launch_downsample_copy(parent.hashes.as<uint64_t>(), on_device ? parent.abunds_dev.as<uint32_t>() : nullptr,
+                           parent.offsets.as<uint64_t>(), offsets.as<uint64_t>(), n, total, hashes.as<uint64_t>(),
+                           on_device ? abunds_dev.as<uint32_t>() : nullptr, dev, s);
+    if (has_abunds && !on_device) {
+      h_abunds.reserve(total);
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* a = parent.h_abunds.data() + parent.h_offsets[i];
+        h_abunds.insert(h_abunds.end(), a, a + (h_offsets[i + 1] - h_offsets[i]));
+      }
+    }
+    // an abundance of 2^32 or more counts only where the cut kept it
+    for (uint64_t p : parent.wide_pos) {
+      const uint32_t i = (uint32_t)(std::upper_bound(parent.h_offsets.begin(), parent.h_offsets.end(), p) - parent.h_offsets.begin() - 1);
+      const uint64_t t = p - parent.h_offsets[i];
+      if (t < h_offsets[i + 1] - h_offsets[i]) { wide_node = std::min(wide_node, i); wide_pos.push_back(h_offsets[i] + t); }
+    }
+    nums.ensure((size_t)n * 4 + 4);
+    HIP_CHECK(hipMemsetAsync(nums.ptr, 0, (size_t)n * 4 + 4, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    dev.count("index_downsampled");
+  }
+  std::lock_guard<std::mutex> g(registry_mu());
+  registry().insert(this);
+}
+
+void ResidentIndex::max_hash_range(uint64_t* lo, uint64_t* hi) const {
+  uint64_t a = 0, b = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    a = i ? std::min(a, params[i].max_hash) : params[i].max_hash;
+    b = std::max(b, params[i].max_hash);
+  }
+  if (lo) *lo = a;
+  if (hi) *hi = b;
 }
 
 ResidentIndex::~ResidentIndex() {

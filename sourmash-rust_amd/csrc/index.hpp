@@ -14,6 +14,7 @@ struct ResidentIndex {
   // decided once for the whole set: every node has the parameters of node 0 (a sketch is then checked against that one
   // block), and whether any node is a bottom-`num` sketch
   bool uniform = true, any_num = false;
+  bool all_scaled = true;   // every node has num == 0 and max_hash != 0: what a cut on the device requires
   // the dictionary of the resident set (dense ranks, components, frequent hashes), built by the first all-vs-all block of
   // the index with itself and kept: later ones skip the pre-pass (the nodes of an index never change)
   CollectionDict* dict = nullptr;
@@ -24,12 +25,18 @@ struct ResidentIndex {
   bool has_abunds = false;
   std::vector<uint32_t> h_abunds;
   uint32_t wide_node = kAngularNoError;   // the first node holding an abundance of 2^32 or more
+  std::vector<uint64_t> wide_pos;         // where in the CSR those abundances are, ascending (few): a cut may drop them
+  bool abunds_resident = false;           // a cut of a parent whose abundances were in HBM: abunds_dev holds them, h_abunds is empty
   bool angular_ready = false;
   uint32_t bad_node = kAngularNoError;
   DeviceBuffer abunds_dev, norm2_dev;
   std::vector<uint64_t> h_norm2;
   explicit ResidentIndex(const std::vector<const KmerMinHash*>& nodes);   // uploads the nodes
+  // the parent's nodes cut at max_hash, built from the parent's device arrays: nothing comes to the host
+  // but the kept lengths.  Refused (kMsg) unless every node is a scaled sketch and 0 < max_hash <= every node's max_hash.
+  ResidentIndex(ResidentIndex& parent, uint64_t max_hash);
   ~ResidentIndex();
+  void max_hash_range(uint64_t* lo, uint64_t* hi) const;   // over the nodes; 0, 0 when empty
   SketchSet set() const { return {hashes.as<uint64_t>(), offsets.as<uint64_t>(), n, h_offsets.data()}; }
   AngularSet angular_set() const {   // after angular_ensure
     return {hashes.as<uint64_t>(), abunds_dev.as<uint32_t>(), offsets.as<uint64_t>(), norm2_dev.as<uint64_t>(), n};
@@ -83,5 +90,18 @@ void angular_block_dev(AngularSet rows, const uint64_t* row_offsets, AngularSet 
 // that share a hash (default: tools/bench_angular.py's sweep, DESIGN.md 3.10 "The prune threshold").  walked / skipped: of the last call.
 constexpr uint64_t kAngularPruneMinPairs = 4096;
 extern uint64_t g_angular_prune_min_pairs, g_angular_walked, g_angular_skipped;
+
+// downsample.cpp (the rules are in include/sourmash_amd.h, "Downsampling").  `out` is a fresh sketch: it
+// receives src's parameters with max_hash / num replaced and the kept prefix.  A state that lives in HBM is cut there into a
+// DeviceSketch of out's own; neither sketch is brought to the host.
+void downsample_max_hash(const KmerMinHash& src, uint64_t max_hash, KmerMinHash& out);
+void downsample_num(const KmerMinHash& src, uint32_t num, KmerMinHash& out);   // host only
+// the bounds pass of a CSR and its read-back (4 bytes per sketch): new_off = the n + 1 offsets of the kept prefixes, from 0;
+// returns the longest of them
+uint32_t downsample_bounds_host(const uint64_t* hashes_dev, const uint64_t* offsets_dev, uint32_t n, uint64_t max_hash,
+                                std::vector<uint64_t>* new_off, Device& dev, hipStream_t s);
+// a CSR in device memory (offsets on the host, n + 1) cut into caller's buffers; out_offsets (host, n + 1) start at 0
+void downsample_block_dev(const uint64_t* hashes_dev, const uint32_t* abunds_dev, const uint64_t* offsets, uint32_t n, uint64_t max_hash,
+                          uint64_t* out_hashes_dev, uint32_t* out_abunds_dev, uint64_t capacity, uint64_t* out_offsets, void* stream);
 
 }  // namespace smh

@@ -1,5 +1,6 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
-// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip).  Plain structs and pointers; no torch types anywhere.
+// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip).  Plain structs and
+// pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -363,5 +364,23 @@ void launch_angular_norms(const uint32_t* abunds, const uint64_t* offsets_dev, u
 void launch_angular_block(const AngularSet& rows, const AngularSet& cols, const uint64_t* prune_dev, bool symmetric,
                           const AngularOut& out, unsigned long long* counters_dev, Device& dev, hipStream_t s);
 uint32_t angular_chunk(uint32_t n_rows, uint32_t n_cols);   // columns per workgroup that launch_angular_block gives a block
+
+// --- downsample_kernels.hip ------------------------------------------------------------
+// Cutting scaled sketches at a smaller max_hash: the kept prefix of every segment of a CSR.
+constexpr uint32_t kDownsampleTile = 4096;      // output elements per workgroup of the copy
+constexpr uint32_t kDownsampleThreads = 256;
+void downsample_geometry(uint32_t* tile_elems, uint32_t* threads);
+// kept_dev[i] = how many hashes of sketch i are <= max_hash (one wave per sketch; profile name downsample_bounds)
+void launch_downsample_bounds(const uint64_t* hashes, const uint64_t* offsets_dev, uint32_t n, uint64_t max_hash, uint32_t* kept_dev,
+                              Device& dev, hipStream_t s);
+// out[new_offsets[i] + t] = in[src_offsets[i] + t] for t < new_offsets[i + 1] - new_offsets[i]: hashes, and abundances when
+// `abunds` is given.  total = new_offsets[n]; new_offsets[0] == 0.  Outputs must not alias inputs (downsample_copy).
+void launch_downsample_copy(const uint64_t* hashes, const uint32_t* abunds, const uint64_t* src_offsets_dev,
+                            const uint64_t* new_offsets_dev, uint32_t n, uint64_t total, uint64_t* out_hashes, uint32_t* out_abunds,
+                            Device& dev, hipStream_t s);
+// one device-resident sketch: out2_dev[0] = cut = how many of uniq[0 .. n) are <= max_hash, out2_dev[1] = the total its kept
+// run starts end at (starts[cut], or `total` when everything is kept); without run starts out2_dev[1] = cut
+void launch_downsample_cut(const uint64_t* uniq, uint64_t n, const uint32_t* starts, uint64_t total, uint64_t max_hash, uint64_t* out2_dev,
+                           hipStream_t s);
 
 }  // namespace smh

@@ -14,7 +14,7 @@ import math
 import numpy as np
 
 from ._lib import SmhGatherRow, lib, u64p
-from .errors import call
+from .errors import SourmashError, call
 
 UNASSIGNED = 0xFFFFFFFF
 
@@ -38,6 +38,18 @@ def scaled_of_max_hash(max_hash):
     return max(1, ((1 << 64) + max_hash // 2) // max_hash)
 
 
+def max_hash_of_scaled(scaled):
+    """the max_hash a `scaled` stands for, min(2^64 // scaled, 2^64 - 1): the inverse of scaled_of_max_hash"""
+    scaled = int(scaled)
+    if scaled <= 0:
+        raise ValueError("scaled must be positive")
+    return min((1 << 64) // scaled, (1 << 64) - 1)
+
+
+def _is_scaled(mh):
+    return mh.num == 0 and mh.max_hash != 0
+
+
 def search_minhashes(nodes, query, threshold):
     """indices i with nodes[i].similarity(query) > threshold"""
     return _find(nodes, query, threshold, False)
@@ -58,17 +70,40 @@ def _find(nodes, query, threshold, containment):
 
 
 class ResidentIndex:
-    """Sketches copied once into HBM (additive ABI smh_index_*): repeated queries upload only the query."""
+    """Sketches copied once into HBM (additive ABI smh_index_*): repeated queries upload only the query.
 
-    def __init__(self, nodes):
+    max_hash: build at that resolution from scaled nodes of mixed `scaled` (every node is cut on the device,
+    smh_index_downsample).  `nodes` keeps the sketches as they were given: for an index built with max_hash, and for
+    every index downsample() returns, they are the UNCUT sketches -- their max_hash and mins are not what the index holds
+    (ask max_hash / max_hash_range, or cut a node with downsample_max_hash).
+
+    The search calls take downsample=False.  With True both operands must be scaled sketches (else Msg): they meet at the
+    smaller max_hash of the two, each finer side replaced by its cut -- a sketch by downsample_max_hash, an index by a child
+    this index caches per max_hash (drop_downsampled() gives the children back).  Node positions in the results are those
+    of this index: the cut never reorders."""
+
+    def __init__(self, nodes, max_hash=None, *, _handle=None):
         self._L = lib()
         self.nodes = list(nodes)
+        self._children = {}
+        self._all_scaled = None
+        self._h = _handle          # (None until a handle is owned: __del__ frees nothing else)
+        if _handle is not None:
+            return
         arr = (C.c_void_p * max(len(self.nodes), 1))(*[m._p for m in self.nodes])
-        self._h = call(self._L.smh_index_new, arr, len(self.nodes))
+        fine = call(self._L.smh_index_new, arr, len(self.nodes))
+        if max_hash is None:
+            self._h = fine
+            return
+        try:
+            self._h = call(self._L.smh_index_downsample, fine, int(max_hash))   # a refusal leaves this object without a handle
+        finally:
+            self._L.smh_index_free(fine)
 
     def __del__(self):
         try:
-            self._L.smh_index_free(self._h)
+            if self._h is not None:
+                self._L.smh_index_free(self._h)
         except Exception:
             pass
 
@@ -79,24 +114,98 @@ class ResidentIndex:
         """gives back the dictionary an all-vs-all compare of the index with itself cached (smh_index_drop_dictionary)"""
         self._L.smh_index_drop_dictionary(self._h)
 
-    def find(self, query, threshold, containment=False):
+    # --- downsampling (additive ABI smh_index_downsample; the rules are in include/sourmash_amd.h)
+    @property
+    def max_hash_range(self):
+        """(smallest, largest) max_hash over the nodes; (0, 0) for an empty index"""
+        lo, hi = C.c_uint64(), C.c_uint64()
+        call(self._L.smh_index_max_hash_range, self._h, C.byref(lo), C.byref(hi))
+        return lo.value, hi.value
+
+    @property
+    def max_hash(self):
+        """the max_hash every node has, or None when the nodes differ (or there are none)"""
+        lo, hi = self.max_hash_range
+        return lo if len(self) and lo == hi else None
+
+    def downsample(self, max_hash=None, scaled=None):
+        """This index cut at max_hash (or at the max_hash `scaled` stands for), made on the device from the resident
+        arrays: a ResidentIndex of its own, cached here per max_hash.  Its `nodes` are this index's uncut sketches."""
+        if (max_hash is None) == (scaled is None):
+            raise ValueError("give max_hash or scaled")
+        mx = int(max_hash) if max_hash is not None else max_hash_of_scaled(scaled)
+        child = self._children.get(mx)
+        if child is None:
+            child = ResidentIndex(self.nodes, _handle=call(self._L.smh_index_downsample, self._h, mx))
+            self._children[mx] = child
+        return child
+
+    def drop_downsampled(self):
+        """gives back the cut indexes downsample() cached"""
+        self._children.clear()
+
+    def _scaled_range(self, what):
+        """max_hash_range of an index whose nodes are all scaled sketches, else Msg"""
+        if self._all_scaled is None:      # from the parameters the index was built with; its nodes never change
+            self._all_scaled = bool(self._L.smh_index_all_scaled(self._h))
+        if not self._all_scaled:
+            raise SourmashError(3, "downsample: %s holds a node that is not a scaled sketch" % what)
+        return self.max_hash_range
+
+    def _at(self, common):
+        lo, hi = self.max_hash_range
+        return self if len(self) == 0 or lo == hi == common else self.downsample(max_hash=common)
+
+    def _meet_sketch(self, query):
+        """(index, query) at the smaller max_hash of the two"""
+        if not _is_scaled(query):
+            raise SourmashError(3, "downsample: the sketch is not a scaled sketch (num = %d, max_hash = %d)" % (query.num, query.max_hash))
+        lo, _ = self._scaled_range("the index")
+        qmx = query.max_hash
+        common = min(qmx, lo) if len(self) else qmx
+        return self._at(common), query if qmx == common else query.downsample_max_hash(common)
+
+    def _meet_index(self, other):
+        if other is self:
+            lo, _ = self._scaled_range("the index")
+            cut = self._at(lo)
+            return cut, cut
+        lo_a, _ = self._scaled_range("the row index")
+        lo_b, _ = other._scaled_range("the column index")
+        if len(self) == 0 or len(other) == 0:
+            return self, other
+        common = min(lo_a, lo_b)
+        return self._at(common), other._at(common)
+
+    def find(self, query, threshold, containment=False, downsample=False):
+        if downsample:
+            idx, q = self._meet_sketch(query)
+            return idx.find(q, threshold, containment)
         out = (C.c_uint32 * max(len(self.nodes), 1))()
         cnt = C.c_uint32()
         call(self._L.smh_index_find, self._h, query._p, float(threshold), bool(containment), out, C.byref(cnt))
         return [int(out[i]) for i in range(cnt.value)]
 
-    def most_common(self, leaf):
+    def most_common(self, leaf, downsample=False):
+        if downsample:
+            idx, q = self._meet_sketch(leaf)
+            return idx.most_common(q)
         pos, cm = C.c_uint32(), C.c_uint64()
         call(self._L.smh_index_most_common, self._h, leaf._p, C.byref(pos), C.byref(cm))
         return pos.value, cm.value
 
-    def gather(self, query, threshold_bp=0, scaled=None, max_rows=None, abund_stats=True):
+    def gather(self, query, threshold_bp=0, scaled=None, max_rows=None, abund_stats=True, downsample=False):
         """Greedy decomposition of `query` against the resident sketches (smh_index_gather): GatherResult(rows, assigned).
         rows: one GatherRecord per round; assigned: uint32 numpy array, the round that consumed each query position (the
         hashes in ascending order) or UNASSIGNED.  threshold_common = ceil(threshold_bp / scaled); scaled defaults to the
         value the query's max_hash stands for.  The integers come from the device; the floats are derived here.  The
         device call leaves a query that lives in HBM where it is; f_unique_weighted, median_abund and std_abund of a query
-        that tracks abundances need those on the host afterwards -- abund_stats=False leaves the three None instead."""
+        that tracks abundances need those on the host afterwards -- abund_stats=False leaves the three None instead.
+        downsample=True: index and query meet at the smaller max_hash first; `scaled` then defaults to what that stands for,
+        `assigned` runs over the positions of the cut query and the fractions are those of the cut query."""
+        if downsample:
+            idx, q = self._meet_sketch(query)
+            return idx.gather(q, threshold_bp, scaled, max_rows, abund_stats)
         if scaled is None:
             mx = query.max_hash
             scaled = scaled_of_max_hash(mx) if mx else 1   # (a num query is refused by the call below)
@@ -141,9 +250,12 @@ class ResidentIndex:
         call(self._L.smh_index_norms2, self._h, out.ctypes.data_as(u64p))
         return out
 
-    def angular(self, query):
+    def angular(self, query, downsample=False):
         """`query` against every node (smh_index_angular_query): AngularResult(dot, cosine, angular), numpy arrays of
         len(self) entries.  A query that lives in HBM stays there."""
+        if downsample:
+            idx, q = self._meet_sketch(query)
+            return idx.angular(q)
         n = len(self)
         dot, cos, ang = np.zeros(n, np.uint64), np.zeros(n, np.float64), np.zeros(n, np.float64)
         f64p = C.POINTER(C.c_double)
@@ -151,10 +263,13 @@ class ResidentIndex:
              ang.ctypes.data_as(f64p))
         return AngularResult(dot, cos, ang)
 
-    def angular_matrix(self, other=None, want=("angular",)):
+    def angular_matrix(self, other=None, want=("angular",), downsample=False):
         """len(self) x len(other) matrix (other=None: the index against itself, symmetric) -> dict name -> array;
         names: dot, cosine, angular (smh_index_angular)."""
         other = self if other is None else other
+        if downsample:
+            a, b = self._meet_index(other)
+            return a.angular_matrix(b, want)
         kinds = {"dot": np.uint64, "cosine": np.float64, "angular": np.float64}
         out = {k: np.zeros((len(self), len(other)), dtype=kinds[k]) for k in want}
 
@@ -166,7 +281,10 @@ class ResidentIndex:
         call(self._L.smh_index_angular, self._h, other._h, p("dot"), p("cosine"), p("angular"))
         return out
 
-    def compare(self, other, want=("jaccard",)):
+    def compare(self, other, want=("jaccard",), downsample=False):
+        if downsample:
+            a, b = self._meet_index(other)
+            return a.compare(b, want)
         n, m = len(self), len(other)
         kinds = {"jaccard": np.float64, "common": np.uint64, "size": np.uint64, "count_common": np.uint64,
                  "containment": np.float64}

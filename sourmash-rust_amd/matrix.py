@@ -122,6 +122,36 @@ def angular_block_dev(row_hashes, row_abunds, row_offsets, col_hashes, col_abund
     return outs
 
 
+def downsample_block_dev(hashes, offsets, max_hash, abunds=None, out_hashes=None, out_abunds=None, stream=None):
+    """The kept prefixes (hashes <= max_hash) of device-resident CSR sketches (smh_downsample_block_dev): hashes uint64/int64,
+    abundances uint32/int32 CUDA tensors, offsets a host array.  Output tensors are allocated with the input's size when not
+    given (their numel is the capacity).  Returns (out_hashes, out_abunds or None, new offsets as a uint64 numpy array); the
+    first new_offsets[-1] elements of the outputs are valid."""
+    import torch
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = off.size - 1
+    dev = hashes.device
+    if out_hashes is None:
+        out_hashes = torch.empty(max(int(off[-1] - off[0]), 1), dtype=hashes.dtype, device=dev)
+    if abunds is not None and out_abunds is None:
+        out_abunds = torch.empty(out_hashes.numel(), dtype=abunds.dtype, device=dev)
+    cap = out_hashes.numel() if abunds is None else min(out_hashes.numel(), out_abunds.numel())
+    new_off = np.zeros(n + 1, dtype=np.uint64)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    call(lib().smh_downsample_block_dev, C.c_void_p(hashes.data_ptr()), C.c_void_p(abunds.data_ptr() if abunds is not None else 0),
+         off.ctypes.data_as(u64p), n, int(max_hash), C.c_void_p(out_hashes.data_ptr()),
+         C.c_void_p(out_abunds.data_ptr() if abunds is not None else 0), cap, new_off.ctypes.data_as(u64p), C.c_void_p(stream))
+    return out_hashes, (out_abunds if abunds is not None else None), new_off
+
+
+def downsample_geometry():
+    """(output elements per workgroup of the copy kernel, its threads)"""
+    t, th = C.c_uint32(), C.c_uint32()
+    lib().smh_downsample_geometry(C.byref(t), C.byref(th))
+    return t.value, th.value
+
+
 def angular_last_stats():
     """(pairs walked, pairs given zeros without a walk) of the last angular call"""
     a, b = C.c_uint64(), C.c_uint64()

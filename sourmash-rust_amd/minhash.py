@@ -212,6 +212,30 @@ class KmerMinHash:
              C.c_void_p(abunds_t.data_ptr() if abunds_t is not None else 0), st.ctypes.data_as(u64p), ln.ctypes.data_as(u64p),
              st.size, C.c_void_p(stream or 0))
 
+    # --- downsampling (additive ABI smh_kmerminhash_downsample_*; the rules are in include/sourmash_amd.h)
+    @property
+    def scaled(self):
+        """the `scaled` this sketch's max_hash stands for; None for a sketch without max_hash"""
+        from .index import scaled_of_max_hash
+        mx = self.max_hash
+        return scaled_of_max_hash(mx) if mx else None
+
+    def downsample_max_hash(self, max_hash):
+        """A new sketch holding the hashes <= max_hash (and their abundances).  A state that lives in HBM is cut there and
+        stays there, for this sketch and for the new one."""
+        return self._wrap(call(self._L.smh_kmerminhash_downsample_max_hash, self._p, int(max_hash)))
+
+    def downsample_scaled(self, scaled):
+        from .index import max_hash_of_scaled
+        return self.downsample_max_hash(max_hash_of_scaled(scaled))
+
+    def downsample_num(self, num):
+        """A new num sketch holding the first `num` hashes (host only)."""
+        return self._wrap(call(self._L.smh_kmerminhash_downsample_num, self._p, int(num)))
+
+    def _wrap(self, ptr):
+        return KmerMinHash(0, 0, _ptr=ptr)
+
     def merge(self, other): call(self._L.kmerminhash_merge, self._p, other._p)
     def add_from(self, other): call(self._L.kmerminhash_add_from, self._p, other._p)
 

@@ -95,6 +95,20 @@ extern "C" {
     fn smh_amino_geometry(total_len: u64, win: u32, tile_positions: *mut u32, run: *mut u32);
 }
 
+// Downsampling (include/sourmash_amd.h); link-checked by tests/c_downsample_symbols.c.
+#[allow(dead_code)]
+extern "C" {
+    fn smh_kmerminhash_downsample_max_hash(ptr: *const RawKmerMinHash, max_hash: u64) -> *mut RawKmerMinHash;
+    fn smh_kmerminhash_downsample_num(ptr: *const RawKmerMinHash, num: u32) -> *mut RawKmerMinHash;
+    fn smh_index_downsample(index: *mut c_void, max_hash: u64) -> *mut c_void;
+    fn smh_index_max_hash_range(index: *const c_void, lo: *mut u64, hi: *mut u64) -> i32;
+    fn smh_downsample_block_dev(
+        hashes_dev: *const u64, abunds_dev: *const u32, offsets: *const u64, n: u32, max_hash: u64, out_hashes_dev: *mut u64,
+        out_abunds_dev: *mut u32, capacity: u64, out_offsets: *mut u64, stream: *mut c_void,
+    ) -> i32;
+    fn smh_downsample_geometry(tile_elems: *mut u32, threads: *mut u32);
+}
+
 /// Error of the library's thread-local slot (codes of reference `src/errors.rs:28-50`).  Stands where
 /// the reference has `failure::Error`.
 #[derive(Debug, Clone, PartialEq)]
@@ -273,6 +287,37 @@ impl KmerMinHash {
     pub fn add_proteins(&mut self, seq: &[u8], offsets: &[u64]) -> Result<(), Error> {
         let n = offsets.len().saturating_sub(1) as u32;
         self.mutate(|h| unsafe { smh_add_proteins(h, seq.as_ptr() as *const c_char, offsets.as_ptr(), n) })
+    }
+
+    /// The sketch the library hands back for a cut of `self` (null: the error slot says why).
+    fn cut_with<F: FnOnce(*const RawKmerMinHash) -> *mut RawKmerMinHash>(&self, f: F) -> Result<KmerMinHash, Error> {
+        let h = self.to_handle();
+        unsafe { sourmash_err_clear() };
+        let p = f(h.0);
+        if p.is_null() {
+            return Err(take_error());
+        }
+        let cut = Handle(p);
+        let mut out = KmerMinHash {
+            num: self.num, ksize: self.ksize, is_protein: self.is_protein, molecule: self.molecule, seed: self.seed,
+            max_hash: self.max_hash, mins: Vec::new(), abunds: if self.abunds.is_some() { Some(Vec::new()) } else { None },
+        };
+        out.read_back(&cut);
+        Ok(out)
+    }
+
+    /// A scaled sketch cut at a smaller `max_hash` (`smh_kmerminhash_downsample_max_hash`): the hashes `<= max_hash`.
+    pub fn downsample_max_hash(&self, max_hash: u64) -> Result<KmerMinHash, Error> {
+        let mut out = self.cut_with(|h| unsafe { smh_kmerminhash_downsample_max_hash(h, max_hash) })?;
+        out.max_hash = max_hash;
+        Ok(out)
+    }
+
+    /// A num sketch cut to its first `num` hashes (`smh_kmerminhash_downsample_num`).
+    pub fn downsample_num(&self, num: u32) -> Result<KmerMinHash, Error> {
+        let mut out = self.cut_with(|h| unsafe { smh_kmerminhash_downsample_num(h, num) })?;
+        out.num = num;
+        Ok(out)
     }
 
     /// reference `src/lib.rs:307-403`
