@@ -187,6 +187,15 @@ hipStream_t Device::user_stream(void* given) {
   return stream_;
 }
 
+uint32_t* Device::tile_counter(hipStream_t s) {
+  std::lock_guard<std::recursive_mutex> lock(mu_);
+  tile_counters_.ensure(kTileCounters * sizeof(uint32_t));   // (allocated once: the size never changes)
+  uint32_t* w = tile_counters_.as<uint32_t>() + tile_counter_next_;
+  tile_counter_next_ = (tile_counter_next_ + 1) % kTileCounters;
+  HIP_CHECK(hipMemsetAsync(w, 0, sizeof(uint32_t), s));
+  return w;
+}
+
 Device& Device::get() {
   static Device* d = new Device();  // leaked on purpose: no teardown-order games with the HIP runtime
   // a different host thread may have another current device

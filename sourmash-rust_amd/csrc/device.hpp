@@ -108,6 +108,15 @@ class Device {
   DeviceBuffer scratch;
   // per-tile record numbers of the running sketch launch (guarded by mutex(); see k_tile_records)
   DeviceBuffer tile_rec;
+  // A zeroed 32-bit word for one launch of a tiled sketch kernel that hands its tiles out dynamically (the kernel's
+  // workgroups atomicAdd it for their next tile).  The zeroing is queued on `s`, in front of the launch.  Words come
+  // from a ring of kTileCounters: a word is zeroed again only behind kTileCounters - 1 later launches.  Reuse is safe
+  // because every caller holds mutex() from here until its launch is queued and every sketching entry point waits for
+  // its stream before it returns, so the launches that can be in flight together are those of ONE call, all on that
+  // call's stream -- where zeroing, kernel and the next zeroing run in that order; the ring keeps launches apart even
+  // if a future caller were to spread a call's launches over several streams.
+  static constexpr uint32_t kTileCounters = 64;
+  uint32_t* tile_counter(hipStream_t s);
 
   // HIP-event timing of named kernels (enabled by smh_profile_enable)
   void profile_enable(bool on);
@@ -130,6 +139,8 @@ class Device {
   hipStream_t open_stream_ = nullptr;
   bool open_ = false;
   std::recursive_mutex mu_;
+  DeviceBuffer tile_counters_;
+  uint32_t tile_counter_next_ = 0;
   bool profiling_ = false;
   struct Pending { std::string name; hipEvent_t a, b; };
   std::vector<Pending> pending_;

@@ -433,9 +433,10 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint
 // on its own dependent murmur chains in a third of its wave cycles), and the hot path reads one LDS dword per
 // 16 bases and decodes nothing.  Dirty dwords end the lane's window of clean groups like a record boundary does; the group
 // then re-reads its four bytes from global memory (rare) and takes the per-base path with the same conditions as ever.
+constexpr int kDnaCtlDwords = 8;   // the LDS header of k_dna_rolling (32 bytes: the staged hashes behind it stay 16-byte aligned)
 template <int KT, int THREADS, int HB, int L, bool PR = false, bool PK = false, int MINW = (PK ? 8 : 4)>
 __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashParams hp, CandSink sink,
-                                                                     int logR, uint32_t stage_cap) {
+                                                                     int logR, uint32_t stage_cap, uint32_t* tile_ctr) {
   // LDS: static: the product tables (6.8 KiB, folded 11.3 KiB, folded with the cross term 12.8 KiB; a compile-time address, so a table read is one
   // ds_read with the table's base as its immediate offset); dynamic: [staged candidates: count,
   // hashes, positions][sequence tile]
@@ -447,8 +448,8 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
   constexpr bool CROSS = FOLD && !PR;
   __shared__ __attribute__((aligned(16))) uint32_t lut[CROSS ? kLutDwordsCross : (FOLD ? kLutDwordsFold : kLutDwords)];
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  uint32_t* st_ctl = smem;                                    // [0] = count, [2..3] = flush base
-  uint64_t* st_hash = reinterpret_cast<uint64_t*>(st_ctl + 4);
+  uint32_t* st_ctl = smem;                                    // [0] = count, [1] = dirty tile, [2..3] = flush base, [4] = next tile
+  uint64_t* st_hash = reinterpret_cast<uint64_t*>(st_ctl + kDnaCtlDwords);
   uint64_t* st_pos = st_hash + stage_cap;
   uint32_t* tile = reinterpret_cast<uint32_t*>(st_pos + (sink.pos ? stage_cap : 0));
   const Stage stage{st_ctl, st_hash, st_pos, stage_cap};
@@ -529,7 +530,16 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
   const uint32_t nsteps = (R + (uint32_t)K - 1 + 3) & ~3u;  // bases walked per lane, multiple of 4
   const uint32_t warm_end = K > 4 ? ((uint32_t)(K - 1) & ~3u) : 0u;   // groups [0, warm_end) end before any window is complete
 
-  for (uint64_t tix = blockIdx.x; tix < ntiles; tix += gridDim.x) {
+  // Tiles.  The launch has as many workgroups as are resident at once (resident_workgroups); a workgroup's first tile is
+  // its own number.  tile_ctr == null (no more tiles than workgroups): that is all.  Otherwise the next tile is
+  // gridDim.x + atomicAdd(tile_ctr, 1) -- the word is zero when the kernel starts -- so that whichever workgroup is done
+  // first takes the next tile and the kernel's tail is one tile long, wherever the dispatcher placed the workgroups and
+  // however slow single tiles (dirty dwords, record edges) or CUs are.  Lane 0 asks for it behind the staging barrier, so
+  // that the round trip runs under the hashing loop, and leaves it in the LDS header; everybody reads it behind the first
+  // barrier of stage_flush and lane 0 writes the word again only behind the next tile's staging barrier.  No workgroup
+  // ever waits for another one.  (Not in the per-record kernels, which are never given a counter: held to 64 registers
+  // they spill, and the second way round the loop made some of them spill more.)
+  for (uint64_t tix = blockIdx.x; tix < ntiles;) {
     const uint64_t T0 = hp.range_lo + tix * TILE;
     const uint64_t thr = hp.thr;
     const uint32_t thr_hi1 = open_thr(hp.thr);
@@ -599,6 +609,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
       }
     }
     __syncthreads();
+    if (!PR && tile_ctr && tid == 0) st_ctl[4] = atomicAdd(tile_ctr, 1u);   // the next tile (see above)
 
     const uint64_t p0 = T0 + ((uint64_t)tid << logR);  // my first k-mer start position
     if (p0 < hp.range_hi) {
@@ -914,6 +925,9 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
 
     // ---- flush the staged candidates: ONE global atomic per tile, coalesced stores
     stage_flush(stage, sink, tid, THREADS);
+    // (uniform: read into a scalar register, or everything derived from the tile number would move to vector registers)
+    if (!PR && tile_ctr) tix = (uint64_t)gridDim.x + (uint32_t)__builtin_amdgcn_readfirstlane((int)st_ctl[4]);
+    else tix += gridDim.x;
   }
 }
 
@@ -2006,13 +2020,60 @@ static DnaCfg dna_cfg() {
   return cfg;
 }
 
+// Workgroups of `kernel` that the chip holds at once: what the runtime's occupancy query says fits one CU with `threads`
+// lanes and `lds` bytes of dynamic LDS (registers and static LDS are the kernel's own), times the CUs.  More workgroups
+// than that run in rounds; exactly that many, taking their tiles dynamically, keep every CU busy to the last tile.  Asked
+// once per kernel and LDS size, on the host.
+template <class Kernel>
+static uint64_t resident_workgroups(Kernel kernel, int threads, size_t lds, Device& dev) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, size_t>, int> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto key = std::make_pair(reinterpret_cast<const void*>(kernel), lds);
+  auto it = cache.find(key);
+  if (it == cache.end()) {
+    int per_cu = 0;
+    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds));
+    if (per_cu < 1) throw_internal("a sketch kernel does not fit a compute unit (occupancy query)");
+    it = cache.emplace(key, per_cu).first;
+  }
+  return (uint64_t)it->second * (uint64_t)dev.cu_count();
+}
+
+// One launch of a k_dna_rolling instantiation over `ntiles` tiles: the grid is what is resident at once; with more tiles
+// than that the workgroups take their further tiles from a counter word (Device::tile_counter, zeroed in stream order in
+// front of the timed launch).  Device::count records which way a launch went (dna_tiles_dynamic / dna_tiles_static).
+// The per-record kernels have no dynamic path (see the kernel's tile loop) and keep the launch they had: 8 workgroups per
+// CU, four of them resident, tiles split statically -- measured on the bench kernel, a static split over just the resident
+// workgroups is SLOWER than over more, smaller shares (profiles/r09_dna_schedule.json, grid_sweep).
+template <class Kernel>
+static void launch_rolling_tiles(Kernel kernel, int threads, bool per_record, const SeqBatch& b, const HashParams& p, const CandSink& sink,
+                                 uint64_t ntiles, size_t lds, int logR, uint32_t stage_cap, Device& dev, hipStream_t s) {
+  uint64_t grid = per_record ? (uint64_t)dev.cu_count() * 8 : resident_workgroups(kernel, threads, lds, dev);
+  bool dynamic = !per_record && ntiles > grid && ntiles < (1ull << 31);
+#ifdef SMH_EXPERIMENTS
+  // "n": n workgroups per CU, tiles split statically (the grid before the residency query was cu_count * 8); "static": the
+  // resident grid with the static split
+  if (const char* e = per_record ? nullptr : std::getenv("SOURMASH_AMD_DNA_GRID")) {
+    if (std::atoi(e) > 0) grid = (uint64_t)dev.cu_count() * (uint64_t)std::atoi(e);
+    dynamic = false;
+  }
+#endif
+  if (grid > ntiles) grid = ntiles;
+  uint32_t* ctr = dynamic ? dev.tile_counter(s) : nullptr;
+  dev.count(dynamic ? "dna_tiles_dynamic" : "dna_tiles_static");
+  dev.prof_begin(s);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, s, b, p, sink, logR, stage_cap, ctr);
+}
+
 template <int KT, int L>
-static void launch_rolling(const SeqBatch& b, const HashParams& p, const CandSink& sink, int grid, size_t lds,
-                           int logR, uint32_t stage_cap, const DnaCfg& c, hipStream_t s) {
-#define SMH_LAUNCH(T, H) hipLaunchKernelGGL((k_dna_rolling<KT, T, H, L>), dim3(grid), dim3(T), lds, s, b, p, sink, logR, stage_cap)
+static void launch_rolling(const SeqBatch& b, const HashParams& p, const CandSink& sink, uint64_t ntiles, size_t lds,
+                           int logR, uint32_t stage_cap, const DnaCfg& c, Device& dev, hipStream_t s) {
+#define SMH_LAUNCH_K(T, ...) launch_rolling_tiles(k_dna_rolling<KT, T, __VA_ARGS__>, T, p.thr_rec != nullptr, b, p, sink, ntiles, lds, logR, stage_cap, dev, s)
+#define SMH_LAUNCH(T, H) SMH_LAUNCH_K(T, H, L)
   if (p.thr_rec) {   // per-record thresholds: default geometry only
-    if (c.packed) hipLaunchKernelGGL((k_dna_rolling<KT, 512, 2, L, true, true>), dim3(grid), dim3(512), lds, s, b, p, sink, logR, stage_cap);
-    else hipLaunchKernelGGL((k_dna_rolling<KT, 512, 2, L, true>), dim3(grid), dim3(512), lds, s, b, p, sink, logR, stage_cap);
+    if (c.packed) SMH_LAUNCH_K(512, 2, L, true, true);
+    else SMH_LAUNCH_K(512, 2, L, true);
     return;
   }
   if (c.packed) {    // the product geometry: 512 lanes, two hashes per block, the tile packed to two bits per base
@@ -2020,7 +2081,7 @@ static void launch_rolling(const SeqBatch& b, const HashParams& p, const CandSin
     if (const char* e = std::getenv("SOURMASH_AMD_DNA_PKV")) {     // "minw,hb" of the packed kernel (A/B)
       int mw = 0, hb = 0;
       if (sscanf(e, "%d,%d", &mw, &hb) == 2) {
-#define SMH_PKV(M_, H_) if (mw == M_ && hb == H_) { hipLaunchKernelGGL((k_dna_rolling<KT, 512, H_, L, false, true, M_>), dim3(grid), dim3(512), lds, s, b, p, sink, logR, stage_cap); return; }
+#define SMH_PKV(M_, H_) if (mw == M_ && hb == H_) { SMH_LAUNCH_K(512, H_, L, false, true, M_); return; }
         SMH_PKV(8, 1) SMH_PKV(7, 1) SMH_PKV(6, 1) SMH_PKV(5, 1) SMH_PKV(4, 1) SMH_PKV(8, 2) SMH_PKV(6, 2) SMH_PKV(5, 2) SMH_PKV(4, 2) SMH_PKV(8, 4) SMH_PKV(6, 4)
 #undef SMH_PKV
       }
@@ -2028,7 +2089,7 @@ static void launch_rolling(const SeqBatch& b, const HashParams& p, const CandSin
 #endif
     // (six waves per SIMD, one hash per block: 80 vector registers keep the scalar values out of vector lanes; 27.2 against
     // 27.6 ms per 10 GB with eight waves and two hashes per block, profiles/r04_pmc_dna_rolling.json "variants_measured")
-    hipLaunchKernelGGL((k_dna_rolling<KT, 512, 1, L, false, true, 6>), dim3(grid), dim3(512), lds, s, b, p, sink, logR, stage_cap);
+    SMH_LAUNCH_K(512, 1, L, false, true, 6);
     return;
   }
 #ifdef SMH_EXPERIMENTS
@@ -2038,6 +2099,7 @@ static void launch_rolling(const SeqBatch& b, const HashParams& p, const CandSin
   SMH_LAUNCH(512, 2);
 #endif
 #undef SMH_LAUNCH
+#undef SMH_LAUNCH_K
 }
 
 // the batch with its per-tile record table (k_tile_records) for a launch of `ntiles` tiles from position `base`
@@ -2066,8 +2128,6 @@ void launch_dna_hash(const SeqBatch& b_in, const HashParams& p, const CandSink& 
     const uint64_t tile = (uint64_t)c.threads << logR;
     const uint64_t ntiles = (span + tile - 1) / tile;
     const SeqBatch b = with_tile_records(b_in, 0, p.range_lo, tile, ntiles, dev, s);
-    dev.prof_begin(s);
-    int grid = (int)(ntiles < (uint64_t)dev.cu_count() * 8 ? ntiles : (uint64_t)dev.cu_count() * 8);
     const int limbs = p.ksize <= 32 ? 2 : (p.ksize <= 64 ? 4 : 8);
     const uint32_t x_bytes = (uint32_t)tile + 16 * limbs + 96;
     // LDS stage for the survivors of one tile: twice the expectation under a uniform hash, within
@@ -2076,20 +2136,21 @@ void launch_dna_hash(const SeqBatch& b_in, const HashParams& p, const CandSink& 
     long double expect = (long double)tile * (((long double)thr + 1.0L) / 18446744073709551616.0L);
     uint32_t stage_cap = expect * 2.0L + 64.0L > 2048.0L ? 2048u : (uint32_t)(expect * 2.0L + 64.0L);
     if (stage_cap < 128) stage_cap = 128;
-    size_t lds = 16 + (size_t)stage_cap * 8 * (sink.pos ? 2 : 1) + x_bytes +   // dynamic part; the tables are static LDS
+    size_t lds = 4 * kDnaCtlDwords + (size_t)stage_cap * 8 * (sink.pos ? 2 : 1) + x_bytes +   // dynamic part; the tables are static LDS
                  4 * ((x_bytes >> logR) + 2);
     if (c.packed) {
       // two bits per base + a pad dword per run + a dirty bit per source dword (the kernel's nchunks_cap)
       const uint32_t ncap = (15u + (uint32_t)tile + 16u * (uint32_t)limbs + 8u + 15u + 32u) >> 4;
-      lds = 16 + (size_t)stage_cap * 8 * (sink.pos ? 2 : 1) + 4 * (size_t)(ncap + (ncap >> (logR - 4)) + 2) + 4 * (size_t)((ncap >> 3) + 8);
+      lds = 4 * kDnaCtlDwords + (size_t)stage_cap * 8 * (sink.pos ? 2 : 1) + 4 * (size_t)(ncap + (ncap >> (logR - 4)) + 2) + 4 * (size_t)((ncap >> 3) + 8);
     }
-    // 8 workgroups per CU may be resident with the packed tile: keep a few tiles per workgroup
-    if (p.ksize == 31) launch_rolling<31, 2>(b, p, sink, grid, lds, logR, stage_cap, c, s);
-    else if (p.ksize == 21) launch_rolling<21, 2>(b, p, sink, grid, lds, logR, stage_cap, c, s);
-    else if (p.ksize == 51) launch_rolling<51, 4>(b, p, sink, grid, lds, logR, stage_cap, c, s);
-    else if (p.ksize <= 32) launch_rolling<0, 2>(b, p, sink, grid, lds, logR, stage_cap, c, s);
-    else if (p.ksize <= 64) launch_rolling<0, 4>(b, p, sink, grid, lds, logR, stage_cap, c, s);
-    else launch_rolling<0, 8>(b, p, sink, grid, lds, logR, stage_cap, c, s);
+    // (the grid and how the tiles are handed out: launch_rolling_tiles.  The bench kernel -- k = 31, packed tile, 71 vector
+    // registers, ~35 KB of LDS -- has three 512-lane workgroups per CU resident.)
+    if (p.ksize == 31) launch_rolling<31, 2>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);
+    else if (p.ksize == 21) launch_rolling<21, 2>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);
+    else if (p.ksize == 51) launch_rolling<51, 4>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);
+    else if (p.ksize <= 32) launch_rolling<0, 2>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);
+    else if (p.ksize <= 64) launch_rolling<0, 4>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);
+    else launch_rolling<0, 8>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);
     HIP_CHECK(hipGetLastError());
     dev.prof_end("dna_rolling", s);
   } else {
