@@ -399,6 +399,60 @@ int smh_downsample_block_dev(const uint64_t *hashes_dev, const uint32_t *abunds_
                              uint64_t *out_offsets, void *stream);
 void smh_downsample_geometry(uint32_t *tile_elems, uint32_t *threads);
 
+/* Matching records: which k-mers of every record of a batch a resident index knows, and which node each record belongs
+ * to -- without a sketch per record and without an N x M matrix.  The reference crate has no counterpart, so the rules are
+ * fixed here -- DESIGN.md 3.13, restated in tests/match_restatement.py.  DNA only: a protein, dayhoff or hp index and
+ * amino-acid input are not served.
+ *   The index     must be uniform, DNA, every node a scaled sketch, with one max_hash; ksize, seed and max_hash are those of
+ *                 node 0.  Anything else -- and an index without nodes -- is refused with SOURMASH_ERROR_CODE_MSG and a
+ *                 message naming the node and the values, as smh_index_downsample refuses.  An index that
+ *                 smh_index_downsample made is an index like any other.
+ *   A window      of record r is a start position p with p + ksize <= end of r.  A window holding a byte outside ACGTacgt is
+ *                 skipped (force = true semantics; never an error here).  A window never spans two records.
+ *   Sampled       a window is sampled when the hash h of its canonical k-mer satisfies h <= max_hash (unsigned, inclusive).
+ *   Hit           a sampled window is a hit when h is held by at least one node of the index.
+ *   SmhMatchRow   per record: windows = sampled windows; distinct = distinct sampled hashes; hit_windows = sampled windows
+ *                 that are hits; hit_distinct = distinct hit hashes; best = the node holding the most of the record's
+ *                 distinct hit hashes, the lowest index on ties, 0xffffffff when hit_distinct == 0; best_common = that count
+ *                 (by construction count_common(sketch(record), node best)).
+ *   The hit list  optional: a CSR of every record's distinct hit hashes, ascending.  hit_offsets (caller's, n + 1 entries)
+ *                 receives the offsets; *hit_hashes a malloc'ed array of *n_hits hashes (at least one element is allocated;
+ *                 free it with free(), as smh_intersection's common_out).  Pass all three or none (NULL).
+ * Every output is an integer: parity is equality.
+ *
+ * smh_index_match_sequences      records in host memory: seq + offsets[0 .. n] (record r = seq[offsets[r] .. offsets[r + 1])).
+ * smh_index_match_sequences_dev  the batch in device memory (total_len bytes), offsets on the host; stream: the caller's.
+ * smh_index_match_records        the records of an SmhRecords handle (they stay in HBM).
+ *                                rows: room for n records.  The first call builds the index's hash directory (the sorted
+ *                                distinct hashes of all nodes and the nodes holding each; fewer than 2^31 resident hashes)
+ *                                and keeps it with the index; smh_index_free and smh_release_workspace give it back.
+ * smh_match_geometry             the sizes at which the kernels' branches change: the owner pairs (hit hashes x the nodes
+ *                                holding them) of one record up to which the tally counts in LDS -- a record with more goes
+ *                                through per-node counters in global memory --, the threads the tally gives a record, and the
+ *                                hashes of the directory the probe samples into LDS (a directory up to that size is searched
+ *                                in LDS alone).
+ * smh_match_set_pair_budget      bounds the work space that grows with the batch: a batch is cut into folds at record
+ * smh_match_pair_budget          boundaries so that a fold's records plus its expected sampled windows stay within the budget
+ *                                (one record always makes a fold: no record is split; a record that alone would leave 2^31
+ *                                candidates is refused, MSG), and the dense regime of the tally serves as many records per
+ *                                round as the budget holds (record, node) counters for (one at least).  Results never depend
+ *                                on it.  0 restores the default, 2^26: a memory cap, not a measured optimum.  Process-wide.
+ * Timers under smh_profile_get: "match_probe", "match_tally"; event counters: "match_directory_built", "match_fold",
+ * "match_dense_round". */
+typedef struct SmhMatchRow {
+  uint32_t windows, distinct, hit_windows, hit_distinct, best, best_common;
+} SmhMatchRow;
+int smh_index_match_sequences(SmhIndex *index, const char *seq, const uint64_t *offsets, uint32_t n_records, SmhMatchRow *rows,
+                              uint64_t *hit_offsets, uint64_t **hit_hashes, uint64_t *n_hits);
+int smh_index_match_sequences_dev(SmhIndex *index, const void *seq_dev, uint64_t total_len, const uint64_t *offsets,
+                                  uint32_t n_records, SmhMatchRow *rows, uint64_t *hit_offsets, uint64_t **hit_hashes,
+                                  uint64_t *n_hits, void *stream);
+int smh_index_match_records(SmhIndex *index, const SmhRecords *records, SmhMatchRow *rows, uint64_t *hit_offsets,
+                            uint64_t **hit_hashes, uint64_t *n_hits);
+void smh_match_geometry(uint32_t *lds_pairs, uint32_t *threads_per_record, uint32_t *probe_samples);
+void smh_match_set_pair_budget(uint64_t pairs);
+uint64_t smh_match_pair_budget(void);
+
 /* deterministic synthetic DNA of SURVEY.md 8d written to device memory (benchmark input) */
 int smh_synth_dna_dev(void *out_dev, uint64_t start, uint64_t len, uint64_t seed, uint64_t n_every,
                       void *stream);
@@ -530,7 +584,8 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * "compare_pair", "compare_fill", "compare_comp", "compare_tiled" (the plain and the pipelined tiled kernels of one call together),
  * "sbt_bins", "sbt_nodes", "sbt_leaves", "sbt_build", "parse_scan" (tile summaries and their scan), "parse_compact",
  * "gather_hits" (the membership pass), "gather_invert" (degree scan + inverted lists), "gather_rounds" (one entry per batch
- * of smh_gather_rounds_per_sync() rounds), "angular_block" (the angular similarity's block kernel). */
+ * of smh_gather_rounds_per_sync() rounds), "angular_block" (the angular similarity's block kernel), "match_probe" (the runs of a
+ * fold against the hash directory), "match_tally" (the per-record tally: its LDS launch, and one entry per dense round). */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -35,6 +35,11 @@ class SmhGatherRow(C.Structure):
                 ("size_match", C.c_uint32), ("abund_sum", C.c_uint64)]
 
 
+class SmhMatchRow(C.Structure):
+    _fields_ = [("windows", C.c_uint32), ("distinct", C.c_uint32), ("hit_windows", C.c_uint32), ("hit_distinct", C.c_uint32),
+                ("best", C.c_uint32), ("best_common", C.c_uint32)]
+
+
 def build(force=False):
     """Compile the HIP/C++ sources in-tree (hipcc --offload-arch=gfx950)."""
     src = os.path.join(HERE, "csrc")
@@ -171,6 +176,13 @@ _SIGS = {
     "smh_downsample_block_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                            u64p, C.c_void_p]),
     "smh_downsample_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "smh_index_match_sequences": (C.c_int, [C.c_void_p, C.c_char_p, u64p, C.c_uint32, C.c_void_p, u64p, C.POINTER(u64p), u64p]),
+    "smh_index_match_sequences_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint32, C.c_void_p, u64p, C.POINTER(u64p), u64p,
+                                                C.c_void_p]),
+    "smh_index_match_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.POINTER(u64p), u64p]),
+    "smh_match_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "smh_match_set_pair_budget": (None, [C.c_uint64]),
+    "smh_match_pair_budget": (C.c_uint64, []),
     "smh_release_workspace": (C.c_int, []),
     "smh_pool_set_limit": (None, [C.c_uint64]),
     "smh_pool_bytes": (C.c_uint64, []),

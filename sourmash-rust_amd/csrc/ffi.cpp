@@ -806,6 +806,77 @@ int smh_downsample_block_dev(const uint64_t* hashes_dev, const uint32_t* abunds_
 bool smh_index_all_scaled(const SmhIndex* index) { return index && index->all_scaled; }
 void smh_downsample_geometry(uint32_t* tile_elems, uint32_t* threads) { smh::downsample_geometry(tile_elems, threads); }
 
+// ------------------------------------------------------------------ matching records (match.cpp)
+
+static_assert(sizeof(SmhMatchRow) == 24 && sizeof(smh::MatchRow) == 24, "SmhMatchRow is 24 bytes");
+static_assert(offsetof(SmhMatchRow, best) == 16 && offsetof(smh::MatchRow, best) == 16, "SmhMatchRow layout");
+
+namespace {
+// the checks every route shares, the call, and the hit list handed out the way smh_intersection hands out common_out
+void match_call(SmhIndex* index, const uint8_t* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n, SmhMatchRow* rows,
+                uint64_t* hit_offsets, uint64_t** hit_hashes, uint64_t* n_hits, hipStream_t s) {
+  const bool want = hit_offsets || hit_hashes || n_hits;
+  std::vector<uint64_t> hits;
+  index->match(seq_dev, total_len, offsets, n, reinterpret_cast<smh::MatchRow*>(rows), want ? hit_offsets : nullptr, want ? &hits : nullptr, s);
+  if (!want) return;
+  uint64_t* out = (uint64_t*)malloc((hits.empty() ? 1 : hits.size()) * sizeof(uint64_t));
+  if (!out) smh::throw_internal("out of memory");
+  if (!hits.empty()) memcpy(out, hits.data(), hits.size() * sizeof(uint64_t));
+  *hit_hashes = out; *n_hits = hits.size();
+}
+void match_require(SmhIndex* index, const uint64_t* offsets, uint32_t n, SmhMatchRow* rows, uint64_t* hit_offsets, uint64_t** hit_hashes,
+                   uint64_t* n_hits) {
+  require(index, "index");
+  if (n) { require(offsets, "offsets"); require(rows, "rows"); }
+  if (hit_offsets || hit_hashes || n_hits) { require(hit_offsets, "hit_offsets"); require(hit_hashes, "hit_hashes"); require(n_hits, "n_hits"); }
+  index->check_matchable();
+}
+}  // namespace
+
+int smh_index_match_sequences(SmhIndex* index, const char* seq, const uint64_t* offsets, uint32_t n_records, SmhMatchRow* rows,
+                              uint64_t* hit_offsets, uint64_t** hit_hashes, uint64_t* n_hits) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();   // first: without a device the call says so, whatever it was handed
+    match_require(index, offsets, n_records, rows, hit_offsets, hit_hashes, n_hits);
+    auto& E = smh::Engine::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    const uint64_t base = n_records ? offsets[0] : 0, total = n_records ? offsets[n_records] - base : 0;
+    if (n_records && offsets[n_records] < base) throw Error(smh::kMsg, "match: offsets must ascend");
+    if (total) require(seq, "seq");
+    std::vector<uint64_t> rel((size_t)n_records + 1, 0);
+    for (uint32_t i = 0; n_records && i <= n_records; i++) rel[i] = offsets[i] - base;
+    E.seqbuf.ensure(total + 64);
+    if (total) HIP_CHECK(hipMemcpyAsync(E.seqbuf.ptr, seq + base, total, hipMemcpyHostToDevice, dev.stream()));
+    match_call(index, E.seqbuf.as<uint8_t>(), total, rel.data(), n_records, rows, hit_offsets, hit_hashes, n_hits, dev.stream());
+  });
+}
+
+int smh_index_match_sequences_dev(SmhIndex* index, const void* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n_records,
+                                  SmhMatchRow* rows, uint64_t* hit_offsets, uint64_t** hit_hashes, uint64_t* n_hits, void* stream) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    match_require(index, offsets, n_records, rows, hit_offsets, hit_hashes, n_hits);
+    if (total_len) require(seq_dev, "seq_dev");
+    match_call(index, (const uint8_t*)seq_dev, total_len, offsets, n_records, rows, hit_offsets, hit_hashes, n_hits, dev.user_stream(stream));
+  });
+}
+
+int smh_index_match_records(SmhIndex* index, const SmhRecords* r, SmhMatchRow* rows, uint64_t* hit_offsets, uint64_t** hit_hashes,
+                            uint64_t* n_hits) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    require(r, "records");
+    match_require(index, r->offsets, r->n, rows, hit_offsets, hit_hashes, n_hits);
+    match_call(index, r->seq_dev(), r->total, r->offsets, r->n, rows, hit_offsets, hit_hashes, n_hits, dev.user_stream(nullptr));
+  });
+}
+
+void smh_match_geometry(uint32_t* lds_pairs, uint32_t* threads_per_record, uint32_t* probe_samples) {
+  smh::match_geometry(lds_pairs, threads_per_record, probe_samples);
+}
+void smh_match_set_pair_budget(uint64_t pairs) { smh::g_match_pair_budget = pairs ? pairs : smh::kMatchPairBudget; }
+uint64_t smh_match_pair_budget(void) { return smh::g_match_pair_budget; }
+
 // ---- a scaled sketch's state as device arrays: the cross-rank union of partial sketches ----
 int smh_sketch_export_dev(KmerMinHash* ptr, uint64_t* mins_dev, uint64_t* abunds_dev, uint64_t capacity, uint64_t* n_out, void* stream) {
   return pad_code([&] {

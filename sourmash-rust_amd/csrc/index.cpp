@@ -123,12 +123,13 @@ void ResidentIndex::max_hash_range(uint64_t* lo, uint64_t* hi) const {
 ResidentIndex::~ResidentIndex() {
   { std::lock_guard<std::mutex> g(registry_mu()); registry().erase(this); }
   drop_dict();
+  drop_match_dir();
 }
 
 void ResidentIndex::drop_all_dictionaries() {
   std::lock_guard<std::recursive_mutex> lock(Device::get().mutex());
   std::lock_guard<std::mutex> g(registry_mu());
-  for (ResidentIndex* i : registry()) i->drop_dict();
+  for (ResidentIndex* i : registry()) { i->drop_dict(); i->drop_match_dir(); }
 }
 
 void ResidentIndex::check_sketch(const KmerMinHash& mh, bool sketch_is_receiver) const {

@@ -1,5 +1,6 @@
 // index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
-// similarity on abundances (angular.cpp).  The C boundary (ffi.cpp) only checks pointers and calls in here.
+// similarity on abundances (angular.cpp), matching records (match.cpp).  The C boundary (ffi.cpp) only checks pointers and
+// calls in here.
 #pragma once
 #include "minhash.hpp"
 
@@ -19,6 +20,9 @@ struct ResidentIndex {
   // the index with itself and kept: later ones skip the pre-pass (the nodes of an index never change)
   CollectionDict* dict = nullptr;
   uint32_t dict_split = 0;      // the frequent-hash setting the dictionary was built under
+  // the hash directory (match.cpp): the sorted distinct hashes of all nodes and who holds each, built by the
+  // first match() and kept like `dict`
+  struct MatchDir* match_dir = nullptr;
   // angular similarity.  has_abunds: EVERY node tracks abundances and every abundance vector matches its
   // hashes; h_abunds then holds them narrowed to u32 (a copy, like the hashes) until the first angular call uploads them
   // and computes the norms -- an index nobody asks pays no HBM.  bad_node: the lowest node whose norm2 does not fit 64 bits.
@@ -58,6 +62,13 @@ struct ResidentIndex {
   void most_common(const KmerMinHash& leaf, uint32_t* best_pos, uint64_t* best_common);
   uint32_t gather(const KmerMinHash& query, uint32_t threshold_common, GatherRow* rows, uint32_t rows_capacity, uint32_t* assigned,
                   Device& dev);
+  // (match.cpp) The records of a batch against the index (the rules: include/sourmash_amd.h, "Matching records").  seq_dev:
+  // the batch in device memory, record r = [offsets[r], offsets[r + 1]) (host, n + 1 ascending entries, the last at most
+  // total_len).  rows: n entries.  hit_offsets (nullable: no hit list): n + 1 entries, *hit_hashes receives the list.
+  void check_matchable() const;   // the refusals (kMsg): needs no device
+  void match(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n_records, MatchRow* rows,
+             uint64_t* hit_offsets, std::vector<uint64_t>* hit_hashes, hipStream_t s);
+  void drop_match_dir();
   void angular_ensure(const char* what, hipStream_t s);   // (angular.cpp from here) the first angular call: abundances to HBM, norms
   void norms2(uint64_t* out);
   void angular(ResidentIndex& cols, uint64_t* dot, double* cosine, double* angular);
@@ -90,6 +101,12 @@ void angular_block_dev(AngularSet rows, const uint64_t* row_offsets, AngularSet 
 // that share a hash (default: tools/bench_angular.py's sweep, DESIGN.md 3.10 "The prune threshold").  walked / skipped: of the last call.
 constexpr uint64_t kAngularPruneMinPairs = 4096;
 extern uint64_t g_angular_prune_min_pairs, g_angular_walked, g_angular_skipped;
+
+// match.cpp: what bounds the work space of match() -- the expected candidates (plus records) of one fold, and the
+// (record, node) counters of one round of the tally's dense regime.  The default is a memory cap (about 3.5 GiB of fold
+// buffers, 256 MiB of counters), not a measured optimum.
+constexpr uint64_t kMatchPairBudget = 1ull << 26;
+extern uint64_t g_match_pair_budget;
 
 // downsample.cpp (the rules are in include/sourmash_amd.h, "Downsampling").  `out` is a fresh sketch: it
 // receives src's parameters with max_hash / num replaced and the kept prefix.  A state that lives in HBM is cut there into a

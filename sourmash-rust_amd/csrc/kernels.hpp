@@ -1,6 +1,6 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
-// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip).  Plain structs and
-// pointers; no torch types anywhere.
+// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip).
+// Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -382,5 +382,42 @@ void launch_downsample_copy(const uint64_t* hashes, const uint32_t* abunds, cons
 // run starts end at (starts[cut], or `total` when everything is kept); without run starts out2_dev[1] = cut
 void launch_downsample_cut(const uint64_t* uniq, uint64_t n, const uint32_t* starts, uint64_t total, uint64_t max_hash, uint64_t* out2_dev,
                            hipStream_t s);
+
+// --- match_kernels.hip -----------------------------------------------------------------
+// Matching records against a resident index (the rules are in include/sourmash_amd.h, "Matching records").
+constexpr uint32_t kMatchSamples = 4096;          // sampled top of the directory's hashes in the probe: 32 KiB of LDS per workgroup
+constexpr uint32_t kMatchLdsPairs = 1024;         // owner pairs of one record that the LDS regime of the tally takes
+constexpr uint32_t kMatchThreadsPerRecord = 64;   // the tally gives a record one wave
+constexpr uint32_t kMatchMiss = 0xffffffffu;      // rank of a hash no node holds; `best` of a record without hits
+struct MatchRow { uint32_t windows, distinct, hit_windows, hit_distinct, best, best_common; };   // SmhMatchRow
+// The hash directory of an index in device memory: U[0 .. n_hashes) the sorted distinct hashes of all nodes, the nodes
+// holding U[g] are owners[starts[g] .. starts[g + 1]) ascending (the last list ends at n_pairs = the index's elements).
+struct MatchDirectory {
+  const uint64_t* U = nullptr;
+  const uint32_t* starts = nullptr;
+  const uint32_t* owners = nullptr;
+  uint32_t n_hashes = 0, n_pairs = 0;
+};
+void match_geometry(uint32_t* lds_pairs, uint32_t* threads_per_record, uint32_t* probe_samples);
+// ids[t] = the node holding element t of the CSR (t counted from offsets[0]), total = its elements
+void launch_match_owner_ids(const uint64_t* offsets_dev, uint32_t n, uint64_t total, uint32_t* ids, Device& dev, hipStream_t s);
+// The runs of one fold (run i: hash run_hash[i] of record run_rec[i], candidates run_start[i] .. run_start[i + 1], the last
+// one ends at ncand; ordered by record, then hash) -> rank_out[i] = rank in d.U or kMatchMiss, hit_flag[i] (nullable) = 0 / 1,
+// and per record r - rec0 of the fold: the first four fields of rows (zeroed by the caller) summed up, rec_first = its first
+// run (caller: 0xff bytes), rec_pairs = the owners of its hit runs added up (caller: zeroed).  Profile name match_probe.
+void launch_match_probe(const MatchDirectory& d, const uint64_t* run_hash, const uint64_t* run_rec, const uint32_t* run_start,
+                        uint32_t nruns, uint32_t ncand, uint32_t rec0, MatchRow* rows, uint32_t* rec_first,
+                        unsigned long long* rec_pairs, uint32_t* rank_out, uint32_t* hit_flag, Device& dev, hipStream_t s);
+// best / best_common of every record of the fold with at most kMatchLdsPairs owner pairs (and of those without a hit); the
+// others are appended to big_list (room for nrec entries; any order), *big_count (caller: zeroed) counts them.  match_tally.
+void launch_match_tally(const MatchDirectory& d, const uint32_t* rank, MatchRow* rows, const uint32_t* rec_first,
+                        const unsigned long long* rec_pairs, uint32_t nrec, uint32_t* big_list, uint32_t* big_count, Device& dev,
+                        hipStream_t s);
+// one round of the dense regime: records big[0 .. nbig) of the fold, slab = room for nbig * n_nodes counters.  match_tally.
+void launch_match_dense(const MatchDirectory& d, const uint32_t* rank, MatchRow* rows, const uint32_t* rec_first, const uint32_t* big,
+                        uint32_t nbig, uint32_t n_nodes, uint32_t* slab, Device& dev, hipStream_t s);
+// out[at[i]] = run_hash[i] for every hit run (at: the exclusive scan of the hit flags)
+void launch_match_hit_scatter(const uint64_t* run_hash, const uint32_t* rank, const uint32_t* at, uint32_t nruns, uint64_t* out, Device& dev,
+                              hipStream_t s);
 
 }  // namespace smh

@@ -1,0 +1,222 @@
+// match.cpp -- ResidentIndex::match (the rules are in include/sourmash_amd.h, "Matching records"): the hash
+// directory of an index and its cache, the folds of a batch cut at record boundaries, and per fold the grouped fold's own
+// sequence (hash with positions, positions to records, two sorts, the two-key run-length pass) followed by the probe, the
+// tally with its two regimes and the read-back.  The kernels are in match_kernels.hip.
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <numeric>
+#include <string>
+
+#include "index.hpp"
+
+namespace smh {
+
+uint64_t g_match_pair_budget = kMatchPairBudget;
+
+struct MatchDir {
+  DeviceBuffer U, starts, owners;
+  uint32_t n_hashes = 0, n_pairs = 0;
+  MatchDirectory view() const { return {U.as<uint64_t>(), starts.as<uint32_t>(), owners.as<uint32_t>(), n_hashes, n_pairs}; }
+};
+
+namespace {
+[[noreturn]] void refuse(const std::string& what) { throw Error(kMsg, "match: " + what); }
+
+// sorted distinct hashes of all nodes + who holds each: owner ids, a stable sort by hash, one run-length pass
+MatchDir* build_directory(const ResidentIndex& idx, Device& dev, hipStream_t s) {
+  const uint64_t total = idx.h_offsets.back() - idx.h_offsets.front();
+  if (total >= (1ull << 31)) refuse("the index holds " + std::to_string(total) + " hashes; the directory takes fewer than 2^31");
+  auto d = std::make_unique<MatchDir>();
+  d->n_pairs = (uint32_t)total;
+  if (total == 0) return d.release();
+  PoolBlock k0(total * 8), k1(total * 8), v0(total * 4), v1(total * 4), uq(total * 8), st(total * 4 + 4), cnt(4);
+  HIP_CHECK(hipMemcpyAsync(k0.ptr, idx.hashes.as<uint64_t>() + idx.h_offsets.front(), total * 8, hipMemcpyDeviceToDevice, s));
+  launch_match_owner_ids(idx.offsets.as<uint64_t>(), idx.n, total, v0.as<uint32_t>(), dev, s);
+  const int cur = radix_sort_u64_v32(k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(), total, dev.scratch, s);
+  run_length_encode_u64_async((cur ? k1 : k0).as<uint64_t>(), total, uq.as<uint64_t>(), st.as<uint32_t>(), dev.scratch, s, nullptr, nullptr,
+                              cnt.as<uint32_t>(), nullptr);
+  uint32_t nu = 0;
+  HIP_CHECK(hipMemcpyAsync(&nu, cnt.ptr, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  d->n_hashes = nu;
+  d->U.ensure((size_t)nu * 8);
+  d->starts.ensure((size_t)nu * 4);
+  d->owners.ensure(total * 4);
+  HIP_CHECK(hipMemcpyAsync(d->U.ptr, uq.ptr, (size_t)nu * 8, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d->starts.ptr, st.ptr, (size_t)nu * 4, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d->owners.ptr, (cur ? v1 : v0).ptr, total * 4, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  k0.synced = k1.synced = v0.synced = v1.synced = uq.synced = st.synced = cnt.synced = true;
+  dev.count("match_directory_built");
+  return d.release();
+}
+
+// The rows of a fold into the caller's pageable array through two page-locked halves: the copy out of one half runs while
+// the transfer into the other is in flight (a pageable destination would be staged by the runtime, one piece after another).
+void fetch_rows(const MatchRow* d_rows, MatchRow* out, size_t n, Engine& E, hipStream_t s) {
+  constexpr size_t kHalf = 1u << 16;   // rows per half: 1.5 MiB
+  const size_t half = std::min(n, kHalf);
+  E.pin_a.ensure(2 * half * sizeof(MatchRow));
+  MatchRow* pin = E.pin_a.as<MatchRow>();
+  size_t done = 0, len = half;
+  int cur = 0;
+  HIP_CHECK(hipMemcpyAsync(pin, d_rows, len * sizeof(MatchRow), hipMemcpyDeviceToHost, s));
+  while (done < n) {
+    HIP_CHECK(hipStreamSynchronize(s));
+    const size_t next = done + len, nlen = std::min(half, n - next);
+    if (nlen) HIP_CHECK(hipMemcpyAsync(pin + (size_t)(cur ^ 1) * half, d_rows + next, nlen * sizeof(MatchRow), hipMemcpyDeviceToHost, s));
+    memcpy(out + done, pin + (size_t)cur * half, len * sizeof(MatchRow));
+    done = next; len = nlen; cur ^= 1;
+  }
+}
+}  // namespace
+
+void ResidentIndex::drop_match_dir() { delete match_dir; match_dir = nullptr; }
+
+void ResidentIndex::check_matchable() const {
+  if (n == 0) refuse("the index holds no node (ksize, seed and max_hash are those of node 0)");
+  for (uint32_t i = 0; i < n; i++) {
+    const KmerMinHash& p = params[i];
+    if (p.molecule != kMoleculeDNA)
+      refuse("node " + std::to_string(i) + " is a " + molecule_name(p.molecule) + " sketch; only DNA sketches can be matched");
+    if (!(p.num == 0 && p.max_hash != 0))
+      refuse("node " + std::to_string(i) + " is not a scaled sketch (num = " + std::to_string(p.num) + ", max_hash = " +
+             std::to_string(p.max_hash) + ")");
+    const KmerMinHash& p0 = params[0];
+    if (p.ksize != p0.ksize || p.seed != p0.seed || p.max_hash != p0.max_hash)
+      refuse("node " + std::to_string(i) + " (ksize = " + std::to_string(p.ksize) + ", seed = " + std::to_string(p.seed) + ", max_hash = " +
+             std::to_string(p.max_hash) + ") differs from node 0 (ksize = " + std::to_string(p0.ksize) + ", seed = " +
+             std::to_string(p0.seed) + ", max_hash = " + std::to_string(p0.max_hash) + ")");
+  }
+}
+
+void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* off, uint32_t nrec, MatchRow* rows, uint64_t* hit_offsets,
+                          std::vector<uint64_t>* hit_hashes, hipStream_t s) {
+  check_matchable();
+  for (uint32_t r = 0; r < nrec; r++)
+    if (off[r + 1] < off[r]) refuse("offsets must ascend (record " + std::to_string(r) + ")");
+  if (nrec && off[nrec] > total_len)
+    refuse("the last offset " + std::to_string(off[nrec]) + " lies beyond the batch's " + std::to_string(total_len) + " bytes");
+  // the rows of records no fold's kernels see (a batch without a window, a fold without a candidate); the others come
+  // back whole from the device
+  auto blank = [&](uint32_t a, uint32_t e) { for (uint32_t r = a; r < e; r++) rows[r] = MatchRow{0, 0, 0, 0, kMatchMiss, 0}; };
+  if (hit_offsets) std::fill(hit_offsets, hit_offsets + nrec + 1, 0);
+  if (hit_hashes) hit_hashes->clear();
+  const uint32_t ksize = params[0].ksize;
+  const uint64_t seed = params[0].seed, max_hash = params[0].max_hash;
+  bool any_long = false;
+  for (uint32_t r = 0; r < nrec; r++) any_long |= off[r + 1] - off[r] >= ksize;
+  if (!any_long || ksize == 0) { blank(0, nrec); return; }
+
+  Device& dev = Device::get();
+  Engine& E = Engine::get();
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  if (!match_dir) match_dir = build_directory(*this, dev, s);
+  const MatchDirectory dir = match_dir->view();
+
+  E.offbuf.ensure((size_t)(nrec + 1) * 8);
+  E.grpbuf.ensure((size_t)nrec * 4);
+  std::vector<uint32_t> identity(nrec);
+  std::iota(identity.begin(), identity.end(), 0u);
+  HIP_CHECK(hipMemcpyAsync(E.offbuf.ptr, off, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(E.grpbuf.ptr, identity.data(), (size_t)nrec * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));   // (identity is a stack-lifetime staging vector)
+  SeqBatch b;
+  b.seq = seq_dev; b.len = total_len; b.starts = E.offbuf.as<uint64_t>(); b.nrec = nrec; b.vend0 = total_len;
+
+  // Folds: consecutive records while their cost -- one per record plus the expected candidates of its bytes -- fits the
+  // budget; a record alone always makes a fold, up to what one chunk of candidates can hold.
+  const double frac = (double)(((long double)max_hash + 1.0L) / 18446744073709551616.0L);
+  const double hard = 1.6e9;   // (estimate_capacity adds a quarter and 64 Ki: below 2^31)
+  const double budget = std::min((double)std::max<uint64_t>(g_match_pair_budget, 1), hard);
+  const bool want_hits = hit_offsets != nullptr;
+  for (uint32_t r0 = 0; r0 < nrec;) {
+    double cost = 0;
+    uint32_t r1 = r0;
+    while (r1 < nrec) {
+      const double c = 1.0 + (double)(off[r1 + 1] - off[r1]) * frac;
+      if (c > hard)
+        refuse("record " + std::to_string(r1) + " (" + std::to_string(off[r1 + 1] - off[r1]) + " bytes) alone would leave about " +
+               std::to_string((uint64_t)c) + " candidates; one fold takes fewer than 2^31 and no record is split");
+      if (r1 > r0 && cost + c > budget) break;
+      cost += c;
+      r1++;
+    }
+    const uint32_t nf = r1 - r0;
+    const uint64_t lo = off[r0], hi = off[r1];
+    const uint32_t f0 = r0;
+    r0 = r1;
+    const uint64_t nc = hi == lo ? 0 : E.run_dna_chunk(b, ksize, seed, lo, hi, max_hash, s);
+    if (nc == 0) { blank(f0, r1); continue; }
+    dev.count("match_fold");
+    // (hash, position) -> (hash, record); sort by hash, then stably by record; one run per distinct (record, hash)
+    launch_pos_to_group(E.cand_pos[0].as<uint64_t>(), nc, E.offbuf.as<uint64_t>(), nrec, E.grpbuf.as<uint32_t>(), s, 0);
+    const int c1 = radix_sort_u64(E.cand_hash[0].as<uint64_t>(), E.cand_hash[1].as<uint64_t>(), E.cand_pos[0].as<uint64_t>(),
+                                  E.cand_pos[1].as<uint64_t>(), nc, dev.scratch, s);
+    const int c2 = radix_sort_u64(E.cand_pos[c1].as<uint64_t>(), E.cand_pos[c1 ^ 1].as<uint64_t>(), E.cand_hash[c1].as<uint64_t>(),
+                                  E.cand_hash[c1 ^ 1].as<uint64_t>(), nc, dev.scratch, s, 0, 8);
+    const int cur = c1 ^ c2;
+    E.uniq.ensure(nc * 8); E.uniq2.ensure(nc * 8); E.starts.ensure((nc + 1) * 4);
+    const uint32_t nruns = run_length_encode_u64(E.cand_hash[cur].as<uint64_t>(), nc, E.uniq.as<uint64_t>(), E.starts.as<uint32_t>(),
+                                                 dev.scratch, s, nullptr, nullptr, E.cand_pos[cur].as<uint64_t>(), E.uniq2.as<uint64_t>(), 0);
+    if (nruns == 0) { blank(f0, r1); continue; }
+
+    PoolBlock d_rows((size_t)nf * sizeof(MatchRow)), d_first((size_t)nf * 4), d_pairs((size_t)nf * 8), d_rank((size_t)nruns * 4),
+        d_flag(want_hits ? ((size_t)nruns + 1) * 4 : 4), d_big((size_t)nf * 4 + 4);
+    uint32_t* big_count = d_big.as<uint32_t>() + nf;
+    HIP_CHECK(hipMemsetAsync(d_rows.ptr, 0, (size_t)nf * sizeof(MatchRow), s));
+    HIP_CHECK(hipMemsetAsync(d_first.ptr, 0xff, (size_t)nf * 4, s));
+    HIP_CHECK(hipMemsetAsync(d_pairs.ptr, 0, (size_t)nf * 8, s));
+    HIP_CHECK(hipMemsetAsync(big_count, 0, 4, s));
+    launch_match_probe(dir, E.uniq.as<uint64_t>(), E.uniq2.as<uint64_t>(), E.starts.as<uint32_t>(), nruns, (uint32_t)nc, f0,
+                       d_rows.as<MatchRow>(), d_first.as<uint32_t>(), d_pairs.as<unsigned long long>(), d_rank.as<uint32_t>(),
+                       want_hits ? d_flag.as<uint32_t>() : nullptr, dev, s);
+    launch_match_tally(dir, d_rank.as<uint32_t>(), d_rows.as<MatchRow>(), d_first.as<uint32_t>(), d_pairs.as<unsigned long long>(), nf,
+                       d_big.as<uint32_t>(), big_count, dev, s);
+    uint32_t nbig = 0;
+    HIP_CHECK(hipMemcpyAsync(&nbig, big_count, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (nbig) {
+      // the dense regime, in rounds of as many records as the budget holds counters for (n per record; one at least)
+      std::vector<uint32_t> big(nbig);
+      HIP_CHECK(hipMemcpyAsync(big.data(), d_big.ptr, (size_t)nbig * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      std::sort(big.begin(), big.end());   // (the kernel appended them in any order)
+      HIP_CHECK(hipMemcpyAsync(d_big.ptr, big.data(), (size_t)nbig * 4, hipMemcpyHostToDevice, s));
+      const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g_match_pair_budget / n, 1), std::min<uint32_t>(nbig, 1u << 16));
+      PoolBlock slab((size_t)per * n * 4);
+      for (uint32_t at = 0; at < nbig; at += per) {
+        launch_match_dense(dir, d_rank.as<uint32_t>(), d_rows.as<MatchRow>(), d_first.as<uint32_t>(), d_big.as<uint32_t>() + at,
+                           std::min(per, nbig - at), n, slab.as<uint32_t>(), dev, s);
+        dev.count("match_dense_round");
+      }
+      HIP_CHECK(hipStreamSynchronize(s));   // (big is read by the upload above)
+      slab.synced = true;
+    }
+    fetch_rows(d_rows.as<MatchRow>(), rows + f0, nf, E, s);
+    if (want_hits) {
+      uint32_t* total_dev = d_flag.as<uint32_t>() + nruns;
+      uint32_t nhit = 0;
+      exclusive_scan_u32_dev(d_flag.as<uint32_t>(), nruns, total_dev, dev.scratch, s);
+      HIP_CHECK(hipMemcpyAsync(&nhit, total_dev, 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (nhit) {
+        PoolBlock d_hits((size_t)nhit * 8);
+        launch_match_hit_scatter(E.uniq.as<uint64_t>(), d_rank.as<uint32_t>(), d_flag.as<uint32_t>(), nruns, d_hits.as<uint64_t>(), dev, s);
+        const size_t have = hit_hashes->size();
+        hit_hashes->resize(have + nhit);
+        HIP_CHECK(hipMemcpyAsync(hit_hashes->data() + have, d_hits.ptr, (size_t)nhit * 8, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        d_hits.synced = true;
+      }
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    d_rows.synced = d_first.synced = d_pairs.synced = d_rank.synced = d_flag.synced = d_big.synced = true;
+  }
+  // folds follow the records and a fold's hit runs follow (record, hash): the list is the CSR already
+  if (hit_offsets)
+    for (uint32_t r = 0; r < nrec; r++) hit_offsets[r + 1] = hit_offsets[r] + rows[r].hit_distinct;
+}
+
+}  // namespace smh

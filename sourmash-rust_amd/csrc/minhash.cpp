@@ -418,6 +418,12 @@ uint64_t Engine::run_chunk(HashSourceRef src_, uint64_t lo, uint64_t hi, uint64_
   throw_internal("candidate buffer overflow after re-run");
 }
 
+uint64_t Engine::run_dna_chunk(const SeqBatch& b, uint32_t ksize, uint64_t seed, uint64_t lo, uint64_t hi, uint64_t thr, hipStream_t s) {
+  DnaSource src;
+  src.b = b; src.ksize = ksize; src.seed = seed; src.dev = &Device::get();
+  return run_chunk(&src, lo, hi, thr, true, s);
+}
+
 bool Engine::run_chunk_small(HashSourceRef src_, uint64_t lo, uint64_t hi, uint64_t thr, uint32_t expected, hipStream_t s,
                              DeviceSketch* out, uint64_t* n_out, uint64_t* cap_out) {
   HashSource& src = *static_cast<HashSource*>(src_);

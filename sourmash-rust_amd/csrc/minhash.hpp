@@ -173,6 +173,8 @@ class Engine {
   // (and cand_pos[0]); returns how many.  Re-runs once with an exact buffer on overflow.  known: the count a launch over
   // the same range has already left behind when it overflowed (0 = none): the buffer is at least that large.
   uint64_t run_chunk(HashSourceRef src, uint64_t lo, uint64_t hi, uint64_t thr, bool want_pos, hipStream_t s, uint64_t known = 0);
+  // run_chunk over the DNA k-mers of a batch, with their stream positions (want_pos): for callers outside minhash.cpp
+  uint64_t run_dna_chunk(const SeqBatch& b, uint32_t ksize, uint64_t seed, uint64_t lo, uint64_t hi, uint64_t thr, hipStream_t s);
   // A chunk expected to leave a few thousand candidates: hash AND fold with one synchronisation (k_small_fold reads the
   // candidate count on the device).  True: `out` holds the sorted distinct hashes and their run starts.  False: *n_out
   // candidates were produced and wait in cand_hash[0] (if they fit *cap_out) for the general path.

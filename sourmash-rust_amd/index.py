@@ -4,6 +4,8 @@
   most_common (scaffold)    reference src/index/sbt.rs:361-370 (nearest leaf = arg-max count_common)
   ResidentIndex.gather      the greedy decomposition of a query (no counterpart in the reference crate: the rules are those
                             of include/sourmash_amd.h, smh_index_gather)
+  ResidentIndex.match       the k-mers of every record of a batch the index knows, and each record's best node (no counterpart
+                            either: include/sourmash_amd.h, "Matching records")
 
 A "node" here is a KmerMinHash (the reference's Leaf wraps a Signature whose first sketch is used,
 src/index.rs:108-161)."""
@@ -13,7 +15,7 @@ import math
 
 import numpy as np
 
-from ._lib import SmhGatherRow, lib, u64p
+from ._lib import SmhGatherRow, SmhMatchRow, lib, u64p
 from .errors import SourmashError, call
 
 UNASSIGNED = 0xFFFFFFFF
@@ -29,6 +31,11 @@ GatherRecord = collections.namedtuple("GatherRecord", [
     "remaining_bp"])       # scaled * (query positions nobody has consumed after this row)
 GatherResult = collections.namedtuple("GatherResult", ["rows", "assigned"])
 AngularResult = collections.namedtuple("AngularResult", ["dot", "cosine", "angular"])
+# one numpy array per field of SmhMatchRow (uint32, a record each); hit_offsets / hit_hashes (uint64) or None
+MatchResult = collections.namedtuple("MatchResult", ["windows", "distinct", "hit_windows", "hit_distinct", "best", "best_common",
+                                                     "hit_offsets", "hit_hashes"])
+NO_MATCH = 0xFFFFFFFF
+_MATCH_ROW = np.dtype([(name, np.uint32) for name, _ in SmhMatchRow._fields_])
 
 
 def scaled_of_max_hash(max_hash):
@@ -238,6 +245,41 @@ class ResidentIndex:
                 0.0 if flat else float(np.std(mine)) if ab is not None else None,
                 scaled * left))
         return GatherResult(out, assigned)
+
+    def match(self, records, hits=False, stream=None):
+        """Every record of a batch against the index (smh_index_match_*; the rules: include/sourmash_amd.h, "Matching
+        records"): MatchResult of numpy arrays, one entry per record.  records: a fastx.Records, a list of bytes, or
+        (dev_ptr, total_len, offsets) for a batch in device memory.  hits=True also returns the CSR of every record's
+        distinct hit hashes, ascending.  best is NO_MATCH for a record without a hit.  There is no downsample argument:
+        raw records have no resolution of their own, they are sampled at the index's max_hash."""
+        from .fastx import Records
+        from .minhash import _free
+        hp, nh = u64p(), C.c_uint64()
+
+        def run(n, fn, *front):
+            rows = np.zeros(n, dtype=_MATCH_ROW)
+            off = np.zeros(n + 1, dtype=np.uint64) if hits else None
+            tail = (off.ctypes.data_as(u64p), C.byref(hp), C.byref(nh)) if hits else (None, None, None)
+            call(fn, self._h, *front, rows.ctypes.data_as(C.c_void_p), *tail)
+            return rows, off
+
+        if isinstance(records, Records):
+            rows, off = run(len(records), self._L.smh_index_match_records, records._p)
+        elif isinstance(records, tuple):
+            ptr, total, offsets = records
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            rows, off = run(len(offsets) - 1, lambda h, *a: self._L.smh_index_match_sequences_dev(h, *a, C.c_void_p(stream or 0)),
+                            C.c_void_p(ptr), int(total), offsets.ctypes.data_as(u64p), len(offsets) - 1)
+        else:
+            seqs = [bytes(s) for s in records]
+            offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+            np.cumsum(np.array([len(s) for s in seqs], dtype=np.uint64), out=offsets[1:])
+            rows, off = run(len(seqs), self._L.smh_index_match_sequences, b"".join(seqs), offsets.ctypes.data_as(u64p), len(seqs))
+        hashes = None
+        if hits:
+            hashes = np.ctypeslib.as_array(hp, shape=(nh.value,)).copy() if nh.value else np.zeros(0, np.uint64)
+            _free(C.cast(hp, C.c_void_p))
+        return MatchResult(*[rows[name] for name in _MATCH_ROW.names], off, hashes)   # views of the rows: no copy
 
     @property
     def has_abundances(self):

@@ -152,6 +152,22 @@ def downsample_geometry():
     return t.value, th.value
 
 
+def match_geometry():
+    """(owner pairs of a record the tally counts in LDS, threads it gives a record, directory hashes the probe samples into LDS)"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().smh_match_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def match_pair_budget():
+    return int(lib().smh_match_pair_budget())
+
+
+def set_match_pair_budget(pairs):
+    """bounds the work space of ResidentIndex.match (smh_match_set_pair_budget); 0 restores the default"""
+    lib().smh_match_set_pair_budget(int(pairs))
+
+
 def angular_last_stats():
     """(pairs walked, pairs given zeros without a walk) of the last angular call"""
     a, b = C.c_uint64(), C.c_uint64()
