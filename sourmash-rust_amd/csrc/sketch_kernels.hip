@@ -305,23 +305,23 @@ __device__ __forceinline__ W2 w2_mul5_add(W2 x, uint64_t c) {
   asm("v_lshl_add_u64 %0, %1, 2, %1" : "=v"(t) : "v"(v));   // (left to itself the compiler multiplies by 5: two v_mad_u64_u32 and two moves)
   return w2_split(t + c);
 }
-// fmix64 WITHOUT its last `k ^= k >> 33`.  That step only touches the low dword, and whether the digest
-// h = fmix(h1) + fmix(h2) can be <= a threshold is settled by the high dwords up to one carry (open_may_pass):
-// the windows that cannot pass -- all but ~1/scaled of them -- skip the last step of both mixes and the 64-bit sum.
-__device__ __forceinline__ W2 w2_fmix_open(W2 k) {
-  k.lo ^= k.hi >> 1;                                   // k ^= k >> 33
-  k = w2_mul(k, 0xff51afd7ed558ccdULL);
-  k.lo ^= k.hi >> 1;
-  k = w2_mul(k, 0xc4ceb9fe1a85ec53ULL);
-  return k;
-}
-// thr_hi1 = open_thr(thr).  h.hi is a.hi + b.hi or that + 1 (mod 2^32), so h <= thr needs a.hi + b.hi + 1 (mod 2^32)
-// <= thr.hi + 1; a superset of the passing windows (exact test: open_finish() <= thr), everything when thr.hi is all ones.
+// The open digest.  After `h1 += h2; h2 += h1` the digest is h = fmix(h1) + fmix(h2).  The sketch kernels stop each
+// fmix in front of its last multiply: ka = w2_fmix_pre(h1), kb = w2_fmix_pre(h2); with C = fmix's second constant,
+// a = ka * C, b = kb * C and h = (a ^ a >> 33) + (b ^ b >> 33) = open_full(ka, kb).  Whether h can be <= a threshold is
+// settled by high dwords alone (open_hi_sum1 against open_thr): the windows that cannot pass -- all but ~1/scaled of
+// them -- never form the two products, the xor-shifts or the 64-bit sum.
+// The filter's threshold, open_thr<SUM>(thr), for the value open_hi_sum1<SUM>(ka, kb) forms (see there); both tests are
+// supersets of the passing windows (exact test: open_full() <= thr).
+//   SUM:  E = hi32((ka + kb) * C) + 1 (mod 2^32) and E - h.hi is 0, 1 or 2, so h <= thr needs E <= thr.hi + 2.  That sum
+//         must not wrap: for thr.hi >= 0xfffffffd the threshold saturates to all ones and everything passes.
+//   !SUM: F = a.hi + b.hi + 1 (mod 2^32) and h.hi is F - 1 or F, so h <= thr needs F <= thr.hi + 1; everything when
+//         thr.hi is all ones.
+template <bool SUM>
 __device__ __forceinline__ uint32_t open_thr(uint64_t thr) {
   const uint32_t hi = (uint32_t)(thr >> 32);
+  if (SUM) return hi >= 0xfffffffdu ? 0xffffffffu : hi + 2u;
   return hi == 0xffffffffu ? hi : hi + 1u;
 }
-__device__ __forceinline__ bool open_may_pass(W2 a, W2 b, uint32_t thr_hi1) { return a.hi + b.hi + 1u <= thr_hi1; }
 __device__ __forceinline__ uint64_t open_finish(W2 a, W2 b) {
   a.lo ^= a.hi >> 1; b.lo ^= b.hi >> 1;
   return ((((uint64_t)a.hi << 32) | a.lo) + (((uint64_t)b.hi << 32) | b.lo));
@@ -333,13 +333,6 @@ __device__ __forceinline__ W2 w2_add_keep(W2 a, W2 b) {
   asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(r) : "v"(((uint64_t)a.hi << 32) | a.lo), "v"(((uint64_t)b.hi << 32) | b.lo));
   return w2_split(r);
 }
-// The DNA kernel stops one multiply earlier than w2_fmix_open: ka = w2_fmix_pre(h1), kb = w2_fmix_pre(h2), and
-// a = ka * C, b = kb * C with C = fmix's second constant.  The filter needs only a.hi + b.hi + 1, and the high dword
-// of x * C is mul_hi(x.lo, C.lo) + x.lo * C.hi + x.hi * C.lo (mod 2^32): the four cross terms chain through the
-// addends of four v_mad_u64_u32 (only the low dword of each is used; the first addend is the + 1), the two mul_hi
-// and the chain meet in one v_add3.  Seven instructions, against the six mads, two adds and the v_add3 of two whole
-// multiplies and open_may_pass.  The products' low dwords are only formed for the rare window that may pass
-// (open_full).
 constexpr uint64_t kFmixC2 = 0xc4ceb9fe1a85ec53ULL;
 __device__ __forceinline__ W2 w2_fmix_pre(W2 k) {
   k.lo ^= k.hi >> 1;                                   // k ^= k >> 33
@@ -347,9 +340,29 @@ __device__ __forceinline__ W2 w2_fmix_pre(W2 k) {
   k.lo ^= k.hi >> 1;
   return k;
 }
-__device__ __forceinline__ uint32_t open_hi_sum1(W2 ka, W2 kb) {   // == a.hi + b.hi + 1 (mod 2^32)
+// What the filter compares with open_thr<SUM>.  The high dword of x * C is mul_hi(x.lo, C.lo) + x.lo * C.hi + x.hi * C.lo
+// (mod 2^32); the cross terms chain through the addends of v_mad_u64_u32 (only the low dword of each is used; the first
+// addend is the + 1).
+//   SUM:  multiplication distributes over the sum, (ka + kb) * C == a + b (mod 2^64), so ONE product's high dword stands
+//         for both: with d = (ka + kb) * C, d.hi = a.hi + b.hi + cy (cy: the carry of a.lo + b.lo), while
+//         h.hi = a.hi + b.hi + cy' (cy': the carry of the two xor-shifted low dwords; `k ^= k >> 33` changes the low
+//         dword only).  E = d.hi + 1 (mod 2^32), hence E - h.hi = 1 + cy - cy' is 0, 1 or 2.  One 64-bit add that keeps
+//         ka and kb (the rare block needs them), two mads, one mul_hi and one 32-bit add.
+//   !SUM: F = a.hi + b.hi + 1 from both products' high dwords: four chained mads, two mul_hi, one v_add3.  Three
+//         slow-class instructions more; kept for the kernels whose registers the sum's pair does not fit (k_dna_rolling,
+//         SUMF).  k_amino_tiled tests the same F on products it forms in full.
+template <bool SUM>
+__device__ __forceinline__ uint32_t open_hi_sum1(W2 ka, W2 kb) {
   const uint32_t cl = (uint32_t)kFmixC2, ch = (uint32_t)(kFmixC2 >> 32);
   uint64_t s0, s1, s2, s3, cy;
+  if (SUM) {
+    const W2 s = w2_add_keep(ka, kb);
+    asm("v_mad_u64_u32 %0, %1, %2, %3, 1" : "=v"(s0), "=s"(cy) : "v"(s.hi), "s"(cl));
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(s1), "=s"(cy) : "v"(s.lo), "s"(ch), "v"(s0));
+    uint32_t e;   // (as asm so that it stays a 32-bit add, see w2_mul)
+    asm("v_add_u32 %0, %1, %2" : "=v"(e) : "v"((uint32_t)s1), "v"(__umulhi(s.lo, cl)));
+    return e;
+  }
   asm("v_mad_u64_u32 %0, %1, %2, %3, 1" : "=v"(s0), "=s"(cy) : "v"(ka.hi), "s"(cl));
   asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(s1), "=s"(cy) : "v"(ka.lo), "s"(ch), "v"(s0));
   asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(s2), "=s"(cy) : "v"(kb.hi), "s"(cl), "v"(s1));
@@ -446,6 +459,11 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
   // the k2 words' cross term from the tables (kLutDwordsCross).  Not in the per-record kernels: held to 64 registers for
   // eight waves per SIMD, they already spill, and the second dword of the {B, B'} reads makes them spill more.
   constexpr bool CROSS = FOLD && !PR;
+  // the filter on the sum ka + kb (open_hi_sum1<true>, open_thr<true>).  Not in the per-record kernels on the folded
+  // tables with a compile-time k (k = 21, 31): held to 64 registers they spill 28 bytes per lane, and the sum's register
+  // pair next to ka and kb makes that 32 -- also with the sum's cross terms formed by 32-bit multiplies, which need no
+  // further pair.  They keep the filter on both products (open_hi_sum1<false>, open_thr<false>).
+  constexpr bool SUMF = !(PR && FOLD && KT != 0);
   __shared__ __attribute__((aligned(16))) uint32_t lut[CROSS ? kLutDwordsCross : (FOLD ? kLutDwordsFold : kLutDwords)];
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* st_ctl = smem;                                    // [0] = count, [1] = dirty tile, [2..3] = flush base, [4] = next tile
@@ -542,7 +560,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
   for (uint64_t tix = blockIdx.x; tix < ntiles;) {
     const uint64_t T0 = hp.range_lo + tix * TILE;
     const uint64_t thr = hp.thr;
-    const uint32_t thr_hi1 = open_thr(hp.thr);
+    const uint32_t thr_hi1 = open_thr<SUMF>(hp.thr);
     // An operand in a scalar register halves the issue rate of a plain two-operand instruction (tools/instr_rate.hip):
     // what the hash xors in per k-mer lives in vector registers.
     W2 seedv{(uint32_t)hp.seed, (uint32_t)(hp.seed >> 32)};
@@ -885,7 +903,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
           }
 #pragma unroll
           for (int q = 0; q < HB; q++)
-            if (open_hi_sum1(ha[q], hb[q]) <= (PR ? open_thr(tq[g0b + q]) : thr_hi1)) {   // ~1 in `scaled` windows gets here
+            if (open_hi_sum1<SUMF>(ha[q], hb[q]) <= (PR ? open_thr<SUMF>(tq[g0b + q]) : thr_hi1)) {   // ~1 in `scaled` windows gets here
               uint32_t om = okmask;
               asm volatile("" : "+v"(om));                  // keeps the mask test inside this rare block
               const uint64_t h = open_full(ha[q], hb[q]);
@@ -1328,7 +1346,7 @@ __global__ __launch_bounds__(256) void k_spliced_windows(SeqBatch b, HashParams 
 
 // murmur64 of a W-byte string, 1 <= W <= 16: no full block, k1 = bytes 0..7, k2 = bytes 8..W-1 (reference
 // src/lib.rs:33-35 on aa.windows()).  k1c1 = k1 * c1 is handed in (the two strands get it differently, see
-// k_protein_fused); k2 = the bytes past the eighth as they are; the digest is left open (w2_fmix_open).
+// k_protein_fused); k2 = the bytes past the eighth as they are; the digest is left open: (a, b) with h = open_full(a, b).
 // W == 9: k2 is one byte, so its whole contribution -- seed ^ mix_k2(byte) ^ W -- comes from a table (h2_ready).
 template <int W>
 __device__ __forceinline__ void murmur_short(W2 k1c1, W2 k2, W2 seedw /* seed ^ W, in vector registers */, uint64_t h2_ready, W2& a, W2& b) {
@@ -1339,7 +1357,7 @@ __device__ __forceinline__ void murmur_short(W2 k1c1, W2 k2, W2 seedw /* seed ^ 
   }
   h1 = w2_xor(h1, w2_mul(w2_rotl(k1c1, 31), kC2));
   w2_cross_add(h1, h2);
-  a = w2_fmix_open(h1); b = w2_fmix_open(h2);
+  a = w2_fmix_pre(h1); b = w2_fmix_pre(h2);
 }
 
 // byte BYTE of x, shifted left by SH, in one sub-dword-addressed instruction (full rate; see k_dna_rolling)
@@ -1392,7 +1410,7 @@ __global__ __launch_bounds__(THREADS, SMH_PF_MINW) void k_protein_fused(SeqBatch
   if (W == 9) for (int e = tid0; e < 256; e += THREADS) k2tab[e] = hp.seed ^ mix_k2((uint64_t)e) ^ (uint64_t)W;
   if (tid0 == 0) st_ctl[0] = 0;
 
-  const uint32_t thr_hi1 = open_thr(hp.thr);
+  const uint32_t thr_hi1 = open_thr<true>(hp.thr);
   W2 seedw{(uint32_t)hp.seed ^ (uint32_t)W, (uint32_t)(hp.seed >> 32)};   // in vector registers: see k_dna_rolling
   asm volatile("" : "+v"(seedw.lo), "+v"(seedw.hi));
   const uint64_t ntiles = (b.len + TILE - 1) / TILE;
@@ -1572,10 +1590,10 @@ __global__ __launch_bounds__(THREADS, SMH_PF_MINW) void k_protein_fused(SeqBatch
           const W2 k2r{ND > 2 ? Sr[t][ND > 2 ? 2 : 0] : 0u, ND > 3 ? Sr[t][ND > 3 ? 3 : 0] : 0u};
           murmur_short<W>(w2_mul(W2{Sf[t][0], Sf[t][1]}, kC1), k2f, seedw, h2f[q], fa, fb);
           murmur_short<W>(W >= 8 ? w2_split(Mr[t]) : w2_mul(W2{Sr[t][0], Sr[t][1]}, kC1), k2r, seedw, h2r[q], ra, rb);
-          if (open_may_pass(fa, fb, thr_hi1) || open_may_pass(ra, rb, thr_hi1)) {   // ~2 in `scaled` positions get here
+          if (open_hi_sum1<true>(fa, fb) <= thr_hi1 || open_hi_sum1<true>(ra, rb) <= thr_hi1) {   // ~2 in `scaled` positions get here
             uint32_t om = okmask;
             asm volatile("" : "+v"(om));
-            const uint64_t hf = open_finish(fa, fb), hr = open_finish(ra, rb);
+            const uint64_t hf = open_full(fa, fb), hr = open_full(ra, rb);
             if ((om >> q) & 1u) {
               const uint64_t a = p0 + i0 + q + 1 - KB;      // first base of the span; see k_protein_positions
               if (hf <= hp.thr) stage_emit(stage, sink, hf, a << 1);
@@ -1785,7 +1803,7 @@ __global__ __launch_bounds__(kAmThreads) void k_amino_tiled(SeqBatch b, HashPara
   if (tid == 0) smem[0] = 0;
   __syncthreads();
 
-  const uint32_t thr_hi1 = open_thr(hp.thr);
+  const uint32_t thr_hi1 = open_thr<false>(hp.thr);
   const uint64_t hi_pos = hp.range_hi < b.len ? hp.range_hi : b.len;      // window starts of this launch: [range_lo, hi_pos)
   const uint64_t ntiles = hi_pos > hp.range_lo ? (hi_pos - hp.range_lo + kAmTile - 1) / kAmTile : 0;
   const uintptr_t gend = ((uintptr_t)(b.seq + b.len) + 15) & ~(uintptr_t)15;
@@ -1874,10 +1892,13 @@ __global__ __launch_bounds__(kAmThreads) void k_amino_tiled(SeqBatch b, HashPara
             h2 = w2_mul5_add(w2_add(w2_rotl(h2, 31), h1), 0x38495ab5ull);
             h1.lo ^= 16u; h2.lo ^= 16u;
             w2_cross_add(h1, h2);
-            fa = w2_fmix_open(h1); fb = w2_fmix_open(h2);
+            fa = w2_fmix_pre(h1); fb = w2_fmix_pre(h2);
           }
-          if (open_may_pass(fa, fb, thr_hi1)) {
-            const uint64_t h = open_finish(fa, fb);
+          // (both closing multiplies for every window, then the filter on the products' high dwords: the filter on the
+          // sum was measured here and is no gain by the project's rule -- DESIGN.md 3.11)
+          const W2 pa = w2_mul(fa, kFmixC2), pb = w2_mul(fb, kFmixC2);
+          if (pa.hi + pb.hi + 1u <= thr_hi1) {
+            const uint64_t h = open_finish(pa, pb);
             if (h <= hp.thr && emit_ok((uint32_t)j)) stage_emit(stage, sink, h, hp.pos_base + p0 + j);
           }
         }
