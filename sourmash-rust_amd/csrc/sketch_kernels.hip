@@ -397,12 +397,27 @@ __device__ __forceinline__ W2 mix_word(int w, W2 M, uint32_t S, uint32_t P) {
   if (FOLD) return (w & 1) ? mix_k2_fold<CROSS>(S, M, P) : mix_k1_fold(S, M);
   return (w & 1) ? w2_mul(w2_rotl(M, 33), kC1) : w2_mul(w2_rotl(M, 31), kC2);
 }
+// h ^ m with the length KX xored into the low dword as well: a ^ b ^ c is v_bitop3_b32 with the truth table 0x96 (gfx950
+// has no v_xor3_b32), and with the third operand an inline constant it issues at the rate of a plain v_xor_b32 (105
+// lanes/clk/CU against 68 with three registers: tools/instr_rate.hip), so the xor of the length costs nothing
+template <int KX>
+__device__ __forceinline__ W2 w2_xor_len(W2 h, W2 m) {
+  uint32_t lo;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(lo) : "v"(h.lo), "v"(m.lo), "n"(KX));
+  return {lo, h.hi ^ m.hi};
+}
 // murmur64 from the table look-ups of the k-mer's words (mix_word).
 // The digest is left OPEN one multiply early: (ka, kb) with h = open_full(ka, kb), filtered by open_hi_sum1.
-template <int L, bool FOLD, bool CROSS>
+// S32: the seed is below 2^32 (the launcher has checked it).  seedv.hi is never read: h1 and h2 start with a high dword
+// that is zero at compile time, so the first xor into each is one instruction on the low dword (k1.hi and k2.hi pass
+// through).  The folded constant seed * 5 + c stays the run-time 64-bit value.
+// KX > 0: k at compile time and not a multiple of 16 (the kernels with S32 and a compile-time k): `^= len` rides on the
+// tail words' xors (w2_xor_len); h2 has no tail word for k mod 16 <= 8 and keeps its own xor.
+template <int L, bool FOLD, bool CROSS, bool S32 = false, int KX = 0>
 __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint32_t (&S)[2 * L], const uint32_t (&P)[2 * L], int K, uint64_t seed, W2 seedv,
                                                 W2& a, W2& b) {
   W2 h1 = seedv, h2 = seedv;                            // (seedv: the seed's halves in vector registers, see k_dna_rolling)
+  if (S32) { h1.hi = 0u; h2.hi = 0u; }
   const int nblocks = K >> 4, tail = K & 15;
 #pragma unroll
   for (int blk = 0; blk < L; blk++) {
@@ -415,11 +430,17 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint
       h2 = w2_xor(h2, mix_word<FOLD, CROSS>(w2, M[w2], S[w2], P[w2]));
       h2 = w2_mul5_add(w2_add_keep(w2_rotl(h2, 31), h1), 0x38495ab5u);
     } else if (blk == nblocks) {
+      if (KX > 0) {
+        if ((KX & 15) > 8) h2 = w2_xor_len<KX>(h2, mix_word<FOLD, CROSS>(w2, M[w2], S[w2], P[w2]));
+        else h2.lo ^= (uint32_t)KX;
+        h1 = w2_xor_len<KX>(h1, mix_word<FOLD, CROSS>(w1, M[w1], S[w1], P[w1]));
+        continue;
+      }
       if (tail > 8) h2 = w2_xor(h2, mix_word<FOLD, CROSS>(w2, M[w2], S[w2], P[w2]));
       if (tail > 0) h1 = w2_xor(h1, mix_word<FOLD, CROSS>(w1, M[w1], S[w1], P[w1]));
     }
   }
-  h1.lo ^= (uint32_t)K; h2.lo ^= (uint32_t)K;          // ^= len (K <= 128)
+  if (KX == 0) { h1.lo ^= (uint32_t)K; h2.lo ^= (uint32_t)K; }          // ^= len (K <= 128)
   w2_cross_add(h1, h2);
   a = w2_fmix_pre(h1); b = w2_fmix_pre(h2);           // first word of the digest = open_full(a, b)
 }
@@ -447,7 +468,10 @@ __device__ __forceinline__ void murmur_kmer_pre(const W2 (&M)[2 * L], const uint
 // 16 bases and decodes nothing.  Dirty dwords end the lane's window of clean groups like a record boundary does; the group
 // then re-reads its four bytes from global memory (rare) and takes the per-base path with the same conditions as ever.
 constexpr int kDnaCtlDwords = 8;   // the LDS header of k_dna_rolling (32 bytes: the staged hashes behind it stay 16-byte aligned)
-template <int KT, int THREADS, int HB, int L, bool PR = false, bool PK = false, int MINW = (PK ? 8 : 4)>
+// S32: hp.seed < 2^32, known to the launcher (murmur_kmer_pre); with a compile-time k the length's xor is folded too
+// (w2_xor_len).  Only the packed two-limb kernels with a launch-uniform threshold have the variant; a seed at or above
+// 2^32 runs the kernel without it, which is the code of before.
+template <int KT, int THREADS, int HB, int L, bool PR = false, bool PK = false, int MINW = (PK ? 8 : 4), bool S32 = false>
 __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashParams hp, CandSink sink,
                                                                      int logR, uint32_t stage_cap, uint32_t* tile_ctr) {
   // LDS: static: the product tables (6.8 KiB, folded 11.3 KiB, folded with the cross term 12.8 KiB; a compile-time address, so a table read is one
@@ -563,8 +587,9 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
     const uint32_t thr_hi1 = open_thr<SUMF>(hp.thr);
     // An operand in a scalar register halves the issue rate of a plain two-operand instruction (tools/instr_rate.hip):
     // what the hash xors in per k-mer lives in vector registers.
-    W2 seedv{(uint32_t)hp.seed, (uint32_t)(hp.seed >> 32)};
-    asm volatile("" : "+v"(seedv.lo), "+v"(seedv.hi));
+    W2 seedv{(uint32_t)hp.seed, S32 ? 0u : (uint32_t)(hp.seed >> 32)};
+    if (S32) asm volatile("" : "+v"(seedv.lo));
+    else asm volatile("" : "+v"(seedv.lo), "+v"(seedv.hi));
     uint64_t lthr = hp.thr;   // PR: threshold of the record the lane is in
 
     // ---- stage [T0, T0 + TILE + K - 1) in LDS: aligned 16-byte loads, one pad dword per R bytes
@@ -899,7 +924,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_dna_rolling(SeqBatch b, HashP
                 }
               }
             }
-            murmur_kmer_pre<L, FOLD, CROSS>(M, S, P, K, hp.seed, seedv, ha[q], hb[q]);
+            murmur_kmer_pre<L, FOLD, CROSS, S32, (S32 && (KT & 15) > 0) ? KT : 0>(M, S, P, K, hp.seed, seedv, ha[q], hb[q]);
           }
 #pragma unroll
           for (int q = 0; q < HB; q++)
@@ -2064,11 +2089,12 @@ static uint64_t resident_workgroups(Kernel kernel, int threads, size_t lds, Devi
 // One launch of a k_dna_rolling instantiation over `ntiles` tiles: the grid is what is resident at once; with more tiles
 // than that the workgroups take their further tiles from a counter word (Device::tile_counter, zeroed in stream order in
 // front of the timed launch).  Device::count records which way a launch went (dna_tiles_dynamic / dna_tiles_static).
+// seed32: the instantiation is the one for seeds below 2^32 (k_dna_rolling's S32), recorded as dna_seed32 / dna_seed64.
 // The per-record kernels have no dynamic path (see the kernel's tile loop) and keep the launch they had: 8 workgroups per
 // CU, four of them resident, tiles split statically -- measured on the bench kernel, a static split over just the resident
 // workgroups is SLOWER than over more, smaller shares (profiles/r09_dna_schedule.json, grid_sweep).
 template <class Kernel>
-static void launch_rolling_tiles(Kernel kernel, int threads, bool per_record, const SeqBatch& b, const HashParams& p, const CandSink& sink,
+static void launch_rolling_tiles(Kernel kernel, int threads, bool per_record, bool seed32, const SeqBatch& b, const HashParams& p, const CandSink& sink,
                                  uint64_t ntiles, size_t lds, int logR, uint32_t stage_cap, Device& dev, hipStream_t s) {
   uint64_t grid = per_record ? (uint64_t)dev.cu_count() * 8 : resident_workgroups(kernel, threads, lds, dev);
   bool dynamic = !per_record && ntiles > grid && ntiles < (1ull << 31);
@@ -2083,6 +2109,7 @@ static void launch_rolling_tiles(Kernel kernel, int threads, bool per_record, co
   if (grid > ntiles) grid = ntiles;
   uint32_t* ctr = dynamic ? dev.tile_counter(s) : nullptr;
   dev.count(dynamic ? "dna_tiles_dynamic" : "dna_tiles_static");
+  dev.count(seed32 ? "dna_seed32" : "dna_seed64");
   dev.prof_begin(s);
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, s, b, p, sink, logR, stage_cap, ctr);
 }
@@ -2090,7 +2117,7 @@ static void launch_rolling_tiles(Kernel kernel, int threads, bool per_record, co
 template <int KT, int L>
 static void launch_rolling(const SeqBatch& b, const HashParams& p, const CandSink& sink, uint64_t ntiles, size_t lds,
                            int logR, uint32_t stage_cap, const DnaCfg& c, Device& dev, hipStream_t s) {
-#define SMH_LAUNCH_K(T, ...) launch_rolling_tiles(k_dna_rolling<KT, T, __VA_ARGS__>, T, p.thr_rec != nullptr, b, p, sink, ntiles, lds, logR, stage_cap, dev, s)
+#define SMH_LAUNCH_K(T, ...) launch_rolling_tiles(k_dna_rolling<KT, T, __VA_ARGS__>, T, p.thr_rec != nullptr, false, b, p, sink, ntiles, lds, logR, stage_cap, dev, s)
 #define SMH_LAUNCH(T, H) SMH_LAUNCH_K(T, H, L)
   if (p.thr_rec) {   // per-record thresholds: default geometry only
     if (c.packed) SMH_LAUNCH_K(512, 2, L, true, true);
@@ -2110,6 +2137,13 @@ static void launch_rolling(const SeqBatch& b, const HashParams& p, const CandSin
 #endif
     // (six waves per SIMD, one hash per block: 80 vector registers keep the scalar values out of vector lanes; 27.2 against
     // 27.6 ms per 10 GB with eight waves and two hashes per block, profiles/r04_pmc_dna_rolling.json "variants_measured")
+    // (two limbs: a seed below 2^32 -- every seed sourmash passes -- has its own instantiation, see murmur_kmer_pre)
+    if constexpr (L == 2) {
+      if ((p.seed >> 32) == 0) {
+        launch_rolling_tiles(k_dna_rolling<KT, 512, 1, L, false, true, 6, true>, 512, false, true, b, p, sink, ntiles, lds, logR, stage_cap, dev, s);
+        return;
+      }
+    }
     SMH_LAUNCH_K(512, 1, L, false, true, 6);
     return;
   }
@@ -2164,8 +2198,8 @@ void launch_dna_hash(const SeqBatch& b_in, const HashParams& p, const CandSink& 
       const uint32_t ncap = (15u + (uint32_t)tile + 16u * (uint32_t)limbs + 8u + 15u + 32u) >> 4;
       lds = 4 * kDnaCtlDwords + (size_t)stage_cap * 8 * (sink.pos ? 2 : 1) + 4 * (size_t)(ncap + (ncap >> (logR - 4)) + 2) + 4 * (size_t)((ncap >> 3) + 8);
     }
-    // (the grid and how the tiles are handed out: launch_rolling_tiles.  The bench kernel -- k = 31, packed tile, 71 vector
-    // registers, ~35 KB of LDS -- has three 512-lane workgroups per CU resident.)
+    // (the grid and how the tiles are handed out: launch_rolling_tiles.  The bench kernel -- k = 31, packed tile, 69 vector
+    // registers (71 for a seed at or above 2^32), ~35 KB of LDS -- has three 512-lane workgroups per CU resident.)
     if (p.ksize == 31) launch_rolling<31, 2>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);
     else if (p.ksize == 21) launch_rolling<21, 2>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);
     else if (p.ksize == 51) launch_rolling<51, 4>(b, p, sink, ntiles, lds, logR, stage_cap, c, dev, s);

@@ -47,6 +47,9 @@ constexpr int ITERS = 2048;
 #define I_BFI(n) "v_bfi_b32 %" #n ", %8, %" #n ", %8\n"
 #define I_OR3(n) "v_or3_b32 %" #n ", %" #n ", %8, %8\n"
 #define I_LSHL_OR(n) "v_lshl_or_b32 %" #n ", %" #n ", 8, %8\n"
+// a ^ b ^ c as v_bitop3_b32 (gfx950 has no v_xor3_b32: the assembler rejects it), third operand a register / an inline constant
+#define I_BITOP3_XOR(n) "v_bitop3_b32 %" #n ", %" #n ", %8, %8 bitop3:0x96\n"
+#define I_BITOP3_XOR_INL(n) "v_bitop3_b32 %" #n ", %" #n ", %8, 31 bitop3:0x96\n"
 
 template <int OP>
 __global__ __launch_bounds__(256) void k32(uint32_t* out, uint32_t b, uint32_t c) {
@@ -84,6 +87,8 @@ __global__ __launch_bounds__(256) void k32(uint32_t* out, uint32_t b, uint32_t c
   if (OP == 31) BODY8(I_BFI)
   if (OP == 32) BODY8(I_OR3)
   if (OP == 33) BODY8(I_LSHL_OR)
+  if (OP == 34) BODY8(I_BITOP3_XOR)
+  if (OP == 35) BODY8(I_BITOP3_XOR_INL)
   uint32_t r = 0;
   for (int i = 0; i < 8; i++) r ^= a[i];
   out[blockIdx.x * blockDim.x + threadIdx.x] = r;
@@ -154,6 +159,7 @@ int main() {
   RUN32(19, "v_xor_b32 literal") RUN32(28, "v_and_b32 literal") RUN32(20, "v_add_u32 inline7") RUN32(21, "v_xor_b32 sgpr") RUN32(22, "v_lshlrev_sdwa")
   RUN32(23, "v_alignbyte_b32") RUN32(24, "v_cmp_lt_u32 vcc") RUN32(25, "v_mov_b32") RUN32(26, "v_add_co_u32") RUN32(27, "v_addc_co_u32")
   RUN32(29, "v_dot4_u32_u8") RUN32(30, "v_dot4_u32_u8 acc") RUN32(31, "v_bfi_b32") RUN32(32, "v_or3_b32") RUN32(33, "v_lshl_or_b32")
+  RUN32(34, "v_bitop3 xor3") RUN32(35, "v_bitop3 xor3 inl")
   RUN64(0, "v_mad_u64_u32") RUN64(1, "v_lshl_add_u64") RUN64(2, "v_lshlrev_b64") RUN64(3, "v_lshrrev_b64")
   RUN64(4, "mad_u64 v,v,v64") RUN64(5, "mad_u64 v,s,0") RUN64(6, "mad_u64 v,v,0") RUN64(7, "v_mov_b64") RUN64(8, "lshl_add_u64 sh0")
   RUN64(9, "v_min_f64 denorm") RUN64(10, "v_min_f64 normal")
