@@ -286,6 +286,48 @@ int smh_index_gather(SmhIndex *index, const KmerMinHash *query, uint32_t thresho
                      uint32_t rows_capacity, uint32_t *n_rows, uint32_t *assigned);
 uint32_t smh_gather_rounds_per_sync(void);   /* rounds queued between two read-backs (tests, tools) */
 
+/* Gather of many queries in one call, through the index's hash directory (the directory is the one
+ * "Matching records" describes: it is built by the first match or gather-many call on the index and kept).
+ *   Equality   For every query q of the batch the rows, their number and `assigned` are exactly what
+ *              smh_index_gather(index, queries[q], threshold_common, rows_q, rows_capacity, ...) gives: the tie rule,
+ *              threshold_common == 0 read as 1, common_original, size_match, abund_sum (1 per hash for a query without
+ *              abundances), and the capacity ending the loop early.  Queries do not interact: the same sketch given twice
+ *              gives the same result twice.  No result depends on chunking, budgets or the order of atomics; every output
+ *              is an integer, so parity is equality.
+ *   Outputs    row_offsets (the caller's, n_queries + 1 entries): the rows of query q are
+ *              (*rows)[row_offsets[q] .. row_offsets[q + 1]).  *rows is a malloc'ed array of row_offsets[n_queries] rows
+ *              (at least one element is allocated); the caller frees it with free().  query_offsets (nullable,
+ *              n_queries + 1 entries): the running sum of the queries' sizes.  assigned (nullable, that sum of entries):
+ *              the positions of query q start at query_offsets[q]; 0xffffffff for the positions nobody consumed.
+ *   Errors     decided before the device is touched, and nothing is written.  Each query is checked as smh_index_gather
+ *              checks it (num != 0 on the query or on any node: SOURMASH_ERROR_CODE_MSG; incompatible: 101-104); when
+ *              several queries fail, the error of the LOWEST failing query is reported and the message names that query.
+ *              An index of 2^31 or more resident hashes is refused (MSG): the directory takes fewer.  row_offsets == NULL
+ *              or rows == NULL is refused.  n_queries == 0, empty queries, an empty index and queries that share nothing
+ *              give zero rows and no error.
+ * smh_index_gather_many       the queries are sketches.  A query whose state lives in HBM is staged device to device (it is
+ *                             not brought to the host); the host-resident queries go up in one upload.
+ * smh_index_gather_block_dev  the CSR / device form (next to smh_compare_block_dev): query q is
+ *                             q_hashes_dev[q_offsets[q] .. q_offsets[q + 1]), q_offsets on the host (n_queries + 1, ascending),
+ *                             q_abunds_dev (nullable: 1 each) one u64 per hash; assigned counts from q_offsets[0].  A CSR
+ *                             carries no parameters, so the index's nodes must all be scaled sketches that agree in ksize,
+ *                             molecule, seed and max_hash (else MSG).  Hashes must ascend strictly inside a query: the
+ *                             caller's contract, as for the compare block.  stream: the caller's.
+ * smh_gather_many_set_budget  the (query, node) counters one chunk of the batch may hold: the batch is cut into chunks at
+ * smh_gather_many_budget      query boundaries, a query alone always makes a chunk.  0 restores the default of 2^26 -- a memory
+ *                             cap, not a measured optimum.  Process-wide; results never depend on it.
+ * Per chunk the work is one probe per query hash plus its hits (not a pass over the resident hashes), and one pair of
+ * launches serves a round of every query of the chunk; smh_gather_rounds_per_sync() rounds are queued between two
+ * read-backs of 8 bytes. */
+int smh_index_gather_many(SmhIndex *index, const KmerMinHash *const *queries, uint32_t n_queries, uint32_t threshold_common,
+                          uint32_t rows_capacity, uint64_t *row_offsets, SmhGatherRow **rows, uint64_t *query_offsets,
+                          uint32_t *assigned);
+int smh_index_gather_block_dev(SmhIndex *index, const uint64_t *q_hashes_dev, const uint64_t *q_abunds_dev,
+                               const uint64_t *q_offsets, uint32_t n_queries, uint32_t threshold_common, uint32_t rows_capacity,
+                               uint64_t *row_offsets, SmhGatherRow **rows, uint32_t *assigned, void *stream);
+void smh_gather_many_set_budget(uint64_t pairs);
+uint64_t smh_gather_many_budget(void);
+
 /* Angular similarity on abundances: what `sourmash compare` and `sourmash search` report by default for sketches that
  * track abundances.  The reference crate has no weighted compare, so the rules are fixed here -- DESIGN.md 3.10, restated
  * in tests/angular_restatement.py.  For two sketches A and B that both track abundances, hashes ascending and distinct, one
@@ -585,7 +627,10 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * "sbt_bins", "sbt_nodes", "sbt_leaves", "sbt_build", "parse_scan" (tile summaries and their scan), "parse_compact",
  * "gather_hits" (the membership pass), "gather_invert" (degree scan + inverted lists), "gather_rounds" (one entry per batch
  * of smh_gather_rounds_per_sync() rounds), "angular_block" (the angular similarity's block kernel), "match_probe" (the runs of a
- * fold against the hash directory), "match_tally" (the per-record tally: its LDS launch, and one entry per dense round). */
+ * fold against the hash directory), "match_tally" (the per-record tally: its LDS launch, and one entry per dense round),
+ * "gather_many_probe" (a chunk's probe, counts and sizing), "gather_many_fill" (the scan and the hit lists),
+ * "gather_many_rounds" (one entry per batch of smh_gather_rounds_per_sync() rounds of a chunk).  Event counters under the
+ * same call: "gather_many_chunk" (chunks run), "match_directory_built". */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

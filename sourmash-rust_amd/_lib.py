@@ -158,6 +158,12 @@ _SIGS = {
     "smh_index_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SmhGatherRow), C.c_uint32, C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint32)]),
     "smh_gather_rounds_per_sync": (C.c_uint32, []),
+    "smh_index_gather_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, u64p,
+                                        C.POINTER(C.POINTER(SmhGatherRow)), u64p, C.POINTER(C.c_uint32)]),
+    "smh_index_gather_block_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, u64p,
+                                             C.POINTER(C.POINTER(SmhGatherRow)), C.POINTER(C.c_uint32), C.c_void_p]),
+    "smh_gather_many_set_budget": (None, [C.c_uint64]),
+    "smh_gather_many_budget": (C.c_uint64, []),
     "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
     "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
     "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),

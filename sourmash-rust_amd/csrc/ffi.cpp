@@ -734,6 +734,51 @@ int smh_index_gather(SmhIndex* index, const KmerMinHash* query, uint32_t thresho
 }
 uint32_t smh_gather_rounds_per_sync(void) { return smh::kGatherRoundsPerSync; }
 
+namespace {
+// the rows handed out the way match hands out hit_hashes: malloc'ed, one element at least
+void gather_many_rows_out(const std::vector<smh::GatherRow>& got, SmhGatherRow** rows) {
+  SmhGatherRow* out = (SmhGatherRow*)malloc((got.empty() ? 1 : got.size()) * sizeof(SmhGatherRow));
+  if (!out) smh::throw_internal("out of memory");
+  if (!got.empty()) memcpy(out, got.data(), got.size() * sizeof(SmhGatherRow));
+  *rows = out;
+}
+}  // namespace
+
+int smh_index_gather_many(SmhIndex* index, const KmerMinHash* const* queries, uint32_t n_queries, uint32_t threshold_common,
+                          uint32_t rows_capacity, uint64_t* row_offsets, SmhGatherRow** rows, uint64_t* query_offsets, uint32_t* assigned) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();   // first: without a device the call says so, whatever it was handed
+    require(index, "index"); require(row_offsets, "row_offsets"); require(rows, "rows");
+    if (n_queries) require(queries, "queries");
+    std::vector<const smh::KmerMinHash*> v(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) { require(queries[q], "queries[q]"); v[q] = queries[q]; }
+    std::vector<smh::GatherRow> got;
+    index->gather_many(v.data(), n_queries, threshold_common, rows_capacity, row_offsets, &got, query_offsets, assigned, dev);
+    gather_many_rows_out(got, rows);
+  });
+}
+
+int smh_index_gather_block_dev(SmhIndex* index, const uint64_t* q_hashes_dev, const uint64_t* q_abunds_dev, const uint64_t* q_offsets,
+                               uint32_t n_queries, uint32_t threshold_common, uint32_t rows_capacity, uint64_t* row_offsets,
+                               SmhGatherRow** rows, uint32_t* assigned, void* stream) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    require(index, "index"); require(row_offsets, "row_offsets"); require(rows, "rows"); require(q_offsets, "q_offsets");
+    // a CSR carries no parameters: the index must speak for itself with one voice
+    if (!(index->uniform && index->all_scaled))
+      throw Error(smh::kMsg, "gather_many: the device form needs an index whose nodes are scaled sketches with the same ksize, molecule, "
+                             "seed and max_hash");
+    if (n_queries && q_offsets[n_queries] != q_offsets[0]) require(q_hashes_dev, "q_hashes_dev");
+    std::vector<smh::GatherRow> got;
+    index->gather_many_dev(q_hashes_dev, q_abunds_dev, q_offsets, n_queries, threshold_common, rows_capacity, row_offsets, &got, assigned,
+                           dev, dev.user_stream(stream));
+    gather_many_rows_out(got, rows);
+  });
+}
+
+void smh_gather_many_set_budget(uint64_t pairs) { smh::g_gather_many_budget = pairs ? pairs : smh::kGatherManyBudget; }
+uint64_t smh_gather_many_budget(void) { return smh::g_gather_many_budget; }
+
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {
   return pad_code([&] { require(rows, "rows"); require(cols, "cols"); rows->compare(*cols, jaccard, common, size, count_common, containment); });

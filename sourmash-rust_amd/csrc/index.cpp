@@ -1,5 +1,5 @@
 // index.cpp -- smh::ResidentIndex: construction (from host nodes, or as the cut of a parent made on the device), parameter
-// checks, the block route and its cached dictionary, one sketch, gather.
+// checks, the block route and its cached dictionary, the hash directory match and gather_many share, one sketch, gather.
 #include "index.hpp"
 
 #include <algorithm>
@@ -124,6 +124,51 @@ ResidentIndex::~ResidentIndex() {
   { std::lock_guard<std::mutex> g(registry_mu()); registry().erase(this); }
   drop_dict();
   drop_match_dir();
+}
+
+struct MatchDir {
+  DeviceBuffer U, starts, owners;
+  uint32_t n_hashes = 0, n_pairs = 0;
+  MatchDirectory view() const { return {U.as<uint64_t>(), starts.as<uint32_t>(), owners.as<uint32_t>(), n_hashes, n_pairs}; }
+};
+
+void ResidentIndex::drop_match_dir() { delete match_dir; match_dir = nullptr; }
+
+void ResidentIndex::check_directory_size(const char* who) const {
+  const uint64_t total = h_offsets.back() - h_offsets.front();
+  if (total >= (1ull << 31))
+    throw Error(kMsg, std::string(who) + ": the index holds " + std::to_string(total) + " hashes; the directory takes fewer than 2^31");
+}
+
+// sorted distinct hashes of all nodes + who holds each: owner ids, a stable sort by hash, one run-length pass
+MatchDirectory ResidentIndex::ensure_directory(const char* who, Device& dev, hipStream_t s) {
+  if (match_dir) return match_dir->view();
+  check_directory_size(who);
+  const uint64_t total = h_offsets.back() - h_offsets.front();
+  auto d = std::make_unique<MatchDir>();
+  d->n_pairs = (uint32_t)total;
+  if (total == 0) { match_dir = d.release(); return match_dir->view(); }
+  PoolBlock k0(total * 8), k1(total * 8), v0(total * 4), v1(total * 4), uq(total * 8), st(total * 4 + 4), cnt(4);
+  HIP_CHECK(hipMemcpyAsync(k0.ptr, hashes.as<uint64_t>() + h_offsets.front(), total * 8, hipMemcpyDeviceToDevice, s));
+  launch_match_owner_ids(offsets.as<uint64_t>(), n, total, v0.as<uint32_t>(), dev, s);
+  const int cur = radix_sort_u64_v32(k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(), total, dev.scratch, s);
+  run_length_encode_u64_async((cur ? k1 : k0).as<uint64_t>(), total, uq.as<uint64_t>(), st.as<uint32_t>(), dev.scratch, s, nullptr, nullptr,
+                              cnt.as<uint32_t>(), nullptr);
+  uint32_t nu = 0;
+  HIP_CHECK(hipMemcpyAsync(&nu, cnt.ptr, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  d->n_hashes = nu;
+  d->U.ensure((size_t)nu * 8);
+  d->starts.ensure((size_t)nu * 4);
+  d->owners.ensure(total * 4);
+  HIP_CHECK(hipMemcpyAsync(d->U.ptr, uq.ptr, (size_t)nu * 8, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d->starts.ptr, st.ptr, (size_t)nu * 4, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d->owners.ptr, (cur ? v1 : v0).ptr, total * 4, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  k0.synced = k1.synced = v0.synced = v1.synced = uq.synced = st.synced = cnt.synced = true;
+  dev.count("match_directory_built");
+  match_dir = d.release();
+  return match_dir->view();
 }
 
 void ResidentIndex::drop_all_dictionaries() {

@@ -20,8 +20,8 @@ struct ResidentIndex {
   // the index with itself and kept: later ones skip the pre-pass (the nodes of an index never change)
   CollectionDict* dict = nullptr;
   uint32_t dict_split = 0;      // the frequent-hash setting the dictionary was built under
-  // the hash directory (match.cpp): the sorted distinct hashes of all nodes and who holds each, built by the
-  // first match() and kept like `dict`
+  // the hash directory: the sorted distinct hashes of all nodes and who holds each, built by the first
+  // match() or gather_many() and kept like `dict`
   struct MatchDir* match_dir = nullptr;
   // angular similarity.  has_abunds: EVERY node tracks abundances and every abundance vector matches its
   // hashes; h_abunds then holds them narrowed to u32 (a copy, like the hashes) until the first angular call uploads them
@@ -68,7 +68,21 @@ struct ResidentIndex {
   void check_matchable() const;   // the refusals (kMsg): needs no device
   void match(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n_records, MatchRow* rows,
              uint64_t* hit_offsets, std::vector<uint64_t>* hit_hashes, hipStream_t s);
+  // The directory, built on the first call (counter match_directory_built).  An index of 2^31 or more hashes is refused
+  // (kMsg, the message begins with `who`); check_directory_size is that refusal alone and needs no device.
+  void check_directory_size(const char* who) const;
+  MatchDirectory ensure_directory(const char* who, Device& dev, hipStream_t s);
   void drop_match_dir();
+  // (gather_many.cpp) Gather of a batch of queries (the rules: include/sourmash_amd.h, smh_index_gather_many).  row_offsets
+  // (n_queries + 1), *rows (row_offsets[n_queries] rows) and query_offsets (nullable, n_queries + 1) are written only when
+  // the call succeeds; assigned (nullable, the queries' positions one after another) is filled chunk by chunk, after every
+  // refusal the rules name.
+  void gather_many(const KmerMinHash* const* queries, uint32_t n_queries, uint32_t threshold_common, uint32_t rows_capacity,
+                   uint64_t* row_offsets, std::vector<GatherRow>* rows, uint64_t* query_offsets, uint32_t* assigned, Device& dev);
+  // the CSR / device form: query q = q_hashes_dev[q_offsets[q] .. q_offsets[q + 1]); assigned counts from q_offsets[0]
+  void gather_many_dev(const uint64_t* q_hashes_dev, const uint64_t* q_abunds_dev, const uint64_t* q_offsets, uint32_t n_queries,
+                       uint32_t threshold_common, uint32_t rows_capacity, uint64_t* row_offsets, std::vector<GatherRow>* rows,
+                       uint32_t* assigned, Device& dev, hipStream_t s);
   void angular_ensure(const char* what, hipStream_t s);   // (angular.cpp from here) the first angular call: abundances to HBM, norms
   void norms2(uint64_t* out);
   void angular(ResidentIndex& cols, uint64_t* dot, double* cosine, double* angular);
@@ -107,6 +121,15 @@ extern uint64_t g_angular_prune_min_pairs, g_angular_walked, g_angular_skipped;
 // buffers, 256 MiB of counters), not a measured optimum.
 constexpr uint64_t kMatchPairBudget = 1ull << 26;
 extern uint64_t g_match_pair_budget;
+
+// gather_many.cpp: the (query, node) counters one chunk of a batch may hold (three u32 arrays of that size: 768 MiB at the
+// default) -- a memory cap, not a measured optimum.  gather_many_chunk_end: the chunk that starts at query `a` ends in front
+// of the returned query -- as many queries as the budget holds counters for, one at least, at most kGatherManyMaxQueries
+// (the grid's second dimension) and fewer than 2^32 - 1 positions unless it is a single query.
+constexpr uint64_t kGatherManyBudget = 1ull << 26;
+constexpr uint32_t kGatherManyMaxQueries = 65535;
+extern uint64_t g_gather_many_budget;
+uint32_t gather_many_chunk_end(const uint64_t* q_offsets, uint32_t a, uint32_t n_queries, uint32_t n_nodes, uint64_t budget);
 
 // downsample.cpp (the rules are in include/sourmash_amd.h, "Downsampling").  `out` is a fresh sketch: it
 // receives src's parameters with max_hash / num replaced and the kept prefix.  A state that lives in HBM is cut there into a

@@ -1,5 +1,6 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
-// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip).
+// compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
+// gather_many_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -419,5 +420,43 @@ void launch_match_dense(const MatchDirectory& d, const uint32_t* rank, MatchRow*
 // out[at[i]] = run_hash[i] for every hit run (at: the exclusive scan of the hit flags)
 void launch_match_hit_scatter(const uint64_t* run_hash, const uint32_t* rank, const uint32_t* at, uint32_t nruns, uint64_t* out, Device& dev,
                               hipStream_t s);
+
+// --- gather_many_kernels.hip -----------------------------------------------------------
+// Gather of a batch of queries through the hash directory (the rules are in include/sourmash_amd.h,
+// smh_index_gather_many).  A chunk is a run of consecutive queries; its positions are those of its queries one after another.
+struct GatherManyQuery { uint32_t done, rounds, best, cap; };   // cap: the rows this query may write (set by the host)
+struct GatherManyState {
+  uint32_t live;         // queries of the chunk that are not done (set by the host to the chunk's queries)
+  uint32_t max_rounds;   // the largest number of rows any query has written
+  unsigned long long hits;   // (query position, node) pairs of the chunk
+};
+struct GatherManyChunk {
+  const uint64_t* hashes = nullptr;   // T hashes: the chunk's queries one after another, ascending strictly inside a query
+  const uint64_t* counts = nullptr;   // T abundances, or null (1 each)
+  const uint32_t* qoff = nullptr;     // nq + 1: where each query starts among the T positions
+  uint32_t nq = 0, T = 0, n = 0;      // queries, positions, nodes of the index
+  uint32_t* rank = nullptr;           // T: the position's rank in the directory or kMatchMiss
+  uint32_t* c0 = nullptr;             // nq x n: |Q_q ^ S_i| (zeroed by the caller before the probe)
+  uint32_t* c = nullptr;              // nq x n: the round counters (zeroed by the caller before the fill, which leaves c == c0)
+  uint32_t* loff = nullptr;           // nq x n + 1: where the hit list of (query, node) starts in `lists`
+  uint32_t* lists = nullptr;          // `hits` positions
+  uint32_t* assigned = nullptr;       // T (caller: 0xff bytes)
+  const uint64_t* rowoff = nullptr;   // nq: where each query's rows start in `rows`
+  GatherRow* rows = nullptr;
+  GatherManyQuery* qs = nullptr;      // nq
+  GatherManyState* st = nullptr;
+};
+// rank, c0 and st->hits of the chunk, then qcnt[q] = the nodes with c0 >= threshold.  Profile name gather_many_probe.
+void launch_gather_many_probe(const MatchDirectory& d, const GatherManyChunk& ck, uint32_t threshold, uint32_t* qcnt, Device& dev,
+                              hipStream_t s);
+// loff (the scan of c0) and the hit lists; c counts up to c0 on the way.  Profile name gather_many_fill.
+void launch_gather_many_fill(const MatchDirectory& d, const GatherManyChunk& ck, Device& dev, hipStream_t s);
+// `rounds` rounds of every query of the chunk: 2 launches each.  node_offsets: the index's CSR offsets (size_match);
+// sub_grid: workgroups per query of the subtract.  Profile name gather_many_rounds (one entry per call).
+void launch_gather_many_rounds(const MatchDirectory& d, const GatherManyChunk& ck, const uint64_t* node_offsets, uint32_t threshold,
+                               uint32_t sub_grid, uint32_t rounds, Device& dev, hipStream_t s);
+// out[p] = the abundance of position p of a device-resident sketch held as run starts (the last run ends at total); starts
+// null: 1 each
+void launch_gather_many_weights(const uint32_t* starts, uint32_t total, uint32_t n, uint64_t* out, hipStream_t s);
 
 }  // namespace smh

@@ -1,5 +1,5 @@
-// match.cpp -- ResidentIndex::match (the rules are in include/sourmash_amd.h, "Matching records"): the hash
-// directory of an index and its cache, the folds of a batch cut at record boundaries, and per fold the grouped fold's own
+// match.cpp -- ResidentIndex::match (the rules are in include/sourmash_amd.h, "Matching records"): the folds
+// of a batch cut at record boundaries (the index's hash directory is index.cpp's), and per fold the grouped fold's own
 // sequence (hash with positions, positions to records, two sorts, the two-key run-length pass) followed by the probe, the
 // tally with its two regimes and the read-back.  The kernels are in match_kernels.hip.
 #include <algorithm>
@@ -14,43 +14,8 @@ namespace smh {
 
 uint64_t g_match_pair_budget = kMatchPairBudget;
 
-struct MatchDir {
-  DeviceBuffer U, starts, owners;
-  uint32_t n_hashes = 0, n_pairs = 0;
-  MatchDirectory view() const { return {U.as<uint64_t>(), starts.as<uint32_t>(), owners.as<uint32_t>(), n_hashes, n_pairs}; }
-};
-
 namespace {
 [[noreturn]] void refuse(const std::string& what) { throw Error(kMsg, "match: " + what); }
-
-// sorted distinct hashes of all nodes + who holds each: owner ids, a stable sort by hash, one run-length pass
-MatchDir* build_directory(const ResidentIndex& idx, Device& dev, hipStream_t s) {
-  const uint64_t total = idx.h_offsets.back() - idx.h_offsets.front();
-  if (total >= (1ull << 31)) refuse("the index holds " + std::to_string(total) + " hashes; the directory takes fewer than 2^31");
-  auto d = std::make_unique<MatchDir>();
-  d->n_pairs = (uint32_t)total;
-  if (total == 0) return d.release();
-  PoolBlock k0(total * 8), k1(total * 8), v0(total * 4), v1(total * 4), uq(total * 8), st(total * 4 + 4), cnt(4);
-  HIP_CHECK(hipMemcpyAsync(k0.ptr, idx.hashes.as<uint64_t>() + idx.h_offsets.front(), total * 8, hipMemcpyDeviceToDevice, s));
-  launch_match_owner_ids(idx.offsets.as<uint64_t>(), idx.n, total, v0.as<uint32_t>(), dev, s);
-  const int cur = radix_sort_u64_v32(k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(), total, dev.scratch, s);
-  run_length_encode_u64_async((cur ? k1 : k0).as<uint64_t>(), total, uq.as<uint64_t>(), st.as<uint32_t>(), dev.scratch, s, nullptr, nullptr,
-                              cnt.as<uint32_t>(), nullptr);
-  uint32_t nu = 0;
-  HIP_CHECK(hipMemcpyAsync(&nu, cnt.ptr, 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  d->n_hashes = nu;
-  d->U.ensure((size_t)nu * 8);
-  d->starts.ensure((size_t)nu * 4);
-  d->owners.ensure(total * 4);
-  HIP_CHECK(hipMemcpyAsync(d->U.ptr, uq.ptr, (size_t)nu * 8, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(d->starts.ptr, st.ptr, (size_t)nu * 4, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(d->owners.ptr, (cur ? v1 : v0).ptr, total * 4, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  k0.synced = k1.synced = v0.synced = v1.synced = uq.synced = st.synced = cnt.synced = true;
-  dev.count("match_directory_built");
-  return d.release();
-}
 
 // The rows of a fold into the caller's pageable array through two page-locked halves: the copy out of one half runs while
 // the transfer into the other is in flight (a pageable destination would be staged by the runtime, one piece after another).
@@ -71,8 +36,6 @@ void fetch_rows(const MatchRow* d_rows, MatchRow* out, size_t n, Engine& E, hipS
   }
 }
 }  // namespace
-
-void ResidentIndex::drop_match_dir() { delete match_dir; match_dir = nullptr; }
 
 void ResidentIndex::check_matchable() const {
   if (n == 0) refuse("the index holds no node (ksize, seed and max_hash are those of node 0)");
@@ -112,8 +75,7 @@ void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint
   Device& dev = Device::get();
   Engine& E = Engine::get();
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-  if (!match_dir) match_dir = build_directory(*this, dev, s);
-  const MatchDirectory dir = match_dir->view();
+  const MatchDirectory dir = ensure_directory("match", dev, s);
 
   E.offbuf.ensure((size_t)(nrec + 1) * 8);
   E.grpbuf.ensure((size_t)nrec * 4);

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 
+#include "directory_probe.hpp"
 #include "kernels.hpp"
 
 namespace smh {
@@ -33,12 +34,6 @@ constexpr uint32_t kShortOwners = 8;   // owner lists up to this length are walk
 __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
   for (int off = 32; off; off >>= 1) { const uint64_t o = __shfl_xor(v, off); v = o > v ? o : v; }
   return v;
-}
-
-// owners of rank g: d.owners[b .. e)
-__device__ __forceinline__ void owner_range(const MatchDirectory& d, uint32_t g, uint32_t* b, uint32_t* e) {
-  *b = d.starts[g];
-  *e = g + 1 < d.n_hashes ? d.starts[g + 1] : d.n_pairs;
 }
 
 __global__ __launch_bounds__(256) void k_match_owner_ids(const uint64_t* __restrict__ offsets, uint32_t n, uint64_t total,
@@ -54,7 +49,7 @@ __global__ __launch_bounds__(256) void k_match_owner_ids(const uint64_t* __restr
   }
 }
 
-// m = ceil(n_hashes / 2^shift) <= kMatchSamples samples; shift == 0: all of U sits in LDS and no global level is left
+// shift, m: directory_sampling (the search itself is directory_probe.hpp's, shared with gather_many_kernels.hip)
 __global__ __launch_bounds__(256) void k_match_probe(MatchDirectory d, uint32_t shift, uint32_t m, const uint64_t* __restrict__ run_hash,
                                                      const uint64_t* __restrict__ run_rec, const uint32_t* __restrict__ run_start,
                                                      uint32_t nruns, uint32_t ncand, uint32_t rec0, MatchRow* __restrict__ rows,
@@ -62,37 +57,16 @@ __global__ __launch_bounds__(256) void k_match_probe(MatchDirectory d, uint32_t 
                                                      uint32_t* __restrict__ rank_out, uint32_t* __restrict__ hit_flag) {
   __shared__ uint64_t samp[kMatchSamples];
   const uint32_t tid = threadIdx.x, lane = tid & 63;
-  for (uint32_t t = tid; t < m; t += 256) samp[t] = d.U[(uint64_t)t << shift];
-  __syncthreads();
+  directory_stage_samples(d, shift, m, samp);
   const uint32_t nU = d.n_hashes;
   for (uint64_t i0 = (uint64_t)blockIdx.x * 256; i0 < nruns; i0 += (uint64_t)gridDim.x * 256) {
     const uint32_t i = (uint32_t)i0 + tid;   // (whole waves stay in the loop: the shuffles below see every lane)
     const bool ok = i < nruns;
     const uint64_t h = ok ? run_hash[i] : 0;
-    // js = number of samples below h
-    uint32_t lo = 0, len = ok ? m : 0;
-    while (len > 0) {
-      const uint32_t half = len >> 1, mid = lo + half;
-      const bool lt = samp[mid] < h;
-      lo = lt ? mid + 1 : lo;
-      len = lt ? len - half - 1 : half;
-    }
-    // sample js - 1 < h <= sample js: the lower bound lies in ((js - 1) << s, js << s]
-    uint32_t g = 0;
-    if (lo != 0) {
-      const uint32_t wlo = ((lo - 1) << shift) + 1;
-      const uint32_t whi = (uint32_t)min((uint64_t)lo << shift, (uint64_t)nU);
-      g = wlo; len = whi - wlo;
-      while (len > 0) {
-        const uint32_t half = len >> 1, mid = g + half;
-        const bool lt = d.U[mid] < h;
-        g = lt ? mid + 1 : g;
-        len = lt ? len - half - 1 : half;
-      }
-    }
+    const uint32_t g = directory_lower_bound(d, samp, shift, m, h, ok);
     const bool hit = ok && g < nU && d.U[g] == h;
     uint32_t deg = 0;
-    if (hit) { uint32_t b, e; owner_range(d, g, &b, &e); deg = e - b; }
+    if (hit) { uint32_t b, e; directory_owner_range(d, g, &b, &e); deg = e - b; }
     if (ok) {
       rank_out[i] = hit ? g : kMatchMiss;
       if (hit_flag) hit_flag[i] = hit ? 1u : 0u;
@@ -148,7 +122,7 @@ __global__ __launch_bounds__(256) void k_match_tally(MatchDirectory d, const uin
       const uint32_t k = k0 + lane;
       const uint32_t g = k < cnt ? rank[first + k] : kMatchMiss;
       uint32_t b = 0, e = 0;
-      if (g != kMatchMiss) owner_range(d, g, &b, &e);
+      if (g != kMatchMiss) directory_owner_range(d, g, &b, &e);
       const uint32_t deg = e - b;
       uint32_t incl = deg;
       for (int off = 1; off < 64; off <<= 1) {
@@ -194,7 +168,7 @@ __global__ __launch_bounds__(256) void k_match_dense_count(MatchDirectory d, con
     const uint32_t k = (uint32_t)k0 + lane;
     const uint32_t g = k < cnt ? rank[first + k] : kMatchMiss;
     uint32_t b = 0, e = 0;
-    if (g != kMatchMiss) owner_range(d, g, &b, &e);
+    if (g != kMatchMiss) directory_owner_range(d, g, &b, &e);
     const bool longl = e - b > kShortOwners;
     if (!longl)
       for (uint32_t t = b; t < e; t++) atomicAdd(&c[d.owners[t]], 1u);
@@ -257,9 +231,8 @@ void launch_match_probe(const MatchDirectory& d, const uint64_t* run_hash, const
                         uint32_t nruns, uint32_t ncand, uint32_t rec0, MatchRow* rows, uint32_t* rec_first,
                         unsigned long long* rec_pairs, uint32_t* rank_out, uint32_t* hit_flag, Device& dev, hipStream_t s) {
   if (nruns == 0) return;
-  uint32_t shift = 0;
-  while ((((uint64_t)d.n_hashes + (1ull << shift) - 1) >> shift) > kMatchSamples) shift++;
-  const uint32_t m = (uint32_t)(((uint64_t)d.n_hashes + (1ull << shift) - 1) >> shift);
+  uint32_t shift = 0, m = 0;
+  directory_sampling(d.n_hashes, &shift, &m);
   dev.prof_begin(s);
   hipLaunchKernelGGL(k_match_probe, dim3(grid_for(nruns, 256, dev)), dim3(256), 0, s, d, shift, m, run_hash, run_rec, run_start, nruns,
                      ncand, rec0, rows, rec_first, rec_pairs, rank_out, hit_flag);

@@ -4,6 +4,7 @@
   most_common (scaffold)    reference src/index/sbt.rs:361-370 (nearest leaf = arg-max count_common)
   ResidentIndex.gather      the greedy decomposition of a query (no counterpart in the reference crate: the rules are those
                             of include/sourmash_amd.h, smh_index_gather)
+  ResidentIndex.gather_many the same decomposition for a batch of queries in one device call (smh_index_gather_many)
   ResidentIndex.match       the k-mers of every record of a batch the index knows, and each record's best node (no counterpart
                             either: include/sourmash_amd.h, "Matching records")
 
@@ -55,6 +56,33 @@ def max_hash_of_scaled(scaled):
 
 def _is_scaled(mh):
     return mh.num == 0 and mh.max_hash != 0
+
+
+def _gather_result(query, rows, n_rows, assigned, scaled, abund_stats):
+    """GatherResult of one query from the integers of the device (rows: n_rows SmhGatherRow; assigned: the query's
+    positions): the derived floats of gather() and gather_many()."""
+    nq = len(assigned)
+    # a query without abundances weighs 1 per hash: its statistics are known without looking at it
+    ab = query.abunds_np() if query.track_abundance and abund_stats and n_rows else None
+    flat = not query.track_abundance
+    total_ab = nq if flat else int(ab.sum(dtype=np.uint64)) if ab is not None else None
+    out, left = [], nq
+    if ab is not None:   # the positions of round r, for every r at once
+        order = np.argsort(assigned, kind="stable")
+        cuts = np.searchsorted(assigned[order], np.arange(n_rows + 1, dtype=np.uint32))
+    for r in range(n_rows):
+        w = rows[r]
+        left -= w.common_remaining
+        mine = ab[order[cuts[r]:cuts[r + 1]]] if ab is not None else None
+        out.append(GatherRecord(
+            w.match, w.common_remaining, w.common_original, w.size_match, w.abund_sum,
+            w.common_original / nq, w.common_remaining / w.size_match, w.common_remaining / nq,
+            w.abund_sum / total_ab if total_ab is not None else None,
+            w.abund_sum / w.common_remaining,
+            1.0 if flat else float(np.median(mine)) if ab is not None else None,
+            0.0 if flat else float(np.std(mine)) if ab is not None else None,
+            scaled * left))
+    return GatherResult(out, assigned)
 
 
 def search_minhashes(nodes, query, threshold):
@@ -224,27 +252,54 @@ class ResidentIndex:
         n_rows = C.c_uint32()
         call(self._L.smh_index_gather, self._h, query._p, thr, rows, cap, C.byref(n_rows),
              assigned.ctypes.data_as(C.POINTER(C.c_uint32)))
-        # a query without abundances weighs 1 per hash: its statistics are known without looking at it
-        ab = query.abunds_np() if query.track_abundance and abund_stats and n_rows.value else None
-        flat = not query.track_abundance
-        total_ab = nq if flat else int(ab.sum(dtype=np.uint64)) if ab is not None else None
-        out, left = [], nq
-        if ab is not None:   # the positions of round r, for every r at once
-            order = np.argsort(assigned, kind="stable")
-            cuts = np.searchsorted(assigned[order], np.arange(n_rows.value + 1, dtype=np.uint32))
-        for r in range(n_rows.value):
-            w = rows[r]
-            left -= w.common_remaining
-            mine = ab[order[cuts[r]:cuts[r + 1]]] if ab is not None else None
-            out.append(GatherRecord(
-                w.match, w.common_remaining, w.common_original, w.size_match, w.abund_sum,
-                w.common_original / nq, w.common_remaining / w.size_match, w.common_remaining / nq,
-                w.abund_sum / total_ab if total_ab is not None else None,
-                w.abund_sum / w.common_remaining,
-                1.0 if flat else float(np.median(mine)) if ab is not None else None,
-                0.0 if flat else float(np.std(mine)) if ab is not None else None,
-                scaled * left))
-        return GatherResult(out, assigned)
+        return _gather_result(query, rows, n_rows.value, assigned, scaled, abund_stats)
+
+    def gather_many(self, queries, threshold_bp=0, scaled=None, max_rows=None, abund_stats=True, downsample=False):
+        """gather() of every query of a batch in one device call (smh_index_gather_many): a list of GatherResult, one per
+        query in order, equal field for field to [self.gather(q, ...same arguments...) for q in queries].  The batch is
+        looked up in the index's hash directory (built by the first such call, or by match(), and kept) and a round of every
+        query shares one pair of launches.  downsample=True: the queries are grouped by the max_hash at which each meets
+        the index; every group is one call."""
+        queries = list(queries)
+        if downsample:
+            met = [self._meet_sketch(q) for q in queries]
+            groups = {}
+            for k, (idx, _) in enumerate(met):
+                groups.setdefault(id(idx), (idx, []))[1].append(k)
+            out = [None] * len(queries)
+            for idx, members in groups.values():
+                got = idx.gather_many([met[k][1] for k in members], threshold_bp, scaled, max_rows, abund_stats)
+                for k, res in zip(members, got):
+                    out[k] = res
+            return out
+        nqs = len(queries)
+        scaleds, thrs = [], set()
+        for q in queries:
+            mx = q.max_hash
+            sc = scaled if scaled is not None else scaled_of_max_hash(mx) if mx else 1
+            scaleds.append(sc)
+            thrs.add(int(math.ceil(threshold_bp / sc)))
+        if len(thrs) > 1:   # (queries the call accepts share their max_hash; the others are refused by a call of their own)
+            return [self.gather(q, threshold_bp, scaled, max_rows, abund_stats) for q in queries]
+        thr = thrs.pop() if thrs else 0
+        cap = len(self) if max_rows is None else int(max_rows)
+        arr = (C.c_void_p * max(nqs, 1))(*[q._p for q in queries])
+        row_off = np.zeros(nqs + 1, dtype=np.uint64)
+        q_off = np.zeros(nqs + 1, dtype=np.uint64)
+        assigned = np.empty(sum(len(q) for q in queries), dtype=np.uint32)   # (the call writes every entry)
+        rows_p = C.POINTER(SmhGatherRow)()
+        call(self._L.smh_index_gather_many, self._h, arr, nqs, thr, cap, row_off.ctypes.data_as(u64p), C.byref(rows_p),
+             q_off.ctypes.data_as(u64p), assigned.ctypes.data_as(C.POINTER(C.c_uint32)))
+        from .minhash import _free
+        try:
+            out = []
+            for k, q in enumerate(queries):
+                a, b = int(row_off[k]), int(row_off[k + 1])
+                rows = [rows_p[r] for r in range(a, b)]
+                out.append(_gather_result(q, rows, b - a, assigned[int(q_off[k]):int(q_off[k + 1])], scaleds[k], abund_stats))
+        finally:
+            _free(C.cast(rows_p, C.c_void_p))
+        return out
 
     def match(self, records, hits=False, stream=None):
         """Every record of a batch against the index (smh_index_match_*; the rules: include/sourmash_amd.h, "Matching

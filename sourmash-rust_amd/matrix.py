@@ -168,6 +168,16 @@ def set_match_pair_budget(pairs):
     lib().smh_match_set_pair_budget(int(pairs))
 
 
+def gather_many_budget():
+    return int(lib().smh_gather_many_budget())
+
+
+def set_gather_many_budget(pairs):
+    """the (query, node) counters one chunk of ResidentIndex.gather_many may hold (smh_gather_many_set_budget); 0 restores
+    the default"""
+    lib().smh_gather_many_set_budget(int(pairs))
+
+
 def angular_last_stats():
     """(pairs walked, pairs given zeros without a walk) of the last angular call"""
     a, b = C.c_uint64(), C.c_uint64()
