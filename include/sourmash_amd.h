@@ -495,6 +495,84 @@ void smh_match_geometry(uint32_t *lds_pairs, uint32_t *threads_per_record, uint3
 void smh_match_set_pair_budget(uint64_t pairs);
 uint64_t smh_match_pair_budget(void);
 
+/* Taxonomic LCA: what a sketch or a read is taxonomically, answered on the resident index (`lca classify`, `lca summarize`,
+ * per-read screening).  The reference crate has no LCA code, so the rules are fixed here -- DESIGN.md 3.15, restated in
+ * tests/lca_restatement.py.
+ *   Taxonomy       parent[0 .. n_taxa), 1 <= n_taxa < 2^32 - 1.  Taxon 0 is the root and parent[0] == 0; parent[t] < t for
+ *                  t > 0 (topological order).  node_taxon[0 .. n_nodes) gives each node's taxon; SMH_NO_TAXON marks a node
+ *                  without a lineage, and such nodes are ignored everywhere below.
+ *   lca(a, b)      the deepest common ancestor; SMH_NO_TAXON is its identity.
+ *   A resident     hash has the taxon lca over the taxa of all nodes holding it, SMH_NO_TAXON when none of them has one.  A
+ *   hash           query hash is ASSIGNED when the index holds it and its taxon is not SMH_NO_TAXON.
+ *   Counts         of a sketch: the multiset of the taxa of its assigned hashes, reported as (taxon, count) pairs, taxon
+ *                  ascending.  No roll-up to ancestors and no abundance weighting happen on the device.
+ *   Classification of a set S of taxa (sourmash's find_lca on the tree built from the lineages): take the union of the root
+ *                  paths of S and descend from the root while the current node has exactly one child in that union; the
+ *                  result is the node where the descent stops.  status = 1 (found) when nothing lies below, 2 (disagree)
+ *                  when it stopped at a branching; status = 0 and taxon SMH_NO_TAXON for the empty S.  This is not lca(S):
+ *                  for S = {B, C} with B an ancestor of C the answer is C, found.
+ *   Join           the classification is the fold of an associative, commutative join on summaries (x, f), f = disagree: a
+ *                  taxon alone is (t, false).  With x the shallower operand: lca(x, y) != x gives (lca(x, y), true);
+ *                  x == y gives (x, fx | fy); otherwise x is a strict ancestor of y and the result is (x, true) if fx, else
+ *                  (y, fy).
+ *   A record       is classified by S = the taxa of its distinct assigned hit hashes: every hit counts (`lca classify
+ *                  --threshold 1`).  Windows, sampled windows, hits and record boundaries are those of "Matching records",
+ *                  word for word.  Thresholds above 1 belong to the sketch route: the caller applies them to the counts.
+ * Every output is an integer: parity is equality.  No result depends on chunking, budgets, launch geometry or the order of
+ * atomics.
+ *
+ * smh_lca_check_taxonomy     the refusals of a taxonomy alone (SOURMASH_ERROR_CODE_MSG, the message names the offending
+ *                            entry): n_taxa == 0 or 2^32 - 1; n_nodes != index_len; parent[0] != 0; parent[t] >= t; a node
+ *                            taxon >= n_taxa that is not SMH_NO_TAXON.  Needs no device and no index.
+ * smh_index_set_taxonomy     checks the arrays as above (index_len = smh_index_len) and copies them; host only.  Setting it
+ *                            again replaces it and drops the per-hash table.
+ * smh_index_has_taxonomy     an index smh_index_downsample makes from an index with a taxonomy carries the same taxonomy
+ *                            (same nodes, same order).  An index without one is refused by the calls below (MSG).
+ * smh_index_lca_many         the counts of every query of a batch.  count_offsets (the caller's, n_queries + 1 entries): the
+ *                            pairs of query q are (*taxa)[count_offsets[q] .. count_offsets[q + 1]) (u32) with *counts (u64);
+ *                            both are malloc'ed (at least one element) and freed with free().  query_offsets (nullable,
+ *                            n_queries + 1): the running sum of the queries' sizes.  hash_taxon (nullable): one u32 per query
+ *                            position in ascending hash order, the taxon of that hash or SMH_NO_TAXON.  Every query is
+ *                            checked as smh_index_gather_many checks it; the error of the LOWEST failing query is reported
+ *                            and nothing is written.  The index's nodes must be scaled sketches that agree in ksize,
+ *                            molecule, seed and max_hash (else MSG).  A query that lives in HBM is staged device to device.
+ * smh_index_lca_block_dev    the CSR / device form, as smh_index_gather_block_dev: hashes ascend strictly inside a query,
+ *                            q_offsets on the host, hash_taxon counts from q_offsets[0]; stream: the caller's.
+ * smh_index_lca_sequences    the three routes of "Matching records"; rows: one SmhLcaRow per record.  windows, distinct and
+ * smh_index_lca_sequences_dev hit_distinct are SmhMatchRow's of the same record; assigned_distinct = the distinct assigned hit
+ * smh_index_lca_records      hashes; taxon / status = the classification.  The index is refused as match refuses it.
+ * smh_lca_geometry           the sizes at which the kernels' branches change: the owners of a hash up to which one lane
+ *                            computes its taxon (a longer list gets a wave), the distinct sampled hashes of a record up to
+ *                            which one lane classifies it (a longer record gets a wave), and the threads of that wave.
+ * smh_lca_set_budget         the keys (query hashes) one chunk of a sketch batch may hold: chunks are cut at query boundaries
+ * smh_lca_budget             and a query alone always makes a chunk.  0 restores the default of 2^26 -- a memory cap, not a
+ *                            measured optimum.  Process-wide; results never depend on it.  The records route keeps using
+ *                            smh_match_pair_budget for its folds.
+ * The per-hash table (one taxon per distinct resident hash) is computed by the first device call after the taxonomy is set,
+ * kept beside the hash directory and dropped with it (smh_release_workspace, smh_index_free) and by smh_index_set_taxonomy.
+ * Timers under smh_profile_get: "lca_table", "lca_probe", "lca_records"; event counters: "lca_table_built", "lca_chunk",
+ * and "match_directory_built" as before. */
+#define SMH_NO_TAXON 0xffffffffu
+typedef struct SmhLcaRow {
+  uint32_t windows, distinct, hit_distinct, assigned_distinct, taxon, status;
+} SmhLcaRow;
+int smh_lca_check_taxonomy(const uint32_t *parent, uint32_t n_taxa, const uint32_t *node_taxon, uint32_t n_nodes,
+                           uint32_t index_len);
+int smh_index_set_taxonomy(SmhIndex *index, const uint32_t *parent, uint32_t n_taxa, const uint32_t *node_taxon,
+                           uint32_t n_nodes);
+bool smh_index_has_taxonomy(const SmhIndex *index);
+int smh_index_lca_many(SmhIndex *index, const KmerMinHash *const *queries, uint32_t n_queries, uint64_t *count_offsets,
+                       uint32_t **taxa, uint64_t **counts, uint64_t *query_offsets, uint32_t *hash_taxon);
+int smh_index_lca_block_dev(SmhIndex *index, const uint64_t *q_hashes_dev, const uint64_t *q_offsets, uint32_t n_queries,
+                            uint64_t *count_offsets, uint32_t **taxa, uint64_t **counts, uint32_t *hash_taxon, void *stream);
+int smh_index_lca_sequences(SmhIndex *index, const char *seq, const uint64_t *offsets, uint32_t n_records, SmhLcaRow *rows);
+int smh_index_lca_sequences_dev(SmhIndex *index, const void *seq_dev, uint64_t total_len, const uint64_t *offsets,
+                                uint32_t n_records, SmhLcaRow *rows, void *stream);
+int smh_index_lca_records(SmhIndex *index, const SmhRecords *records, SmhLcaRow *rows);
+void smh_lca_geometry(uint32_t *owner_lane_max, uint32_t *record_lane_max, uint32_t *threads);
+void smh_lca_set_budget(uint64_t keys);
+uint64_t smh_lca_budget(void);
+
 /* deterministic synthetic DNA of SURVEY.md 8d written to device memory (benchmark input) */
 int smh_synth_dna_dev(void *out_dev, uint64_t start, uint64_t len, uint64_t seed, uint64_t n_every,
                       void *stream);

@@ -11,6 +11,7 @@ SO_PATH = os.environ.get("SOURMASH_AMD_LIB") or os.path.join(HERE, "lib", "libso
 
 u64p = C.POINTER(C.c_uint64)
 f64p = C.POINTER(C.c_double)
+u32p = C.POINTER(C.c_uint32)
 
 
 class SourmashStr(C.Structure):
@@ -38,6 +39,11 @@ class SmhGatherRow(C.Structure):
 class SmhMatchRow(C.Structure):
     _fields_ = [("windows", C.c_uint32), ("distinct", C.c_uint32), ("hit_windows", C.c_uint32), ("hit_distinct", C.c_uint32),
                 ("best", C.c_uint32), ("best_common", C.c_uint32)]
+
+
+class SmhLcaRow(C.Structure):
+    _fields_ = [("windows", C.c_uint32), ("distinct", C.c_uint32), ("hit_distinct", C.c_uint32), ("assigned_distinct", C.c_uint32),
+                ("taxon", C.c_uint32), ("status", C.c_uint32)]
 
 
 def build(force=False):
@@ -189,6 +195,18 @@ _SIGS = {
     "smh_match_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smh_match_set_pair_budget": (None, [C.c_uint64]),
     "smh_match_pair_budget": (C.c_uint64, []),
+    "smh_lca_check_taxonomy": (C.c_int, [u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32]),
+    "smh_index_set_taxonomy": (C.c_int, [C.c_void_p, u32p, C.c_uint32, u32p, C.c_uint32]),
+    "smh_index_has_taxonomy": (C.c_bool, [C.c_void_p]),
+    "smh_index_lca_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, u64p, C.POINTER(u32p), C.POINTER(u64p), u64p, u32p]),
+    "smh_index_lca_block_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, u64p, C.POINTER(u32p), C.POINTER(u64p), u32p,
+                                          C.c_void_p]),
+    "smh_index_lca_sequences": (C.c_int, [C.c_void_p, C.c_char_p, u64p, C.c_uint32, C.c_void_p]),
+    "smh_index_lca_sequences_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "smh_index_lca_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "smh_lca_geometry": (None, [u32p, u32p, u32p]),
+    "smh_lca_set_budget": (None, [C.c_uint64]),
+    "smh_lca_budget": (C.c_uint64, []),
     "smh_release_workspace": (C.c_int, []),
     "smh_pool_set_limit": (None, [C.c_uint64]),
     "smh_pool_bytes": (C.c_uint64, []),

@@ -922,6 +922,118 @@ void smh_match_geometry(uint32_t* lds_pairs, uint32_t* threads_per_record, uint3
 void smh_match_set_pair_budget(uint64_t pairs) { smh::g_match_pair_budget = pairs ? pairs : smh::kMatchPairBudget; }
 uint64_t smh_match_pair_budget(void) { return smh::g_match_pair_budget; }
 
+// ------------------------------------------------------------------ taxonomic LCA (lca.cpp)
+
+static_assert(sizeof(SmhLcaRow) == 24 && sizeof(smh::LcaRow) == 24, "SmhLcaRow is 24 bytes");
+static_assert(offsetof(SmhLcaRow, taxon) == 16 && offsetof(smh::LcaRow, taxon) == 16, "SmhLcaRow layout");
+static_assert(SMH_NO_TAXON == smh::kLcaNoTaxon, "SMH_NO_TAXON");
+
+int smh_lca_check_taxonomy(const uint32_t* parent, uint32_t n_taxa, const uint32_t* node_taxon, uint32_t n_nodes, uint32_t index_len) {
+  return pad_code([&] {
+    if (n_taxa) require(parent, "parent");
+    if (n_nodes) require(node_taxon, "node_taxon");
+    smh::lca_check_taxonomy(parent, n_taxa, node_taxon, n_nodes, index_len);
+  });
+}
+int smh_index_set_taxonomy(SmhIndex* index, const uint32_t* parent, uint32_t n_taxa, const uint32_t* node_taxon, uint32_t n_nodes) {
+  return pad_code([&] {
+    require(index, "index");
+    if (n_taxa) require(parent, "parent");
+    if (n_nodes) require(node_taxon, "node_taxon");
+    index->set_taxonomy(parent, n_taxa, node_taxon, n_nodes);
+  });
+}
+bool smh_index_has_taxonomy(const SmhIndex* index) { return index && index->has_taxonomy(); }
+
+namespace {
+// the pairs handed out the way gather_many hands out its rows: malloc'ed, one element at least
+void lca_counts_out(const std::vector<uint32_t>& t, const std::vector<uint64_t>& c, uint32_t** taxa, uint64_t** counts) {
+  const size_t k = t.empty() ? 1 : t.size();
+  uint32_t* ot = (uint32_t*)malloc(k * sizeof(uint32_t));
+  uint64_t* oc = (uint64_t*)malloc(k * sizeof(uint64_t));
+  if (!ot || !oc) { free(ot); free(oc); smh::throw_internal("out of memory"); }
+  if (!t.empty()) { memcpy(ot, t.data(), t.size() * sizeof(uint32_t)); memcpy(oc, c.data(), c.size() * sizeof(uint64_t)); }
+  *taxa = ot; *counts = oc;
+}
+void lca_records_require(SmhIndex* index, const uint64_t* offsets, uint32_t n, SmhLcaRow* rows) {
+  require(index, "index");
+  if (n) { require(offsets, "offsets"); require(rows, "rows"); }
+  index->check_matchable();
+  if (!index->has_taxonomy()) throw Error(smh::kMsg, "lca_records: the index has no taxonomy (smh_index_set_taxonomy)");
+}
+}  // namespace
+
+int smh_index_lca_many(SmhIndex* index, const KmerMinHash* const* queries, uint32_t n_queries, uint64_t* count_offsets, uint32_t** taxa,
+                       uint64_t** counts, uint64_t* query_offsets, uint32_t* hash_taxon) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();   // first: without a device the call says so, whatever it was handed
+    require(index, "index"); require(count_offsets, "count_offsets"); require(taxa, "taxa"); require(counts, "counts");
+    if (n_queries) require(queries, "queries");
+    std::vector<const smh::KmerMinHash*> v(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) { require(queries[q], "queries[q]"); v[q] = queries[q]; }
+    std::vector<uint32_t> t;
+    std::vector<uint64_t> c;
+    index->lca_many(v.data(), n_queries, count_offsets, &t, &c, query_offsets, hash_taxon, dev);
+    lca_counts_out(t, c, taxa, counts);
+  });
+}
+
+int smh_index_lca_block_dev(SmhIndex* index, const uint64_t* q_hashes_dev, const uint64_t* q_offsets, uint32_t n_queries,
+                            uint64_t* count_offsets, uint32_t** taxa, uint64_t** counts, uint32_t* hash_taxon, void* stream) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    require(index, "index"); require(count_offsets, "count_offsets"); require(taxa, "taxa"); require(counts, "counts");
+    require(q_offsets, "q_offsets");
+    if (n_queries && q_offsets[n_queries] != q_offsets[0]) require(q_hashes_dev, "q_hashes_dev");
+    std::vector<uint32_t> t;
+    std::vector<uint64_t> c;
+    index->lca_many_dev(q_hashes_dev, q_offsets, n_queries, count_offsets, &t, &c, hash_taxon, dev, dev.user_stream(stream));
+    lca_counts_out(t, c, taxa, counts);
+  });
+}
+
+int smh_index_lca_sequences(SmhIndex* index, const char* seq, const uint64_t* offsets, uint32_t n_records, SmhLcaRow* rows) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();   // first: without a device the call says so, whatever it was handed
+    lca_records_require(index, offsets, n_records, rows);
+    auto& E = smh::Engine::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    const uint64_t base = n_records ? offsets[0] : 0, total = n_records ? offsets[n_records] - base : 0;
+    if (n_records && offsets[n_records] < base) throw Error(smh::kMsg, "match: offsets must ascend");
+    if (total) require(seq, "seq");
+    std::vector<uint64_t> rel((size_t)n_records + 1, 0);
+    for (uint32_t i = 0; n_records && i <= n_records; i++) rel[i] = offsets[i] - base;
+    E.seqbuf.ensure(total + 64);
+    if (total) HIP_CHECK(hipMemcpyAsync(E.seqbuf.ptr, seq + base, total, hipMemcpyHostToDevice, dev.stream()));
+    index->lca_records(E.seqbuf.as<uint8_t>(), total, rel.data(), n_records, reinterpret_cast<smh::LcaRow*>(rows), dev.stream());
+  });
+}
+
+int smh_index_lca_sequences_dev(SmhIndex* index, const void* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n_records,
+                                SmhLcaRow* rows, void* stream) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    lca_records_require(index, offsets, n_records, rows);
+    if (total_len) require(seq_dev, "seq_dev");
+    index->lca_records((const uint8_t*)seq_dev, total_len, offsets, n_records, reinterpret_cast<smh::LcaRow*>(rows), dev.user_stream(stream));
+  });
+}
+
+int smh_index_lca_records(SmhIndex* index, const SmhRecords* r, SmhLcaRow* rows) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    require(r, "records");
+    lca_records_require(index, r->offsets, r->n, rows);
+    index->lca_records(r->seq_dev(), r->total, r->offsets, r->n, reinterpret_cast<smh::LcaRow*>(rows), dev.user_stream(nullptr));
+  });
+}
+
+void smh_lca_geometry(uint32_t* owner_lane_max, uint32_t* record_lane_max, uint32_t* threads) {
+  smh::lca_geometry(owner_lane_max, record_lane_max, threads);
+}
+void smh_lca_set_budget(uint64_t keys) { smh::g_lca_budget = keys ? keys : smh::kLcaBudget; }
+uint64_t smh_lca_budget(void) { return smh::g_lca_budget; }
+
 // ---- a scaled sketch's state as device arrays: the cross-rank union of partial sketches ----
 int smh_sketch_export_dev(KmerMinHash* ptr, uint64_t* mins_dev, uint64_t* abunds_dev, uint64_t capacity, uint64_t* n_out, void* stream) {
   return pad_code([&] {

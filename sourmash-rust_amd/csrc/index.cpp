@@ -66,6 +66,7 @@ ResidentIndex::ResidentIndex(ResidentIndex& parent, uint64_t mx) {
   n = parent.n;
   h_nums.assign(n, 0);
   params = parent.params;
+  tax_parent = parent.tax_parent; tax_depth = parent.tax_depth; node_taxon = parent.node_taxon;   // same nodes, same order
   for (uint32_t i = 0; i < n; i++) {
     params[i].max_hash = mx;
     const KmerMinHash &p = params[i], &p0 = params[0];
@@ -132,7 +133,7 @@ struct MatchDir {
   MatchDirectory view() const { return {U.as<uint64_t>(), starts.as<uint32_t>(), owners.as<uint32_t>(), n_hashes, n_pairs}; }
 };
 
-void ResidentIndex::drop_match_dir() { delete match_dir; match_dir = nullptr; }
+void ResidentIndex::drop_match_dir() { delete match_dir; match_dir = nullptr; drop_lca_dev(); }   // (hash_taxon is per rank)
 
 void ResidentIndex::check_directory_size(const char* who) const {
   const uint64_t total = h_offsets.back() - h_offsets.front();

@@ -1,7 +1,9 @@
 // index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
-// similarity on abundances (angular.cpp), matching records (match.cpp).  The C boundary (ffi.cpp) only checks pointers and
+// similarity on abundances (angular.cpp), matching records (match.cpp), taxonomic LCA (lca.cpp).  The C boundary (ffi.cpp) only checks pointers and
 // calls in here.
 #pragma once
+#include <functional>
+
 #include "minhash.hpp"
 
 namespace smh {
@@ -68,6 +70,24 @@ struct ResidentIndex {
   void check_matchable() const;   // the refusals (kMsg): needs no device
   void match(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n_records, MatchRow* rows,
              uint64_t* hit_offsets, std::vector<uint64_t>* hit_hashes, hipStream_t s);
+  // The front half of match, shared with lca_records: the folds of a batch cut at record boundaries and per fold the grouped
+  // fold's sequence up to the probe.  blank(a, e): records [a, e) are seen by no fold's kernels; tail(dir, fold): what the
+  // caller does with a probed fold on `s` (the stream is waited for behind it and the fold's buffers go back).
+  // check_match_batch: check_matchable and the offsets -- every refusal that needs no device, for callers to run in front of
+  // their first write.
+  struct MatchFold {
+    uint32_t f0 = 0, nf = 0, nruns = 0;   // the fold's records [f0, f0 + nf) and its runs
+    const uint64_t* run_hash = nullptr;   // nruns hashes
+    MatchRow* rows = nullptr;             // nf rows: the four sums of the probe
+    uint32_t* rec_first = nullptr;
+    unsigned long long* rec_pairs = nullptr;
+    uint32_t* rank = nullptr;             // nruns
+    uint32_t* hit_flag = nullptr;         // nruns + 1 when the hits are wanted, else null
+  };
+  void check_match_batch(const uint64_t* offsets, uint32_t n_records, uint64_t total_len) const;
+  void match_folds(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n_records, bool want_hits, hipStream_t s,
+                   const std::function<void(uint32_t, uint32_t)>& blank,
+                   const std::function<void(const MatchDirectory&, const MatchFold&)>& tail);
   // The directory, built on the first call (counter match_directory_built).  An index of 2^31 or more hashes is refused
   // (kMsg, the message begins with `who`); check_directory_size is that refusal alone and needs no device.
   void check_directory_size(const char* who) const;
@@ -83,6 +103,25 @@ struct ResidentIndex {
   void gather_many_dev(const uint64_t* q_hashes_dev, const uint64_t* q_abunds_dev, const uint64_t* q_offsets, uint32_t n_queries,
                        uint32_t threshold_common, uint32_t rows_capacity, uint64_t* row_offsets, std::vector<GatherRow>* rows,
                        uint32_t* assigned, Device& dev, hipStream_t s);
+  // (lca.cpp) Taxonomic LCA (the rules: include/sourmash_amd.h, "Taxonomic LCA").  The taxonomy is kept on the host
+  // (tax_parent empty: none); the first device call uploads it and computes hash_taxon, one taxon per rank of the directory,
+  // kept beside it in lca_dev (counter lca_table_built) and dropped with it, and by set_taxonomy.
+  std::vector<uint32_t> tax_parent, tax_depth, node_taxon;
+  struct LcaDev* lca_dev = nullptr;
+  bool has_taxonomy() const { return !tax_parent.empty(); }
+  void set_taxonomy(const uint32_t* parent, uint32_t n_taxa, const uint32_t* node_taxon_in, uint32_t n_nodes);   // host only
+  void drop_lca_dev();
+  struct LcaView { LcaTaxonomy tax; const uint32_t* hash_taxon = nullptr; };
+  LcaView ensure_lca(const MatchDirectory& dir, Device& dev, hipStream_t s);
+  void check_lca_sketches(const char* who) const;   // a taxonomy, and scaled nodes that agree in ksize, molecule, seed, max_hash
+  // the counts of a batch of sketches / of a CSR in device memory: count_offsets (n_queries + 1), taxa / counts
+  // (count_offsets[n_queries] pairs), query_offsets (nullable, n_queries + 1), hash_taxon (nullable, one per query position)
+  void lca_many(const KmerMinHash* const* queries, uint32_t n_queries, uint64_t* count_offsets, std::vector<uint32_t>* taxa,
+                std::vector<uint64_t>* counts, uint64_t* query_offsets, uint32_t* hash_taxon, Device& dev);
+  void lca_many_dev(const uint64_t* q_hashes_dev, const uint64_t* q_offsets, uint32_t n_queries, uint64_t* count_offsets,
+                    std::vector<uint32_t>* taxa, std::vector<uint64_t>* counts, uint32_t* hash_taxon, Device& dev, hipStream_t s);
+  // the records of a batch classified (arguments as match's)
+  void lca_records(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* offsets, uint32_t n_records, LcaRow* rows, hipStream_t s);
   void angular_ensure(const char* what, hipStream_t s);   // (angular.cpp from here) the first angular call: abundances to HBM, norms
   void norms2(uint64_t* out);
   void angular(ResidentIndex& cols, uint64_t* dot, double* cosine, double* angular);
@@ -121,6 +160,15 @@ extern uint64_t g_angular_prune_min_pairs, g_angular_walked, g_angular_skipped;
 // buffers, 256 MiB of counters), not a measured optimum.
 constexpr uint64_t kMatchPairBudget = 1ull << 26;
 extern uint64_t g_match_pair_budget;
+
+// match.cpp: the rows of a fold (MatchRow or LcaRow, 24 bytes each) into the caller's array
+void fetch_rows(const void* d_rows, void* out, size_t n, Engine& E, hipStream_t s);
+
+// lca.cpp: the taxonomy's refusals alone (kMsg, the message names the entry; index_len: what n_nodes must equal), and the keys
+// (query hashes) one chunk of a sketch batch may hold -- a memory cap, not a measured optimum
+void lca_check_taxonomy(const uint32_t* parent, uint32_t n_taxa, const uint32_t* node_taxon, uint32_t n_nodes, uint32_t index_len);
+constexpr uint64_t kLcaBudget = 1ull << 26;
+extern uint64_t g_lca_budget;
 
 // gather_many.cpp: the (query, node) counters one chunk of a batch may hold (three u32 arrays of that size: 768 MiB at the
 // default) -- a memory cap, not a measured optimum.  gather_many_chunk_end: the chunk that starts at query `a` ends in front

@@ -1,6 +1,6 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
-// gather_many_kernels.hip).
+// gather_many_kernels.hip, lca_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -458,5 +458,36 @@ void launch_gather_many_rounds(const MatchDirectory& d, const GatherManyChunk& c
 // out[p] = the abundance of position p of a device-resident sketch held as run starts (the last run ends at total); starts
 // null: 1 each
 void launch_gather_many_weights(const uint32_t* starts, uint32_t total, uint32_t n, uint64_t* out, hipStream_t s);
+
+// --- lca_kernels.hip -------------------------------------------------------------------
+// Taxonomic LCA on a resident index (the rules are in include/sourmash_amd.h, "Taxonomic LCA").
+constexpr uint32_t kLcaNoTaxon = 0xffffffffu;    // SMH_NO_TAXON: a node without a lineage, an unassigned hash, an empty set
+constexpr uint32_t kLcaOwnerLaneMax = 8;         // owner lists up to this length are folded by one lane of the table kernel
+constexpr uint32_t kLcaRecordLaneMax = 8;        // records with up to this many runs are folded by one lane
+constexpr uint32_t kLcaThreads = 64;             // what a longer owner list / record gets: one wave
+struct LcaRow { uint32_t windows, distinct, hit_distinct, assigned_distinct, taxon, status; };   // SmhLcaRow
+// The taxonomy in device memory: tax[t] = {parent, depth} (8 bytes, one load per step of the walk), node_taxon[i] = the
+// taxon of node i or kLcaNoTaxon.
+struct LcaTaxonomy {
+  const uint64_t* tax = nullptr;   // read as uint2 {parent, depth}
+  const uint32_t* node_taxon = nullptr;
+};
+void lca_geometry(uint32_t* owner_lane_max, uint32_t* record_lane_max, uint32_t* threads);
+// hash_taxon[g] for every rank g of the directory.  long_list: room for n_pairs / (kLcaOwnerLaneMax + 1) + 1 entries,
+// long_count: one word (zeroed here).  Profile name lca_table.
+void launch_lca_table(const MatchDirectory& d, const LcaTaxonomy& t, uint32_t* hash_taxon, uint32_t* long_list, uint32_t* long_count,
+                      Device& dev, hipStream_t s);
+// The T positions of a chunk of nq queries (qoff: nq + 1 offsets among them; hashes ascend strictly inside a query):
+// taxon_out[p] = the taxon of hash p or kLcaNoTaxon, key_out[p] = (query << 32) | taxon, flag_out[p] = 1 for an assigned
+// hash.  Profile name lca_probe.
+void launch_lca_probe(const MatchDirectory& d, const uint32_t* hash_taxon, const uint64_t* hashes, const uint32_t* qoff, uint32_t nq,
+                      uint32_t T, uint32_t* taxon_out, uint64_t* key_out, uint32_t* flag_out, Device& dev, hipStream_t s);
+// out[at[p]] = key[p] for every assigned position (at: the exclusive scan of the flags)
+void launch_lca_keys(const uint64_t* key, const uint32_t* at, uint32_t T, uint64_t* out, Device& dev, hipStream_t s);
+// The rows of a fold's nrec records after launch_match_probe (rows, rec_first, rank as it left them) -> out.  big_list: room
+// for nrec entries, big_count: one word (zeroed here).  Profile name lca_records.
+void launch_lca_records(const LcaTaxonomy& t, const uint32_t* hash_taxon, const uint32_t* rank, const MatchRow* rows,
+                        const uint32_t* rec_first, uint32_t nrec, LcaRow* out, uint32_t* big_list, uint32_t* big_count, Device& dev,
+                        hipStream_t s);
 
 }  // namespace smh

@@ -1,0 +1,224 @@
+// lca.cpp -- taxonomic LCA on a resident index (the rules are in include/sourmash_amd.h, "Taxonomic LCA"):
+// the taxonomy's checks and its copy, the upload and the per-hash table kept beside the hash directory, the sketch route
+// (staging, chunks cut at query boundaries, per chunk the probe, the compaction, the sort and the run-length pass) and the
+// records route (match's front half, then the fold of the join per record).  The kernels are in lca_kernels.hip.
+#include <algorithm>
+#include <memory>
+#include <string>
+
+#include "index.hpp"
+
+namespace smh {
+
+uint64_t g_lca_budget = kLcaBudget;
+
+namespace {
+[[noreturn]] void refuse(const std::string& what) { throw Error(kMsg, "lca: " + what); }
+}  // namespace
+
+struct LcaDev {
+  DeviceBuffer tax, node_taxon, hash_taxon;
+};
+
+void lca_check_taxonomy(const uint32_t* parent, uint32_t n_taxa, const uint32_t* node_taxon, uint32_t n_nodes, uint32_t index_len) {
+  if (n_taxa == 0) refuse("n_taxa is 0; a taxonomy holds its root at least");
+  if (n_taxa == kLcaNoTaxon) refuse("n_taxa is " + std::to_string(n_taxa) + "; a taxonomy holds fewer than 2^32 - 1 taxa");
+  if (n_nodes != index_len)
+    refuse("n_nodes is " + std::to_string(n_nodes) + " but the index holds " + std::to_string(index_len) + " nodes");
+  if (parent[0] != 0) refuse("parent[0] is " + std::to_string(parent[0]) + "; taxon 0 is the root and its own parent");
+  for (uint32_t t = 1; t < n_taxa; t++)
+    if (parent[t] >= t)
+      refuse("parent[" + std::to_string(t) + "] is " + std::to_string(parent[t]) + "; a parent comes before its children (parent[t] < t)");
+  for (uint32_t i = 0; i < n_nodes; i++)
+    if (node_taxon[i] != kLcaNoTaxon && node_taxon[i] >= n_taxa)
+      refuse("node_taxon[" + std::to_string(i) + "] is " + std::to_string(node_taxon[i]) + "; the taxonomy holds " + std::to_string(n_taxa) +
+             " taxa");
+}
+
+void ResidentIndex::set_taxonomy(const uint32_t* parent, uint32_t n_taxa, const uint32_t* nt, uint32_t n_nodes) {
+  lca_check_taxonomy(parent, n_taxa, nt, n_nodes, n);
+  std::vector<uint32_t> p(parent, parent + n_taxa), d(n_taxa, 0), t(nt, nt + n_nodes);
+  for (uint32_t k = 1; k < n_taxa; k++) d[k] = d[p[k]] + 1;   // (topological order: one pass)
+  if (lca_dev) {
+    std::lock_guard<std::recursive_mutex> lock(Device::get().mutex());   // (device state exists: so does the device)
+    drop_lca_dev();
+  }
+  tax_parent.swap(p); tax_depth.swap(d); node_taxon.swap(t);
+}
+
+void ResidentIndex::drop_lca_dev() { delete lca_dev; lca_dev = nullptr; }
+
+ResidentIndex::LcaView ResidentIndex::ensure_lca(const MatchDirectory& dir, Device& dev, hipStream_t s) {
+  if (!lca_dev) {
+    auto L = std::make_unique<LcaDev>();
+    const size_t nt = tax_parent.size();
+    std::vector<uint64_t> packed(nt);
+    for (size_t t = 0; t < nt; t++) packed[t] = ((uint64_t)tax_depth[t] << 32) | tax_parent[t];
+    L->tax.ensure(nt * 8);
+    L->node_taxon.ensure((size_t)n * 4 + 4);
+    L->hash_taxon.ensure((size_t)dir.n_hashes * 4 + 4);
+    HIP_CHECK(hipMemcpyAsync(L->tax.ptr, packed.data(), nt * 8, hipMemcpyHostToDevice, s));
+    if (n) HIP_CHECK(hipMemcpyAsync(L->node_taxon.ptr, node_taxon.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    const LcaTaxonomy T{L->tax.as<uint64_t>(), L->node_taxon.as<uint32_t>()};
+    const size_t longs = (size_t)dir.n_pairs / (kLcaOwnerLaneMax + 1) + 1;
+    PoolBlock d_long((longs + 1) * 4);
+    launch_lca_table(dir, T, L->hash_taxon.as<uint32_t>(), d_long.as<uint32_t>(), d_long.as<uint32_t>() + longs, dev, s);
+    HIP_CHECK(hipStreamSynchronize(s));   // (`packed` is read by the upload)
+    d_long.synced = true;
+    dev.count("lca_table_built");
+    lca_dev = L.release();
+  }
+  return {{lca_dev->tax.as<uint64_t>(), lca_dev->node_taxon.as<uint32_t>()}, lca_dev->hash_taxon.as<uint32_t>()};
+}
+
+void ResidentIndex::check_lca_sketches(const char* who) const {
+  if (!has_taxonomy()) throw Error(kMsg, std::string(who) + ": the index has no taxonomy (smh_index_set_taxonomy)");
+  if (!(uniform && all_scaled))
+    throw Error(kMsg, std::string(who) + ": the index's nodes must be scaled sketches with the same ksize, molecule, seed and max_hash");
+}
+
+void ResidentIndex::lca_many_dev(const uint64_t* qh, const uint64_t* qoff, uint32_t nq, uint64_t* count_offsets, std::vector<uint32_t>* taxa_out,
+                                 std::vector<uint64_t>* counts_out, uint32_t* hash_taxon, Device& dev, hipStream_t s) {
+  check_lca_sketches("lca_many");
+  for (uint32_t q = 0; q < nq; q++) {
+    if (qoff[q + 1] < qoff[q]) throw Error(kMsg, "lca_many: offsets must ascend (query " + std::to_string(q) + ")");
+    if (qoff[q + 1] - qoff[q] >= (1ull << 31)) throw_internal("lca_many: a query of 2^31 or more hashes");
+  }
+  check_directory_size("lca_many");
+  const uint64_t total = nq ? qoff[nq] - qoff[0] : 0, base0 = nq ? qoff[0] : 0;
+  std::vector<uint64_t> coff((size_t)nq + 1, 0);
+  std::vector<uint32_t> taxa;
+  std::vector<uint64_t> counts;
+  auto finish = [&] {
+    std::copy(coff.begin(), coff.end(), count_offsets);
+    taxa_out->swap(taxa);
+    counts_out->swap(counts);
+  };
+  auto blank = [&](uint64_t from, uint64_t len) { if (hash_taxon) std::fill(hash_taxon + from, hash_taxon + from + len, kLcaNoTaxon); };
+  if (n == 0 || total == 0) { blank(0, total); finish(); return; }
+
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  const MatchDirectory dir = ensure_directory("lca_many", dev, s);
+  if (dir.n_hashes == 0) { blank(0, total); finish(); return; }
+  const LcaView L = ensure_lca(dir, dev, s);
+  const uint64_t budget = std::max<uint64_t>(g_lca_budget, 1);
+  std::vector<uint32_t> rel;
+  std::vector<uint64_t> h_keys, h_cnt, per;
+
+  for (uint32_t a = 0, b = 0; a < nq; a = b) {
+    // the chunk: queries while their hashes fit the budget (and 2^31 - 1 positions, what the sort takes); one at least
+    b = a + 1;
+    while (b < nq && qoff[b + 1] - qoff[a] <= budget && qoff[b + 1] - qoff[a] < (1ull << 31)) b++;
+    const uint32_t Qc = b - a;
+    const uint32_t T = (uint32_t)(qoff[b] - qoff[a]);
+    dev.count("lca_chunk");
+    for (uint32_t q = a; q < b; q++) coff[q + 1] = coff[q];
+    if (T == 0) continue;
+    PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_tax((size_t)T * 4), d_key((size_t)T * 8), d_flag(((size_t)T + 1) * 4);
+    rel.resize((size_t)Qc + 1);
+    for (uint32_t k = 0; k <= Qc; k++) rel[k] = (uint32_t)(qoff[a + k] - qoff[a]);
+    HIP_CHECK(hipMemcpyAsync(d_qoff.ptr, rel.data(), ((size_t)Qc + 1) * 4, hipMemcpyHostToDevice, s));
+    launch_lca_probe(dir, L.hash_taxon, qh + qoff[a], d_qoff.as<uint32_t>(), Qc, T, d_tax.as<uint32_t>(), d_key.as<uint64_t>(),
+                     d_flag.as<uint32_t>(), dev, s);
+    if (hash_taxon) HIP_CHECK(hipMemcpyAsync(hash_taxon + (qoff[a] - base0), d_tax.ptr, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+    uint32_t* total_dev = d_flag.as<uint32_t>() + T;
+    uint32_t nkeys = 0;
+    exclusive_scan_u32_dev(d_flag.as<uint32_t>(), T, total_dev, dev.scratch, s);
+    HIP_CHECK(hipMemcpyAsync(&nkeys, total_dev, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));   // (`rel` is read by the upload)
+    auto idle = [&] { d_qoff.synced = d_tax.synced = d_key.synced = d_flag.synced = true; };
+    if (nkeys == 0) { idle(); continue; }
+    // the assigned keys compacted, sorted, run-length encoded: the runs are (query, taxon) ascending with their counts
+    PoolBlock k0((size_t)nkeys * 8), k1((size_t)nkeys * 8), d_uniq((size_t)nkeys * 8), d_starts(((size_t)nkeys + 1) * 4);
+    launch_lca_keys(d_key.as<uint64_t>(), d_flag.as<uint32_t>(), T, k0.as<uint64_t>(), dev, s);
+    const int cur = radix_sort_u64_keys(k0.as<uint64_t>(), k1.as<uint64_t>(), nkeys, dev.scratch, s, 0);
+    const uint32_t nruns = run_length_encode_u64((cur ? k1 : k0).as<uint64_t>(), nkeys, d_uniq.as<uint64_t>(), d_starts.as<uint32_t>(),
+                                                 dev.scratch, s);
+    uint64_t* d_cnt = (cur ? k0 : k1).as<uint64_t>();   // (the sort's other half is free now: nruns <= nkeys)
+    starts_to_counts(d_starts.as<uint32_t>(), nruns, nkeys, d_cnt, s);
+    h_keys.resize(nruns); h_cnt.resize(nruns);
+    HIP_CHECK(hipMemcpyAsync(h_keys.data(), d_uniq.ptr, (size_t)nruns * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)nruns * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    idle();
+    k0.synced = k1.synced = d_uniq.synced = d_starts.synced = true;
+    per.assign(Qc, 0);
+    for (uint32_t r = 0; r < nruns; r++) {
+      taxa.push_back((uint32_t)h_keys[r]);
+      counts.push_back(h_cnt[r]);
+      per[(uint32_t)(h_keys[r] >> 32)]++;
+    }
+    for (uint32_t k = 0; k < Qc; k++) coff[(size_t)a + k + 1] = coff[(size_t)a + k] + per[k];
+  }
+  finish();
+}
+
+void ResidentIndex::lca_many(const KmerMinHash* const* queries, uint32_t nq, uint64_t* count_offsets, std::vector<uint32_t>* taxa,
+                             std::vector<uint64_t>* counts, uint64_t* query_offsets, uint32_t* hash_taxon, Device& dev) {
+  check_lca_sketches("lca_many");
+  // every query as gather_many checks it; the lowest failing query decides, and the message names it
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string who = "lca_many: query " + std::to_string(q);
+    if (queries[q]->num != 0) throw Error(kMsg, who + " is a num sketch; only scaled sketches (num == 0) have lca counts");
+    try {
+      check_sketch(*queries[q]);
+    } catch (const Error& e) {
+      throw Error(e.code, who + ": " + e.message);
+    }
+  }
+  check_directory_size("lca_many");
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  hipStream_t s = dev.stream();
+  // the batch as one CSR in device memory: a state that lives in HBM is copied there device to device, the host states go up
+  // in one upload
+  std::vector<uint64_t> qoff((size_t)nq + 1, 0);
+  for (uint32_t q = 0; q < nq; q++) {
+    const KmerMinHash& Q = *queries[q];
+    Q.flush_pending();
+    const uint64_t lq = Q.dev ? Q.dev->n : Q.mins.size();
+    if (lq >= (1ull << 31)) throw_internal("lca_many: a query of 2^31 or more hashes");
+    qoff[q + 1] = qoff[q] + lq;
+  }
+  const uint64_t total = qoff[nq];
+  PoolBlock csr(total * 8);
+  uint64_t* d_h = csr.as<uint64_t>();
+  std::vector<uint64_t> stage;
+  std::vector<uint64_t> stage_at((size_t)nq, 0);
+  for (uint32_t q = 0; q < nq; q++) {
+    const KmerMinHash& Q = *queries[q];
+    if (Q.dev) continue;
+    stage_at[q] = stage.size();
+    stage.insert(stage.end(), Q.mins.begin(), Q.mins.end());
+  }
+  PoolBlock up(stage.size() * 8);
+  if (!stage.empty()) HIP_CHECK(hipMemcpyAsync(up.ptr, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
+  for (uint32_t q = 0; q < nq; q++) {
+    const KmerMinHash& Q = *queries[q];
+    const uint64_t lq = qoff[q + 1] - qoff[q];
+    if (lq == 0) continue;
+    const void* src = Q.dev ? Q.dev->uniq.ptr : (const void*)(up.as<uint64_t>() + stage_at[q]);
+    HIP_CHECK(hipMemcpyAsync(d_h + qoff[q], src, lq * 8, hipMemcpyDeviceToDevice, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));   // (`stage` is read by the upload)
+  csr.synced = up.synced = true;
+  lca_many_dev(d_h, qoff.data(), nq, count_offsets, taxa, counts, hash_taxon, dev, s);
+  if (query_offsets) std::copy(qoff.begin(), qoff.end(), query_offsets);
+}
+
+void ResidentIndex::lca_records(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* off, uint32_t nrec, LcaRow* rows, hipStream_t s) {
+  check_match_batch(off, nrec, total_len);
+  if (!has_taxonomy()) throw Error(kMsg, "lca_records: the index has no taxonomy (smh_index_set_taxonomy)");
+  auto blank = [&](uint32_t a, uint32_t e) { for (uint32_t r = a; r < e; r++) rows[r] = LcaRow{0, 0, 0, 0, kLcaNoTaxon, 0}; };
+  auto tail = [&](const MatchDirectory& dir, const MatchFold& f) {
+    Device& dev = Device::get();
+    const LcaView L = ensure_lca(dir, dev, s);
+    PoolBlock d_out((size_t)f.nf * sizeof(LcaRow)), d_big((size_t)f.nf * 4 + 4);
+    launch_lca_records(L.tax, L.hash_taxon, f.rank, f.rows, f.rec_first, f.nf, d_out.as<LcaRow>(), d_big.as<uint32_t>(),
+                       d_big.as<uint32_t>() + f.nf, dev, s);
+    fetch_rows(d_out.ptr, rows + f.f0, f.nf, Engine::get(), s);
+    d_out.synced = d_big.synced = true;   // (fetch_rows has waited for the stream)
+  };
+  match_folds(seq_dev, total_len, off, nrec, false, s, blank, tail);
+}
+
+}  // namespace smh

@@ -1,7 +1,8 @@
 // match.cpp -- ResidentIndex::match (the rules are in include/sourmash_amd.h, "Matching records"): the folds
 // of a batch cut at record boundaries (the index's hash directory is index.cpp's), and per fold the grouped fold's own
 // sequence (hash with positions, positions to records, two sorts, the two-key run-length pass) followed by the probe, the
-// tally with its two regimes and the read-back.  The kernels are in match_kernels.hip.
+// tally with its two regimes and the read-back.  The kernels are in match_kernels.hip.  Everything up to the probe is
+// match_folds, which lca.cpp's records route runs too; what follows the probe is the caller's `tail`.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -16,10 +17,14 @@ uint64_t g_match_pair_budget = kMatchPairBudget;
 
 namespace {
 [[noreturn]] void refuse(const std::string& what) { throw Error(kMsg, "match: " + what); }
+}  // namespace
 
 // The rows of a fold into the caller's pageable array through two page-locked halves: the copy out of one half runs while
 // the transfer into the other is in flight (a pageable destination would be staged by the runtime, one piece after another).
-void fetch_rows(const MatchRow* d_rows, MatchRow* out, size_t n, Engine& E, hipStream_t s) {
+static_assert(sizeof(MatchRow) == sizeof(LcaRow), "fetch_rows serves both row types");
+void fetch_rows(const void* d_rows_v, void* out_v, size_t n, Engine& E, hipStream_t s) {
+  const MatchRow* d_rows = static_cast<const MatchRow*>(d_rows_v);
+  MatchRow* out = static_cast<MatchRow*>(out_v);
   constexpr size_t kHalf = 1u << 16;   // rows per half: 1.5 MiB
   const size_t half = std::min(n, kHalf);
   E.pin_a.ensure(2 * half * sizeof(MatchRow));
@@ -35,7 +40,6 @@ void fetch_rows(const MatchRow* d_rows, MatchRow* out, size_t n, Engine& E, hipS
     done = next; len = nlen; cur ^= 1;
   }
 }
-}  // namespace
 
 void ResidentIndex::check_matchable() const {
   if (n == 0) refuse("the index holds no node (ksize, seed and max_hash are those of node 0)");
@@ -54,18 +58,17 @@ void ResidentIndex::check_matchable() const {
   }
 }
 
-void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* off, uint32_t nrec, MatchRow* rows, uint64_t* hit_offsets,
-                          std::vector<uint64_t>* hit_hashes, hipStream_t s) {
+void ResidentIndex::check_match_batch(const uint64_t* off, uint32_t nrec, uint64_t total_len) const {
   check_matchable();
   for (uint32_t r = 0; r < nrec; r++)
     if (off[r + 1] < off[r]) refuse("offsets must ascend (record " + std::to_string(r) + ")");
   if (nrec && off[nrec] > total_len)
     refuse("the last offset " + std::to_string(off[nrec]) + " lies beyond the batch's " + std::to_string(total_len) + " bytes");
-  // the rows of records no fold's kernels see (a batch without a window, a fold without a candidate); the others come
-  // back whole from the device
-  auto blank = [&](uint32_t a, uint32_t e) { for (uint32_t r = a; r < e; r++) rows[r] = MatchRow{0, 0, 0, 0, kMatchMiss, 0}; };
-  if (hit_offsets) std::fill(hit_offsets, hit_offsets + nrec + 1, 0);
-  if (hit_hashes) hit_hashes->clear();
+}
+
+void ResidentIndex::match_folds(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* off, uint32_t nrec, bool want_hits,
+                                hipStream_t s, const std::function<void(uint32_t, uint32_t)>& blank,
+                                const std::function<void(const MatchDirectory&, const MatchFold&)>& tail) {
   const uint32_t ksize = params[0].ksize;
   const uint64_t seed = params[0].seed, max_hash = params[0].max_hash;
   bool any_long = false;
@@ -92,7 +95,6 @@ void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint
   const double frac = (double)(((long double)max_hash + 1.0L) / 18446744073709551616.0L);
   const double hard = 1.6e9;   // (estimate_capacity adds a quarter and 64 Ki: below 2^31)
   const double budget = std::min((double)std::max<uint64_t>(g_match_pair_budget, 1), hard);
-  const bool want_hits = hit_offsets != nullptr;
   for (uint32_t r0 = 0; r0 < nrec;) {
     double cost = 0;
     uint32_t r1 = r0;
@@ -125,17 +127,41 @@ void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint
     if (nruns == 0) { blank(f0, r1); continue; }
 
     PoolBlock d_rows((size_t)nf * sizeof(MatchRow)), d_first((size_t)nf * 4), d_pairs((size_t)nf * 8), d_rank((size_t)nruns * 4),
-        d_flag(want_hits ? ((size_t)nruns + 1) * 4 : 4), d_big((size_t)nf * 4 + 4);
-    uint32_t* big_count = d_big.as<uint32_t>() + nf;
+        d_flag(want_hits ? ((size_t)nruns + 1) * 4 : 4);
     HIP_CHECK(hipMemsetAsync(d_rows.ptr, 0, (size_t)nf * sizeof(MatchRow), s));
     HIP_CHECK(hipMemsetAsync(d_first.ptr, 0xff, (size_t)nf * 4, s));
     HIP_CHECK(hipMemsetAsync(d_pairs.ptr, 0, (size_t)nf * 8, s));
-    HIP_CHECK(hipMemsetAsync(big_count, 0, 4, s));
     launch_match_probe(dir, E.uniq.as<uint64_t>(), E.uniq2.as<uint64_t>(), E.starts.as<uint32_t>(), nruns, (uint32_t)nc, f0,
                        d_rows.as<MatchRow>(), d_first.as<uint32_t>(), d_pairs.as<unsigned long long>(), d_rank.as<uint32_t>(),
                        want_hits ? d_flag.as<uint32_t>() : nullptr, dev, s);
-    launch_match_tally(dir, d_rank.as<uint32_t>(), d_rows.as<MatchRow>(), d_first.as<uint32_t>(), d_pairs.as<unsigned long long>(), nf,
-                       d_big.as<uint32_t>(), big_count, dev, s);
+    MatchFold f;
+    f.f0 = f0; f.nf = nf; f.nruns = nruns;
+    f.run_hash = E.uniq.as<uint64_t>();
+    f.rows = d_rows.as<MatchRow>(); f.rec_first = d_first.as<uint32_t>(); f.rec_pairs = d_pairs.as<unsigned long long>();
+    f.rank = d_rank.as<uint32_t>(); f.hit_flag = want_hits ? d_flag.as<uint32_t>() : nullptr;
+    tail(dir, f);
+    HIP_CHECK(hipStreamSynchronize(s));
+    d_rows.synced = d_first.synced = d_pairs.synced = d_rank.synced = d_flag.synced = true;
+  }
+}
+
+void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* off, uint32_t nrec, MatchRow* rows, uint64_t* hit_offsets,
+                          std::vector<uint64_t>* hit_hashes, hipStream_t s) {
+  // the rows of records no fold's kernels see (a batch without a window, a fold without a candidate); the others come
+  // back whole from the device
+  auto blank = [&](uint32_t a, uint32_t e) { for (uint32_t r = a; r < e; r++) rows[r] = MatchRow{0, 0, 0, 0, kMatchMiss, 0}; };
+  check_match_batch(off, nrec, total_len);   // (in front of the first write)
+  if (hit_offsets) std::fill(hit_offsets, hit_offsets + nrec + 1, 0);
+  if (hit_hashes) hit_hashes->clear();
+  const bool want_hits = hit_offsets != nullptr;
+  auto tail = [&](const MatchDirectory& dir, const MatchFold& f) {
+    Device& dev = Device::get();
+    Engine& E = Engine::get();
+    const uint32_t nf = f.nf;
+    PoolBlock d_big((size_t)nf * 4 + 4);
+    uint32_t* big_count = d_big.as<uint32_t>() + nf;
+    HIP_CHECK(hipMemsetAsync(big_count, 0, 4, s));
+    launch_match_tally(dir, f.rank, f.rows, f.rec_first, f.rec_pairs, nf, d_big.as<uint32_t>(), big_count, dev, s);
     uint32_t nbig = 0;
     HIP_CHECK(hipMemcpyAsync(&nbig, big_count, 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -149,23 +175,24 @@ void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint
       const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g_match_pair_budget / n, 1), std::min<uint32_t>(nbig, 1u << 16));
       PoolBlock slab((size_t)per * n * 4);
       for (uint32_t at = 0; at < nbig; at += per) {
-        launch_match_dense(dir, d_rank.as<uint32_t>(), d_rows.as<MatchRow>(), d_first.as<uint32_t>(), d_big.as<uint32_t>() + at,
-                           std::min(per, nbig - at), n, slab.as<uint32_t>(), dev, s);
+        launch_match_dense(dir, f.rank, f.rows, f.rec_first, d_big.as<uint32_t>() + at, std::min(per, nbig - at), n, slab.as<uint32_t>(),
+                           dev, s);
         dev.count("match_dense_round");
       }
       HIP_CHECK(hipStreamSynchronize(s));   // (big is read by the upload above)
       slab.synced = true;
     }
-    fetch_rows(d_rows.as<MatchRow>(), rows + f0, nf, E, s);
+    fetch_rows(f.rows, rows + f.f0, nf, E, s);
+    d_big.synced = true;   // (fetch_rows has waited for the stream behind the last kernel that reads the list)
     if (want_hits) {
-      uint32_t* total_dev = d_flag.as<uint32_t>() + nruns;
+      uint32_t* total_dev = f.hit_flag + f.nruns;
       uint32_t nhit = 0;
-      exclusive_scan_u32_dev(d_flag.as<uint32_t>(), nruns, total_dev, dev.scratch, s);
+      exclusive_scan_u32_dev(f.hit_flag, f.nruns, total_dev, dev.scratch, s);
       HIP_CHECK(hipMemcpyAsync(&nhit, total_dev, 4, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       if (nhit) {
         PoolBlock d_hits((size_t)nhit * 8);
-        launch_match_hit_scatter(E.uniq.as<uint64_t>(), d_rank.as<uint32_t>(), d_flag.as<uint32_t>(), nruns, d_hits.as<uint64_t>(), dev, s);
+        launch_match_hit_scatter(f.run_hash, f.rank, f.hit_flag, f.nruns, d_hits.as<uint64_t>(), dev, s);
         const size_t have = hit_hashes->size();
         hit_hashes->resize(have + nhit);
         HIP_CHECK(hipMemcpyAsync(hit_hashes->data() + have, d_hits.ptr, (size_t)nhit * 8, hipMemcpyDeviceToHost, s));
@@ -173,12 +200,12 @@ void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint
         d_hits.synced = true;
       }
     }
-    HIP_CHECK(hipStreamSynchronize(s));
-    d_rows.synced = d_first.synced = d_pairs.synced = d_rank.synced = d_flag.synced = d_big.synced = true;
-  }
+  };
+  match_folds(seq_dev, total_len, off, nrec, want_hits, s, blank, tail);
   // folds follow the records and a fold's hit runs follow (record, hash): the list is the CSR already
   if (hit_offsets)
     for (uint32_t r = 0; r < nrec; r++) hit_offsets[r + 1] = hit_offsets[r] + rows[r].hit_distinct;
 }
 
 }  // namespace smh
+

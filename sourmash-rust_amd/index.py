@@ -16,7 +16,7 @@ import math
 
 import numpy as np
 
-from ._lib import SmhGatherRow, SmhMatchRow, lib, u64p
+from ._lib import SmhGatherRow, SmhLcaRow, SmhMatchRow, lib, u32p, u64p
 from .errors import SourmashError, call
 
 UNASSIGNED = 0xFFFFFFFF
@@ -37,6 +37,11 @@ MatchResult = collections.namedtuple("MatchResult", ["windows", "distinct", "hit
                                                      "hit_offsets", "hit_hashes"])
 NO_MATCH = 0xFFFFFFFF
 _MATCH_ROW = np.dtype([(name, np.uint32) for name, _ in SmhMatchRow._fields_])
+# one numpy array per field of SmhLcaRow (uint32, a record each)
+LcaRecords = collections.namedtuple("LcaRecords", ["windows", "distinct", "hit_distinct", "assigned_distinct", "taxon", "status"])
+NO_TAXON = 0xFFFFFFFF
+LCA_NONE, LCA_FOUND, LCA_DISAGREE = 0, 1, 2
+_LCA_ROW = np.dtype([(name, np.uint32) for name, _ in SmhLcaRow._fields_])
 
 
 def scaled_of_max_hash(max_hash):
@@ -52,6 +57,38 @@ def max_hash_of_scaled(scaled):
     if scaled <= 0:
         raise ValueError("scaled must be positive")
     return min((1 << 64) // scaled, (1 << 64) - 1)
+
+
+def lca_summarize(parent, taxa, counts):
+    """The counts of lca_counts rolled up (`lca summarize`): dict taxon -> the sum of the counts of the taxon and of everything
+    below it.  Host work on the small output: the device does not roll up."""
+    out = collections.Counter()
+    for t, c in zip(taxa, counts):
+        t, c = int(t), int(c)
+        while True:
+            out[t] += c
+            if t == 0:
+                break
+            t = int(parent[t])
+    return dict(out)
+
+
+def lca_classify(parent, taxa, counts, threshold=1):
+    """(taxon, status) of the classification rule applied to the taxa with count >= threshold (`lca classify`): descend from
+    the root through the union of their root paths while there is exactly one child; LCA_FOUND when nothing lies below where
+    it stops, LCA_DISAGREE at a branching, (NO_TAXON, LCA_NONE) when no taxon reaches the threshold."""
+    kept = {int(t) for t, c in zip(taxa, counts) if int(c) >= threshold}
+    if not kept:
+        return NO_TAXON, LCA_NONE
+    children = {}
+    for t in kept:
+        while t != 0 and t not in children.get(int(parent[t]), ()):
+            children.setdefault(int(parent[t]), set()).add(t)
+            t = int(parent[t])
+    at = 0
+    while len(children.get(at, ())) == 1:
+        (at,) = children[at]
+    return at, LCA_DISAGREE if children.get(at) else LCA_FOUND
 
 
 def _is_scaled(mh):
@@ -335,6 +372,101 @@ class ResidentIndex:
             hashes = np.ctypeslib.as_array(hp, shape=(nh.value,)).copy() if nh.value else np.zeros(0, np.uint64)
             _free(C.cast(hp, C.c_void_p))
         return MatchResult(*[rows[name] for name in _MATCH_ROW.names], off, hashes)   # views of the rows: no copy
+
+    # --- taxonomic LCA (additive ABI smh_index_*taxonomy, smh_index_lca_*; the rules: include/sourmash_amd.h, "Taxonomic LCA")
+    def set_taxonomy(self, parent, node_taxon):
+        """parent[t] of every taxon (taxon 0 is the root, parent[t] < t) and the taxon of every node (NO_TAXON: none).  Replaces
+        an earlier taxonomy; the cut indexes downsample() cached are given back (a child takes its taxonomy when it is made)."""
+        parent = np.ascontiguousarray(parent, dtype=np.uint32)
+        node_taxon = np.ascontiguousarray(node_taxon, dtype=np.uint32)
+        call(self._L.smh_index_set_taxonomy, self._h, parent.ctypes.data_as(u32p), len(parent), node_taxon.ctypes.data_as(u32p),
+             len(node_taxon))
+        self._children.clear()
+
+    @property
+    def has_taxonomy(self):
+        return bool(self._L.smh_index_has_taxonomy(self._h))
+
+    def lca_counts(self, queries, hash_taxon=False, downsample=False):
+        """Per query (taxa, counts): the taxa of its assigned hashes ascending (uint32) and how many hashes each got (uint64),
+        from one device call (smh_index_lca_many).  hash_taxon=True: per query (taxa, counts, per_hash), per_hash the taxon of
+        every hash of the query in ascending hash order or NO_TAXON.  downsample=True: the queries are grouped by the max_hash
+        at which each meets the index, every group is one call; per_hash then runs over the hashes of the cut query."""
+        queries = list(queries)
+        if downsample:
+            met = [self._meet_sketch(q) for q in queries]
+            groups = {}
+            for k, (idx, _) in enumerate(met):
+                groups.setdefault(id(idx), (idx, []))[1].append(k)
+            out = [None] * len(queries)
+            for idx, members in groups.values():
+                for k, res in zip(members, idx.lca_counts([met[k][1] for k in members], hash_taxon)):
+                    out[k] = res
+            return out
+        nqs = len(queries)
+        arr = (C.c_void_p * max(nqs, 1))(*[q._p for q in queries])
+        c_off = np.zeros(nqs + 1, dtype=np.uint64)
+        q_off = np.zeros(nqs + 1, dtype=np.uint64)
+        per = np.empty(sum(len(q) for q in queries), dtype=np.uint32) if hash_taxon else None
+        tp, cp = u32p(), u64p()
+        call(self._L.smh_index_lca_many, self._h, arr, nqs, c_off.ctypes.data_as(u64p), C.byref(tp), C.byref(cp),
+             q_off.ctypes.data_as(u64p), per.ctypes.data_as(u32p) if hash_taxon else None)
+        return self._lca_split(tp, cp, c_off, q_off, per)
+
+    def lca_counts_block_dev(self, hashes_dev, offsets, hash_taxon=False, stream=None):
+        """lca_counts of a CSR in device memory (smh_index_lca_block_dev): query q is the hashes [offsets[q], offsets[q + 1])
+        behind the device pointer hashes_dev, ascending strictly; offsets on the host."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nqs = len(offsets) - 1
+        c_off = np.zeros(nqs + 1, dtype=np.uint64)
+        per = np.empty(int(offsets[-1] - offsets[0]), dtype=np.uint32) if hash_taxon else None
+        tp, cp = u32p(), u64p()
+        call(self._L.smh_index_lca_block_dev, self._h, C.c_void_p(hashes_dev), offsets.ctypes.data_as(u64p), nqs,
+             c_off.ctypes.data_as(u64p), C.byref(tp), C.byref(cp), per.ctypes.data_as(u32p) if hash_taxon else None,
+             C.c_void_p(stream or 0))
+        return self._lca_split(tp, cp, c_off, offsets - offsets[0], per)
+
+    @staticmethod
+    def _lca_split(tp, cp, c_off, q_off, per):
+        from .minhash import _free
+        total = int(c_off[-1])
+        try:
+            taxa = np.ctypeslib.as_array(tp, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
+            counts = np.ctypeslib.as_array(cp, shape=(total,)).copy() if total else np.zeros(0, np.uint64)
+        finally:
+            _free(C.cast(tp, C.c_void_p))
+            _free(C.cast(cp, C.c_void_p))
+        out = []
+        for k in range(len(c_off) - 1):
+            a, b = int(c_off[k]), int(c_off[k + 1])
+            one = (taxa[a:b], counts[a:b])
+            out.append(one + (per[int(q_off[k]):int(q_off[k + 1])],) if per is not None else one)
+        return out
+
+    def lca_classify_records(self, records, stream=None):
+        """Every record of a batch classified (smh_index_lca_*): LcaRecords of numpy arrays, one entry per record.  records: the
+        three forms match() takes.  taxon is NO_TAXON and status LCA_NONE for a record without an assigned hit; status is
+        LCA_FOUND or LCA_DISAGREE otherwise."""
+        from .fastx import Records
+
+        def run(n, fn, *front):
+            rows = np.zeros(n, dtype=_LCA_ROW)
+            call(fn, self._h, *front, rows.ctypes.data_as(C.c_void_p))
+            return rows
+
+        if isinstance(records, Records):
+            rows = run(len(records), self._L.smh_index_lca_records, records._p)
+        elif isinstance(records, tuple):
+            ptr, total, offsets = records
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            rows = run(len(offsets) - 1, lambda h, *a: self._L.smh_index_lca_sequences_dev(h, *a, C.c_void_p(stream or 0)),
+                       C.c_void_p(ptr), int(total), offsets.ctypes.data_as(u64p), len(offsets) - 1)
+        else:
+            seqs = [bytes(s) for s in records]
+            offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+            np.cumsum(np.array([len(s) for s in seqs], dtype=np.uint64), out=offsets[1:])
+            rows = run(len(seqs), self._L.smh_index_lca_sequences, b"".join(seqs), offsets.ctypes.data_as(u64p), len(seqs))
+        return LcaRecords(*[rows[name] for name in _LCA_ROW.names])   # views of the rows: no copy
 
     @property
     def has_abundances(self):

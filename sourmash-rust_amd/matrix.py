@@ -168,6 +168,22 @@ def set_match_pair_budget(pairs):
     lib().smh_match_set_pair_budget(int(pairs))
 
 
+def lca_geometry():
+    """(owners of a hash one lane folds, distinct sampled hashes of a record one lane folds, threads a longer one gets)"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().smh_lca_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def lca_budget():
+    return int(lib().smh_lca_budget())
+
+
+def set_lca_budget(keys):
+    """the query hashes one chunk of ResidentIndex.lca_counts may hold (smh_lca_set_budget); 0 restores the default"""
+    lib().smh_lca_set_budget(int(keys))
+
+
 def gather_many_budget():
     return int(lib().smh_gather_many_budget())
 
