@@ -328,6 +328,77 @@ int smh_index_gather_block_dev(SmhIndex *index, const uint64_t *q_hashes_dev, co
 void smh_gather_many_set_budget(uint64_t pairs);
 uint64_t smh_gather_many_budget(void);
 
+/* Search of many queries in one call: the (query, node) pairs over a threshold, as a sparse list (what `manysearch`,
+ * `multisearch` and `pairwise` report), through the index's hash directory (the directory is the one
+ * "Matching records" describes: it is built by the first match, gather-many, LCA or search-many call on the index and kept).
+ * The reference crate has no batch search, so the rules are fixed here; restated in tests/search_many_restatement.py.
+ *   Inputs     the n resident sketches S_0 .. S_{n-1}, all scaled (num == 0); a batch of scaled queries Q_0 .. Q_{Q-1};
+ *              metric, threshold (double), threshold_common (0 is read as 1).
+ *   Per pair   common = |Q_q ^ S_i|, and the metric's value:
+ *                SMH_SEARCH_JACCARD            common / max(1, |Q_q| + |S_i| - common)   (smh_index_find's similarity of
+ *                                                                                         scaled sketches)
+ *                SMH_SEARCH_CONTAINMENT_NODE   common / |S_i|                            (smh_index_find, containment)
+ *                SMH_SEARCH_CONTAINMENT_QUERY  common / |Q_q|
+ *                SMH_SEARCH_MAX_CONTAINMENT    common / min(|Q_q|, |S_i|)
+ *              The value is ONE IEEE binary64 division of the two integers converted to double (the library is built
+ *              without fast math).  The pair is reported iff common >= max(1, threshold_common) AND value > threshold:
+ *              the comparison is strict, as smh_index_find's.  A pair that shares nothing is never reported, whatever the
+ *              threshold is.
+ *   Outputs    row_offsets (the caller's, n_queries + 1 entries): the rows of query q are
+ *              (*rows)[row_offsets[q] .. row_offsets[q + 1]).  *rows is a malloc'ed array of row_offsets[n_queries]
+ *              SmhSearchRow (at least one element is allocated); the caller frees it with free().  The rows are ordered by
+ *              query, then by node ascending.  Every field is an integer, so parity is equality; the metric's value, ANI
+ *              and the like are derived from the integers by the caller.  No row depends on chunking, the budget or the
+ *              order of atomics.
+ *   Equality   For threshold >= 0 and threshold_common <= 1 the nodes of query q are exactly, and in the order of,
+ *              smh_index_find(index, queries[q], threshold, false, ...) under SMH_SEARCH_JACCARD and
+ *              smh_index_find(index, queries[q], threshold, true, ...) under SMH_SEARCH_CONTAINMENT_NODE.
+ *   Errors     decided before the device is touched, and nothing is written.  row_offsets == NULL or rows == NULL (a panic, as
+ *              every NULL argument), a NaN threshold and an unknown metric (MSG) are refused before anything else is looked at.  Each query is checked
+ *              as smh_index_gather_many checks it (num != 0 on the query or on any node: MSG; incompatible: 101-104); the
+ *              error of the LOWEST failing query is reported and the message names that query.  An index of 2^31 or more
+ *              resident hashes is refused (MSG): the directory takes fewer.  n_queries == 0, empty queries, an empty index
+ *              and queries that share nothing give zero rows and no error.  If the rows cannot be allocated the call
+ *              returns MSG, having written nothing the caller must free.
+ * smh_index_search_many       the queries are sketches.  A query whose state lives in HBM is staged device to device (it is
+ *                             not brought to the host); the host-resident queries go up in one upload.
+ * smh_index_search_block_dev  the CSR / device form, with the contract of smh_index_gather_block_dev: query q is
+ *                             q_hashes_dev[q_offsets[q] .. q_offsets[q + 1]), q_offsets on the host (n_queries + 1,
+ *                             ascending); the index's nodes must all be scaled sketches that agree in ksize, molecule, seed
+ *                             and max_hash (else MSG); hashes must ascend strictly inside a query.  stream: the caller's.
+ * smh_index_search_self       the queries are the index's own nodes, read from the resident CSR in place (no staging copy, no
+ *                             upload); row_offsets has smh_index_len(index) + 1 entries.  Rows with node == query are never
+ *                             reported; with upper_only only rows with node > query are.  The result equals
+ *                             smh_index_search_many of the same sketches with those rows taken out.  Works on an index
+ *                             smh_index_downsample returned: its nodes are the cut ones.
+ * smh_search_many_set_budget  the (query, node) counters one chunk of the batch may hold: the batch is cut into chunks at
+ * smh_search_many_budget      query boundaries, a query alone always makes a chunk.  0 restores the default of 2^26 -- a memory
+ *                             cap, not a measured optimum.  Process-wide; results never depend on it.
+ * smh_search_geometry         the sizes at which the kernels' branches change: the owners of a hash up to which the lane
+ *                             holding the query position walks them itself (longer lists: its wave), the nodes of one
+ *                             workgroup of the select and emit kernels, and the most queries a chunk takes (tests, tools).
+ * Per chunk the work is one probe per query hash plus one atomic per (position, owner) hit (not a pass over the resident
+ * hashes), 4 bytes written and twice 4 bytes read per (query, node) pair, and 16 bytes per reported row. */
+enum {
+  SMH_SEARCH_JACCARD = 0,
+  SMH_SEARCH_CONTAINMENT_NODE = 1,
+  SMH_SEARCH_CONTAINMENT_QUERY = 2,
+  SMH_SEARCH_MAX_CONTAINMENT = 3
+};
+typedef struct SmhSearchRow {
+  uint32_t node, common, node_size, query_size;
+} SmhSearchRow;   /* 16 bytes */
+int smh_index_search_many(SmhIndex *index, const KmerMinHash *const *queries, uint32_t n_queries, uint32_t metric, double threshold,
+                          uint32_t threshold_common, uint64_t *row_offsets, SmhSearchRow **rows);
+int smh_index_search_block_dev(SmhIndex *index, const uint64_t *q_hashes_dev, const uint64_t *q_offsets, uint32_t n_queries,
+                               uint32_t metric, double threshold, uint32_t threshold_common, uint64_t *row_offsets,
+                               SmhSearchRow **rows, void *stream);
+int smh_index_search_self(SmhIndex *index, uint32_t metric, double threshold, uint32_t threshold_common, bool upper_only,
+                          uint64_t *row_offsets, SmhSearchRow **rows);
+void smh_search_many_set_budget(uint64_t pairs);
+uint64_t smh_search_many_budget(void);
+void smh_search_geometry(uint32_t *short_owners, uint32_t *node_tile, uint32_t *max_queries);
+
 /* Angular similarity on abundances: what `sourmash compare` and `sourmash search` report by default for sketches that
  * track abundances.  The reference crate has no weighted compare, so the rules are fixed here -- DESIGN.md 3.10, restated
  * in tests/angular_restatement.py.  For two sketches A and B that both track abundances, hashes ascending and distinct, one
@@ -707,8 +778,10 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * of smh_gather_rounds_per_sync() rounds), "angular_block" (the angular similarity's block kernel), "match_probe" (the runs of a
  * fold against the hash directory), "match_tally" (the per-record tally: its LDS launch, and one entry per dense round),
  * "gather_many_probe" (a chunk's probe, counts and sizing), "gather_many_fill" (the scan and the hit lists),
- * "gather_many_rounds" (one entry per batch of smh_gather_rounds_per_sync() rounds of a chunk).  Event counters under the
- * same call: "gather_many_chunk" (chunks run), "match_directory_built". */
+ * "gather_many_rounds" (one entry per batch of smh_gather_rounds_per_sync() rounds of a chunk), "search_many_probe" (a
+ * chunk's probe), "search_many_select" (the rule on every counter, the counts per tile and their scan), "search_many_emit" (the
+ * rows of a chunk).  Event counters under the same call: "gather_many_chunk", "search_many_chunk" (chunks run),
+ * "match_directory_built". */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -36,6 +36,10 @@ class SmhGatherRow(C.Structure):
                 ("size_match", C.c_uint32), ("abund_sum", C.c_uint64)]
 
 
+class SmhSearchRow(C.Structure):
+    _fields_ = [("node", C.c_uint32), ("common", C.c_uint32), ("node_size", C.c_uint32), ("query_size", C.c_uint32)]
+
+
 class SmhMatchRow(C.Structure):
     _fields_ = [("windows", C.c_uint32), ("distinct", C.c_uint32), ("hit_windows", C.c_uint32), ("hit_distinct", C.c_uint32),
                 ("best", C.c_uint32), ("best_common", C.c_uint32)]
@@ -170,6 +174,15 @@ _SIGS = {
                                              C.POINTER(C.POINTER(SmhGatherRow)), C.POINTER(C.c_uint32), C.c_void_p]),
     "smh_gather_many_set_budget": (None, [C.c_uint64]),
     "smh_gather_many_budget": (C.c_uint64, []),
+    "smh_index_search_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, u64p,
+                                        C.POINTER(C.POINTER(SmhSearchRow))]),
+    "smh_index_search_block_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, u64p,
+                                             C.POINTER(C.POINTER(SmhSearchRow)), C.c_void_p]),
+    "smh_index_search_self": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_bool, u64p,
+                                        C.POINTER(C.POINTER(SmhSearchRow))]),
+    "smh_search_many_set_budget": (None, [C.c_uint64]),
+    "smh_search_many_budget": (C.c_uint64, []),
+    "smh_search_geometry": (None, [u32p, u32p, u32p]),
     "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
     "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
     "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),

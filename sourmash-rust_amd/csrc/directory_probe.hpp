@@ -1,5 +1,5 @@
 // directory_probe.hpp -- device code shared by the kernels that look hashes up in an index's hash directory
-// (match_kernels.hip, gather_many_kernels.hip; MatchDirectory is in kernels.hpp).  U, the sorted distinct hashes of the whole
+// (match_kernels.hip, gather_many_kernels.hip, search_many_kernels.hip; MatchDirectory is in kernels.hpp).  U, the sorted distinct hashes of the whole
 // index, does not fit LDS when it matters, so LDS holds its sampled top -- every 2^s-th hash, at most kMatchSamples -- and
 // the last s levels of the search read global memory inside a window of 2^s (as k_gather_hits searches the query).
 #pragma once
@@ -55,6 +55,38 @@ __device__ __forceinline__ uint32_t directory_lower_bound(const MatchDirectory& 
     }
   }
   return g;
+}
+
+// --- a chunk of queries probed at once (gather_many_kernels.hip, search_many_kernels.hip): position t of the chunk belongs to
+// query q when qoff[q] <= t < qoff[q + 1], and every owner of a hit position is visited
+constexpr uint32_t kShortOwners = 8;   // owner lists up to this length are walked by the lane that holds the position
+
+// the query holding position t: the last q with qoff[q] <= t (empty queries share their start with the next one)
+__device__ __forceinline__ uint32_t query_of(const uint32_t* __restrict__ qoff, uint32_t nq, uint32_t t) {
+  uint32_t lo = 0, hi = nq;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (qoff[mid] <= t) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// f(owner, q, t) for every owner in owners[b .. e) of every lane with `active`.  EVERY lane of the wave calls it: the long
+// lists are handed round by ballot and walked by all 64 lanes.
+template <class F>
+__device__ __forceinline__ void walk_owners(const uint32_t* __restrict__ owners, bool active, uint32_t b, uint32_t e, uint32_t q,
+                                            uint32_t t, uint32_t lane, F f) {
+  const bool longl = active && e - b > kShortOwners;
+  if (active && !longl)
+    for (uint32_t k = b; k < e; k++) f(owners[k], q, t);
+  uint64_t lm = __ballot(longl);
+  while (lm) {
+    const int src = __builtin_ctzll(lm);
+    lm &= lm - 1;
+    const uint32_t bb = (uint32_t)__shfl((int)b, src), ee = (uint32_t)__shfl((int)e, src);
+    const uint32_t qq = (uint32_t)__shfl((int)q, src), tt = (uint32_t)__shfl((int)t, src);
+    for (uint32_t k = bb + lane; k < ee; k += 64) f(owners[k], qq, tt);
+  }
 }
 
 }  // namespace smh

@@ -779,6 +779,65 @@ int smh_index_gather_block_dev(SmhIndex* index, const uint64_t* q_hashes_dev, co
 void smh_gather_many_set_budget(uint64_t pairs) { smh::g_gather_many_budget = pairs ? pairs : smh::kGatherManyBudget; }
 uint64_t smh_gather_many_budget(void) { return smh::g_gather_many_budget; }
 
+static_assert(sizeof(SmhSearchRow) == 16 && sizeof(smh::SearchRow) == 16, "SmhSearchRow is 16 bytes");
+static_assert(offsetof(SmhSearchRow, query_size) == 12 && offsetof(smh::SearchRow, query_size) == 12, "SmhSearchRow layout");
+static_assert(SMH_SEARCH_JACCARD == smh::kSearchJaccard && SMH_SEARCH_CONTAINMENT_NODE == smh::kSearchContainmentNode &&
+                  SMH_SEARCH_CONTAINMENT_QUERY == smh::kSearchContainmentQuery && SMH_SEARCH_MAX_CONTAINMENT == smh::kSearchMaxContainment,
+              "the metrics of the header are the kernels'");
+
+namespace {
+// what every search call refuses before it looks at anything else -- and before the device: these need none
+void search_require(uint32_t metric, double threshold, uint64_t* row_offsets, SmhSearchRow** rows) {
+  require(row_offsets, "row_offsets"); require(rows, "rows");
+  smh::check_search(metric, threshold);
+}
+}  // namespace
+
+int smh_index_search_many(SmhIndex* index, const KmerMinHash* const* queries, uint32_t n_queries, uint32_t metric, double threshold,
+                          uint32_t threshold_common, uint64_t* row_offsets, SmhSearchRow** rows) {
+  return pad_code([&] {
+    search_require(metric, threshold, row_offsets, rows);
+    auto& dev = smh::Device::get();
+    require(index, "index");
+    if (n_queries) require(queries, "queries");
+    std::vector<const smh::KmerMinHash*> v(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) { require(queries[q], "queries[q]"); v[q] = queries[q]; }
+    *rows = reinterpret_cast<SmhSearchRow*>(index->search_many(v.data(), n_queries, metric, threshold, threshold_common, row_offsets, dev));
+  });
+}
+
+int smh_index_search_block_dev(SmhIndex* index, const uint64_t* q_hashes_dev, const uint64_t* q_offsets, uint32_t n_queries, uint32_t metric,
+                               double threshold, uint32_t threshold_common, uint64_t* row_offsets, SmhSearchRow** rows, void* stream) {
+  return pad_code([&] {
+    search_require(metric, threshold, row_offsets, rows);
+    auto& dev = smh::Device::get();
+    require(index, "index"); require(q_offsets, "q_offsets");
+    // a CSR carries no parameters: the index must speak for itself with one voice
+    if (!(index->uniform && index->all_scaled))
+      throw Error(smh::kMsg, "search_many: the device form needs an index whose nodes are scaled sketches with the same ksize, molecule, "
+                             "seed and max_hash");
+    if (n_queries && q_offsets[n_queries] != q_offsets[0]) require(q_hashes_dev, "q_hashes_dev");
+    *rows = reinterpret_cast<SmhSearchRow*>(index->search_many_dev(q_hashes_dev, q_offsets, n_queries, metric, threshold, threshold_common,
+                                                                   smh::kSearchNotSelf, row_offsets, dev, dev.user_stream(stream)));
+  });
+}
+
+int smh_index_search_self(SmhIndex* index, uint32_t metric, double threshold, uint32_t threshold_common, bool upper_only,
+                          uint64_t* row_offsets, SmhSearchRow** rows) {
+  return pad_code([&] {
+    search_require(metric, threshold, row_offsets, rows);
+    auto& dev = smh::Device::get();
+    require(index, "index");
+    *rows = reinterpret_cast<SmhSearchRow*>(index->search_self(metric, threshold, threshold_common, upper_only, row_offsets, dev));
+  });
+}
+
+void smh_search_many_set_budget(uint64_t pairs) { smh::g_search_many_budget = pairs ? pairs : smh::kSearchManyBudget; }
+uint64_t smh_search_many_budget(void) { return smh::g_search_many_budget; }
+void smh_search_geometry(uint32_t* short_owners, uint32_t* node_tile, uint32_t* max_queries) {
+  smh::search_geometry(short_owners, node_tile, max_queries);
+}
+
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {
   return pad_code([&] { require(rows, "rows"); require(cols, "cols"); rows->compare(*cols, jaccard, common, size, count_common, containment); });

@@ -12,11 +12,15 @@ namespace smh {
 
 uint64_t g_gather_many_budget = kGatherManyBudget;
 
-uint32_t gather_many_chunk_end(const uint64_t* qoff, uint32_t a, uint32_t nq, uint32_t n_nodes, uint64_t budget) {
-  const uint64_t per = std::min<uint64_t>(std::max<uint64_t>(budget / std::max(n_nodes, 1u), 1), kGatherManyMaxQueries);
+uint32_t query_chunk_end(const uint64_t* qoff, uint32_t a, uint32_t nq, uint32_t n_nodes, uint64_t budget, uint32_t max_queries) {
+  const uint64_t per = std::min<uint64_t>(std::max<uint64_t>(budget / std::max(n_nodes, 1u), 1), max_queries);
   uint32_t b = (uint32_t)std::min<uint64_t>(nq, a + per);
   while (b > a + 1 && qoff[b] - qoff[a] >= 0xffffffffull) b--;
   return b;
+}
+
+uint32_t gather_many_chunk_end(const uint64_t* qoff, uint32_t a, uint32_t nq, uint32_t n_nodes, uint64_t budget) {
+  return query_chunk_end(qoff, a, nq, n_nodes, budget, kGatherManyMaxQueries);
 }
 
 void ResidentIndex::gather_many_dev(const uint64_t* qh, const uint64_t* qab, const uint64_t* qoff, uint32_t nq, uint32_t threshold,

@@ -20,6 +20,7 @@
 //   k_gm_subtract  blockIdx.y is the query.  Walks the winner's hit list, labels the positions nobody consumed, sums their
 //                  abundances (one 64-bit atomic per wave) and decrements c[q][owner] for every owner of the position's rank.
 // A done query's workgroups return at once.  Integer atomics only; no cooperative launch, no workgroup waits for another.
+// query_of, walk_owners and kShortOwners are directory_probe.hpp's (shared with search_many_kernels.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,7 +32,6 @@
 namespace smh {
 namespace {
 
-constexpr uint32_t kShortOwners = 8;   // owner lists up to this length are walked by the lane that holds the position
 constexpr uint32_t kUnassigned = 0xffffffffu;
 constexpr uint32_t kPickThreads = 512;
 
@@ -42,34 +42,6 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
   for (int off = 32; off; off >>= 1) { const uint64_t o = __shfl_xor(v, off); v = o > v ? o : v; }
   return v;
-}
-
-// the query holding position t: the last q with qoff[q] <= t (empty queries share their start with the next one)
-__device__ __forceinline__ uint32_t query_of(const uint32_t* __restrict__ qoff, uint32_t nq, uint32_t t) {
-  uint32_t lo = 0, hi = nq;
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (qoff[mid] <= t) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// f(owner, q, t) for every owner in owners[b .. e) of every lane with `active`.  EVERY lane of the wave calls it: the long
-// lists are handed round by ballot and walked by all 64 lanes.
-template <class F>
-__device__ __forceinline__ void walk_owners(const uint32_t* __restrict__ owners, bool active, uint32_t b, uint32_t e, uint32_t q,
-                                            uint32_t t, uint32_t lane, F f) {
-  const bool longl = active && e - b > kShortOwners;
-  if (active && !longl)
-    for (uint32_t k = b; k < e; k++) f(owners[k], q, t);
-  uint64_t lm = __ballot(longl);
-  while (lm) {
-    const int src = __builtin_ctzll(lm);
-    lm &= lm - 1;
-    const uint32_t bb = (uint32_t)__shfl((int)b, src), ee = (uint32_t)__shfl((int)e, src);
-    const uint32_t qq = (uint32_t)__shfl((int)q, src), tt = (uint32_t)__shfl((int)t, src);
-    for (uint32_t k = bb + lane; k < ee; k += 64) f(owners[k], qq, tt);
-  }
 }
 
 // shift, m: directory_sampling

@@ -1,5 +1,6 @@
 // index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
-// similarity on abundances (angular.cpp), matching records (match.cpp), taxonomic LCA (lca.cpp).  The C boundary (ffi.cpp) only checks pointers and
+// similarity on abundances (angular.cpp), matching records (match.cpp), taxonomic LCA (lca.cpp), the thresholded search of a
+// batch (search_many.cpp).  The C boundary (ffi.cpp) only checks pointers and
 // calls in here.
 #pragma once
 #include <functional>
@@ -103,6 +104,17 @@ struct ResidentIndex {
   void gather_many_dev(const uint64_t* q_hashes_dev, const uint64_t* q_abunds_dev, const uint64_t* q_offsets, uint32_t n_queries,
                        uint32_t threshold_common, uint32_t rows_capacity, uint64_t* row_offsets, std::vector<GatherRow>* rows,
                        uint32_t* assigned, Device& dev, hipStream_t s);
+  // (search_many.cpp) The (query, node) pairs over a threshold (the rules: include/sourmash_amd.h, smh_index_search_many).
+  // Each returns the malloc'ed rows (one element at least; the caller frees them with free()), ordered by query, then node;
+  // row_offsets (n_queries + 1, or n + 1 for search_self) is written only when the call succeeds.  metric: SearchMetric.
+  SearchRow* search_many(const KmerMinHash* const* queries, uint32_t n_queries, uint32_t metric, double threshold,
+                         uint32_t threshold_common, uint64_t* row_offsets, Device& dev);
+  // the CSR / device form: query q = q_hashes_dev[q_offsets[q] .. q_offsets[q + 1]).  self (SearchSelf): the queries are this
+  // index's nodes in order, and the diagonal (or everything up to it) is left out
+  SearchRow* search_many_dev(const uint64_t* q_hashes_dev, const uint64_t* q_offsets, uint32_t n_queries, uint32_t metric, double threshold,
+                             uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s);
+  // the index against itself: the queries are read from the resident CSR in place
+  SearchRow* search_self(uint32_t metric, double threshold, uint32_t threshold_common, bool upper_only, uint64_t* row_offsets, Device& dev);
   // (lca.cpp) Taxonomic LCA (the rules: include/sourmash_amd.h, "Taxonomic LCA").  The taxonomy is kept on the host
   // (tax_parent empty: none); the first device call uploads it and computes hash_taxon, one taxon per rank of the directory,
   // kept beside it in lca_dev (counter lca_table_built) and dropped with it, and by set_taxonomy.
@@ -177,7 +189,18 @@ extern uint64_t g_lca_budget;
 constexpr uint64_t kGatherManyBudget = 1ull << 26;
 constexpr uint32_t kGatherManyMaxQueries = 65535;
 extern uint64_t g_gather_many_budget;
+// the rule itself (gather_many.cpp), shared with search_many: max_queries is what one grid dimension carries
+uint32_t query_chunk_end(const uint64_t* q_offsets, uint32_t a, uint32_t n_queries, uint32_t n_nodes, uint64_t budget, uint32_t max_queries);
 uint32_t gather_many_chunk_end(const uint64_t* q_offsets, uint32_t a, uint32_t n_queries, uint32_t n_nodes, uint64_t budget);
+
+// search_many.cpp: the (query, node) counters one chunk of a batch may hold (one u32 array of that size: 256 MiB at the
+// default) -- a memory cap, not a measured optimum.  search_many_chunk_end: query_chunk_end with kSearchMaxQueries
+// (the grid's second dimension of the select and emit kernels).  check_search: the refusals of a metric
+// and a threshold alone (kMsg); needs no device.
+constexpr uint64_t kSearchManyBudget = 1ull << 26;
+extern uint64_t g_search_many_budget;
+uint32_t search_many_chunk_end(const uint64_t* q_offsets, uint32_t a, uint32_t n_queries, uint32_t n_nodes, uint64_t budget);
+void check_search(uint32_t metric, double threshold);
 
 // downsample.cpp (the rules are in include/sourmash_amd.h, "Downsampling").  `out` is a fresh sketch: it
 // receives src's parameters with max_hash / num replaced and the kept prefix.  A state that lives in HBM is cut there into a

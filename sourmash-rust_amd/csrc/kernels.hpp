@@ -1,6 +1,6 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
-// gather_many_kernels.hip, lca_kernels.hip).
+// gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -458,6 +458,35 @@ void launch_gather_many_rounds(const MatchDirectory& d, const GatherManyChunk& c
 // out[p] = the abundance of position p of a device-resident sketch held as run starts (the last run ends at total); starts
 // null: 1 each
 void launch_gather_many_weights(const uint32_t* starts, uint32_t total, uint32_t n, uint64_t* out, hipStream_t s);
+
+// --- search_many_kernels.hip -----------------------------------------------------------
+// The (query, node) pairs of a batch of queries over a threshold (the rules are in include/sourmash_amd.h,
+// smh_index_search_many).  A chunk is a run of consecutive queries, as gather_many's.
+constexpr uint32_t kSearchTile = 1024;           // nodes of one workgroup of the select and emit kernels (256 threads, 4 nodes each)
+constexpr uint32_t kSearchMaxQueries = 65535;    // queries per chunk: the second dimension of their grid
+enum SearchMetric : uint32_t { kSearchJaccard = 0, kSearchContainmentNode = 1, kSearchContainmentQuery = 2, kSearchMaxContainment = 3 };
+enum SearchSelf : uint32_t { kSearchNotSelf = 0, kSearchNoDiagonal = 1, kSearchUpperOnly = 2 };
+struct SearchRow { uint32_t node, common, node_size, query_size; };   // SmhSearchRow
+struct SearchChunk {
+  const uint64_t* hashes = nullptr;        // T hashes: the chunk's queries one after another, ascending strictly inside a query
+  const uint32_t* qoff = nullptr;          // nq + 1: where each query starts among the T positions
+  uint32_t nq = 0, T = 0, n = 0;           // queries, positions, nodes of the index
+  uint32_t q0 = 0;                         // self modes: the node that the chunk's first query is
+  uint32_t* c = nullptr;                   // nq x n: |Q_q ^ S_i| (zeroed by the caller before the probe)
+  uint32_t* tile_rows = nullptr;           // nq x tiles + 1: survivors per (query, tile); after the scan where each tile's rows start
+  uint32_t tiles = 0;                      // ceil(n / kSearchTile)
+  const uint64_t* node_offsets = nullptr;  // the index's CSR offsets in device memory (|S_i|)
+  uint32_t metric = 0, self = 0, threshold_common = 1;
+  double threshold = 0;
+};
+void search_geometry(uint32_t* short_owners, uint32_t* node_tile, uint32_t* max_queries);
+// c of the chunk.  Profile name search_many_probe.
+void launch_search_many_probe(const MatchDirectory& d, const SearchChunk& ck, Device& dev, hipStream_t s);
+// tile_rows counted and scanned in place: tile_rows[nq * tiles] is the chunk's rows.  Profile name search_many_select.
+void launch_search_many_select(const SearchChunk& ck, Device& dev, hipStream_t s);
+// the chunk's rows in order (query, then node), and query_rows[q] = where the rows of query q start.  Profile name
+// search_many_emit.
+void launch_search_many_emit(const SearchChunk& ck, SearchRow* rows, uint32_t* query_rows, Device& dev, hipStream_t s);
 
 // --- lca_kernels.hip -------------------------------------------------------------------
 // Taxonomic LCA on a resident index (the rules are in include/sourmash_amd.h, "Taxonomic LCA").

@@ -1,0 +1,190 @@
+// search_many.cpp -- ResidentIndex::search_many / search_self (the rules are in include/sourmash_amd.h,
+// smh_index_search_many): the checks of every query, the staging of a batch of sketches into one CSR in device memory, the
+// chunks cut at query boundaries, and per chunk the probe, the select, the sizing read-back, the emit and the rows' way into
+// the caller's array.  The kernels are in search_many_kernels.hip; the hash directory is the index's (index.cpp), shared with
+// match, gather_many and the LCA.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <memory>
+#include <string>
+
+#include "index.hpp"
+
+namespace smh {
+
+uint64_t g_search_many_budget = kSearchManyBudget;
+
+uint32_t search_many_chunk_end(const uint64_t* qoff, uint32_t a, uint32_t nq, uint32_t n_nodes, uint64_t budget) {
+  return query_chunk_end(qoff, a, nq, n_nodes, budget, kSearchMaxQueries);
+}
+
+void check_search(uint32_t metric, double threshold) {
+  if (std::isnan(threshold)) throw Error(kMsg, "search_many: the threshold is NaN");
+  if (metric > kSearchMaxContainment) throw Error(kMsg, "search_many: unknown metric " + std::to_string(metric));
+}
+
+namespace {
+// the rows on their way to the caller: malloc'ed (the caller frees them with free()), grown chunk by chunk, one element at least
+struct RowsOut {
+  SearchRow* p = nullptr;
+  size_t len = 0, cap = 0;
+  ~RowsOut() { free(p); }
+  SearchRow* room(size_t more) {   // `more` rows behind the ones held
+    if (len + more > cap || !p) {
+      const size_t want = std::max<size_t>({len + more, cap * 2, 1});
+      SearchRow* np = (SearchRow*)realloc(p, want * sizeof(SearchRow));
+      if (!np) throw Error(kMsg, "search_many: out of memory for " + std::to_string(want) + " rows");
+      p = np; cap = want;
+    }
+    return p + len;
+  }
+  SearchRow* release() { room(0); SearchRow* r = p; p = nullptr; return r; }
+};
+}  // namespace
+
+SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qoff, uint32_t nq, uint32_t metric, double threshold,
+                                          uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s) {
+  check_search(metric, threshold);
+  if (any_num) throw Error(kMsg, "search_many: the index holds a num sketch; only scaled sketches (num == 0) can be searched");
+  if (threshold_common == 0) threshold_common = 1;
+  for (uint32_t q = 0; q < nq; q++) {
+    if (qoff[q + 1] < qoff[q]) throw Error(kMsg, "search_many: offsets must ascend (query " + std::to_string(q) + ")");
+    if (qoff[q + 1] - qoff[q] >= 0xffffffffull) throw_internal("search_many: a query of 2^32 - 1 or more hashes");
+  }
+  check_directory_size("search_many");
+  if (n > 0xffffffffu - 2 * kSearchTile) throw_internal("search_many: too many nodes");
+  const uint64_t total = nq ? qoff[nq] - qoff[0] : 0;
+  std::vector<uint64_t> roff((size_t)nq + 1, 0);
+  RowsOut out;
+  auto finish = [&] {
+    SearchRow* r = out.release();   // (may refuse: nothing has been written then)
+    std::copy(roff.begin(), roff.end(), row_offsets);
+    return r;
+  };
+  if (n == 0 || total == 0) return finish();
+
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  const MatchDirectory dir = ensure_directory("search_many", dev, s);
+  if (dir.n_hashes == 0) return finish();
+  std::vector<uint32_t> rel, qrows;
+  const uint32_t tiles = (n + kSearchTile - 1) / kSearchTile;
+
+  for (uint32_t a = 0, b = 0; a < nq; a = b) {
+    b = search_many_chunk_end(qoff, a, nq, n, g_search_many_budget);
+    const uint32_t Qc = b - a;
+    const uint64_t T = qoff[b] - qoff[a];
+    const uint64_t base = roff[a];
+    for (uint32_t q = a; q < b; q++) roff[q + 1] = base;
+    dev.count("search_many_chunk");
+    if (T == 0) continue;
+    const size_t pairs = (size_t)Qc * n, cells = (size_t)Qc * tiles;
+    PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_c(pairs * 4), d_tiles((cells + 1) * 4), d_qrows((size_t)Qc * 4);
+    SearchChunk ck;
+    ck.hashes = qh + qoff[a];
+    ck.qoff = d_qoff.as<uint32_t>();
+    ck.nq = Qc; ck.T = (uint32_t)T; ck.n = n;
+    ck.q0 = self ? a : 0;
+    ck.c = d_c.as<uint32_t>();
+    ck.tile_rows = d_tiles.as<uint32_t>();
+    ck.tiles = tiles;
+    ck.node_offsets = offsets.as<uint64_t>();
+    ck.metric = metric; ck.self = self; ck.threshold_common = threshold_common; ck.threshold = threshold;
+    rel.resize((size_t)Qc + 1);
+    for (uint32_t k = 0; k <= Qc; k++) rel[k] = (uint32_t)(qoff[a + k] - qoff[a]);
+    HIP_CHECK(hipMemcpyAsync(d_qoff.ptr, rel.data(), ((size_t)Qc + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(ck.c, 0, pairs * 4, s));
+    launch_search_many_probe(dir, ck, dev, s);
+    launch_search_many_select(ck, dev, s);
+    uint32_t R = 0;
+    HIP_CHECK(hipMemcpyAsync(&R, ck.tile_rows + cells, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    d_qoff.synced = d_c.synced = d_tiles.synced = d_qrows.synced = true;
+    if (R == 0) continue;
+    SearchRow* dst = out.room(R);   // (before the device rows: a refusal leaves only blocks that go back by themselves)
+    PoolBlock d_rows((size_t)R * sizeof(SearchRow));
+    launch_search_many_emit(ck, d_rows.as<SearchRow>(), d_qrows.as<uint32_t>(), dev, s);
+    qrows.resize(Qc);
+    HIP_CHECK(hipMemcpyAsync(dst, d_rows.ptr, (size_t)R * sizeof(SearchRow), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(qrows.data(), d_qrows.ptr, (size_t)Qc * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    d_rows.synced = true;
+    out.len += R;
+    for (uint32_t k = 1; k < Qc; k++) roff[a + k] = base + qrows[k];
+    roff[b] = base + R;
+  }
+  return finish();
+}
+
+SearchRow* ResidentIndex::search_many(const KmerMinHash* const* queries, uint32_t nq, uint32_t metric, double threshold,
+                                      uint32_t threshold_common, uint64_t* row_offsets, Device& dev) {
+  check_search(metric, threshold);
+  // every query as gather_many checks it; the lowest failing query decides, and the message names it
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string who = "search_many: query " + std::to_string(q);
+    if (queries[q]->num != 0) throw Error(kMsg, who + " is a num sketch; only scaled sketches (num == 0) can be searched");
+    if (any_num) throw Error(kMsg, who + ": the index holds a num sketch; only scaled sketches (num == 0) can be searched");
+    try {
+      check_sketch(*queries[q]);
+    } catch (const Error& e) {
+      throw Error(e.code, who + ": " + e.message);
+    }
+  }
+  check_directory_size("search_many");
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  hipStream_t s = dev.stream();
+  // the batch as one CSR in device memory: a state that lives in HBM is copied there device to device, the host states go up
+  // in one upload (straight into place when no query lives in HBM)
+  std::vector<uint64_t> qoff((size_t)nq + 1, 0);
+  bool any_dev = false;
+  uint64_t host_total = 0;
+  for (uint32_t q = 0; q < nq; q++) {
+    const KmerMinHash& Q = *queries[q];
+    Q.flush_pending();
+    const uint64_t lq = Q.dev ? Q.dev->n : Q.mins.size();
+    if (lq >= 0xffffffffull) throw_internal("search_many: a query of 2^32 - 1 or more hashes");
+    qoff[q + 1] = qoff[q] + lq;
+    any_dev |= Q.dev != nullptr;
+    if (!Q.dev) host_total += lq;
+  }
+  const uint64_t total = qoff[nq];
+  PoolBlock csr(total * 8);
+  uint64_t* d_h = csr.as<uint64_t>();
+  std::unique_ptr<PoolBlock> up;
+  std::vector<uint64_t> stage;
+  stage.reserve(host_total);
+  for (uint32_t q = 0; q < nq; q++)
+    if (!queries[q]->dev) stage.insert(stage.end(), queries[q]->mins.begin(), queries[q]->mins.end());
+  if (!any_dev) {
+    if (total) HIP_CHECK(hipMemcpyAsync(d_h, stage.data(), total * 8, hipMemcpyHostToDevice, s));
+  } else {
+    up = std::make_unique<PoolBlock>(stage.size() * 8);
+    if (!stage.empty()) HIP_CHECK(hipMemcpyAsync(up->ptr, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
+    uint64_t at = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+      const KmerMinHash& Q = *queries[q];
+      const uint64_t lq = qoff[q + 1] - qoff[q];
+      if (lq == 0) continue;
+      HIP_CHECK(hipMemcpyAsync(d_h + qoff[q], Q.dev ? Q.dev->uniq.ptr : (void*)(up->as<uint64_t>() + at), lq * 8, hipMemcpyDeviceToDevice, s));
+      if (!Q.dev) at += lq;
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(s));   // (`stage` is read by the upload)
+  csr.synced = true;
+  if (up) up->synced = true;
+  return search_many_dev(d_h, qoff.data(), nq, metric, threshold, threshold_common, kSearchNotSelf, row_offsets, dev, s);
+}
+
+SearchRow* ResidentIndex::search_self(uint32_t metric, double threshold, uint32_t threshold_common, bool upper_only, uint64_t* row_offsets,
+                                      Device& dev) {
+  check_search(metric, threshold);
+  if (any_num) throw Error(kMsg, "search_self: the index holds a num sketch; only scaled sketches (num == 0) can be searched");
+  check_index(*this);   // nodes that differ refuse each other (O(1) when they agree)
+  check_directory_size("search_many");
+  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+  // the queries are the nodes where they lie: the resident CSR and its offsets
+  return search_many_dev(hashes.as<uint64_t>(), h_offsets.data(), n, metric, threshold, threshold_common,
+                         upper_only ? kSearchUpperOnly : kSearchNoDiagonal, row_offsets, dev, dev.stream());
+}
+
+}  // namespace smh

@@ -5,6 +5,8 @@
   ResidentIndex.gather      the greedy decomposition of a query (no counterpart in the reference crate: the rules are those
                             of include/sourmash_amd.h, smh_index_gather)
   ResidentIndex.gather_many the same decomposition for a batch of queries in one device call (smh_index_gather_many)
+  ResidentIndex.search_many the (query, node) pairs of a batch of queries over a threshold, as a sparse list (no counterpart
+                            either: include/sourmash_amd.h, smh_index_search_many); pairwise is the index against itself
   ResidentIndex.match       the k-mers of every record of a batch the index knows, and each record's best node (no counterpart
                             either: include/sourmash_amd.h, "Matching records")
 
@@ -16,7 +18,7 @@ import math
 
 import numpy as np
 
-from ._lib import SmhGatherRow, SmhLcaRow, SmhMatchRow, lib, u32p, u64p
+from ._lib import SmhGatherRow, SmhLcaRow, SmhMatchRow, SmhSearchRow, lib, u32p, u64p
 from .errors import SourmashError, call
 
 UNASSIGNED = 0xFFFFFFFF
@@ -42,6 +44,46 @@ LcaRecords = collections.namedtuple("LcaRecords", ["windows", "distinct", "hit_d
 NO_TAXON = 0xFFFFFFFF
 LCA_NONE, LCA_FOUND, LCA_DISAGREE = 0, 1, 2
 _LCA_ROW = np.dtype([(name, np.uint32) for name, _ in SmhLcaRow._fields_])
+# the metrics of search_many / pairwise (SMH_SEARCH_* of include/sourmash_amd.h); their names are SearchResult's float columns
+SEARCH_METRICS = {"jaccard": 0, "containment_node": 1, "containment_query": 2, "max_containment": 3}
+_SEARCH_ROW = np.dtype([(name, np.uint32) for name, _ in SmhSearchRow._fields_])
+
+
+class SearchResult:
+    """The pairs search_many / pairwise report.  offsets (uint64, queries + 1): the rows of query q are
+    [offsets[q], offsets[q + 1]); node, common, node_size, query_size (uint32, a row each) are the device's integers, ordered
+    by query, then node; jaccard, containment_node, containment_query and max_containment (float64, a row each) are derived
+    here from the integers, one division each, as the rule of the header derives the value it thresholds."""
+
+    def __init__(self, offsets, rows, ksize=None, molecule=None):
+        self.offsets = offsets
+        self.node, self.common, self.node_size, self.query_size = (rows[name] for name in _SEARCH_ROW.names)
+        self.ksize, self.molecule = ksize, molecule
+        c, ls, lq = (a.astype(np.float64) for a in (self.common, self.node_size, self.query_size))
+        self.jaccard = c / np.maximum(1.0, lq + ls - c)
+        self.containment_node = c / ls
+        self.containment_query = c / lq
+        self.max_containment = c / np.minimum(lq, ls)
+
+    def __len__(self):
+        return len(self.node)
+
+    def rows_of(self, q):
+        """the slice of query q's rows"""
+        return slice(int(self.offsets[q]), int(self.offsets[q + 1]))
+
+    def query(self):
+        """the query of every row (uint32)"""
+        return np.repeat(np.arange(len(self.offsets) - 1, dtype=np.uint32), np.diff(self.offsets).astype(np.int64))
+
+    def ani(self, column="containment_query"):
+        """value ** (1 / ksize) of a containment column: the point estimate of the average nucleotide identity that
+        `sourmash --ani` prints.  DNA indexes only."""
+        if column not in ("containment_node", "containment_query", "max_containment"):
+            raise ValueError("ani is estimated from a containment column, not from %r" % (column,))
+        if self.molecule != "DNA" or not self.ksize:
+            raise ValueError("ani is defined for DNA sketches only (this result: %s)" % (self.molecule or "an index without nodes"))
+        return getattr(self, column) ** (1.0 / self.ksize)
 
 
 def scaled_of_max_hash(max_hash):
@@ -337,6 +379,84 @@ class ResidentIndex:
         finally:
             _free(C.cast(rows_p, C.c_void_p))
         return out
+
+    # --- the pairs over a threshold (additive ABI smh_index_search_*; the rules: include/sourmash_amd.h, smh_index_search_many)
+    def _search_result(self, nqs, fn, *args):
+        from .minhash import _free
+        row_off = np.zeros(nqs + 1, dtype=np.uint64)
+        rows_p = C.POINTER(SmhSearchRow)()
+        call(fn, *args, row_off.ctypes.data_as(u64p), C.byref(rows_p))
+        try:
+            total = int(row_off[-1])
+            rows = np.ctypeslib.as_array(C.cast(rows_p, C.POINTER(C.c_uint32)), shape=(total * 4,)).view(_SEARCH_ROW).copy() \
+                if total else np.zeros(0, dtype=_SEARCH_ROW)
+        finally:
+            _free(C.cast(rows_p, C.c_void_p))
+        first = self.nodes[0] if self.nodes else None
+        return SearchResult(row_off, rows, first.ksize if first else None, first.molecule if first else None)
+
+    @staticmethod
+    def _threshold_common(threshold_bp, scaled):
+        return int(math.ceil(threshold_bp / scaled))
+
+    def search_many(self, queries, threshold, metric="jaccard", threshold_bp=0, scaled=None, downsample=False):
+        """The (query, node) pairs with metric > threshold and at least ceil(threshold_bp / scaled) hashes in common (one
+        at least), from one device call (smh_index_search_many): a SearchResult.  metric: a key of SEARCH_METRICS.  scaled
+        defaults to the value the queries' max_hash stands for.  Under "jaccard" / "containment_node" the nodes of query q are
+        those of find(q, threshold) / find(q, threshold, containment=True).  downsample=True: the queries are grouped by the
+        max_hash at which each meets the index; every group is one call, and the sizes are those of the cut sketches."""
+        queries = list(queries)
+        if downsample:
+            met = [self._meet_sketch(q) for q in queries]
+            groups = {}
+            for k, (idx, _) in enumerate(met):
+                groups.setdefault(id(idx), (idx, []))[1].append(k)
+            parts = {}
+            for idx, members in groups.values():
+                got = idx.search_many([met[k][1] for k in members], threshold, metric, threshold_bp, scaled)
+                for j, k in enumerate(members):
+                    parts[k] = (got, got.rows_of(j))
+            offsets = np.zeros(len(queries) + 1, dtype=np.uint64)
+            rows = np.zeros(sum(sl.stop - sl.start for _, sl in parts.values()), dtype=_SEARCH_ROW)
+            for k in range(len(queries)):
+                got, sl = parts[k]
+                a = int(offsets[k])
+                offsets[k + 1] = a + sl.stop - sl.start
+                for name in _SEARCH_ROW.names:
+                    rows[name][a:int(offsets[k + 1])] = getattr(got, name)[sl]
+            first = self.nodes[0] if self.nodes else None
+            return SearchResult(offsets, rows, first.ksize if first else None, first.molecule if first else None)
+        nqs = len(queries)
+        thrs = set()
+        for q in queries:
+            mx = q.max_hash
+            thrs.add(self._threshold_common(threshold_bp, scaled if scaled is not None else scaled_of_max_hash(mx) if mx else 1))
+        if len(thrs) > 1:   # (queries the call accepts share their max_hash)
+            raise ValueError("search_many: the queries differ in max_hash; give scaled, or downsample=True")
+        arr = (C.c_void_p * max(nqs, 1))(*[q._p for q in queries])
+        return self._search_result(nqs, self._L.smh_index_search_many, self._h, arr, nqs, SEARCH_METRICS[metric], float(threshold),
+                                   thrs.pop() if thrs else 0)
+
+    def search_block_dev(self, hashes_dev, offsets, threshold, metric="jaccard", threshold_common=0, stream=None):
+        """search_many of a CSR in device memory (smh_index_search_block_dev): query q is the hashes [offsets[q], offsets[q + 1])
+        behind the device pointer hashes_dev, ascending strictly; offsets on the host.  A CSR has no `scaled`: the threshold on
+        the common hashes is given as a count."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nqs = len(offsets) - 1
+        return self._search_result(nqs, lambda *a: self._L.smh_index_search_block_dev(*a, C.c_void_p(stream or 0)), self._h,
+                                   C.c_void_p(hashes_dev), offsets.ctypes.data_as(u64p), nqs, SEARCH_METRICS[metric], float(threshold),
+                                   int(threshold_common))
+
+    def pairwise(self, threshold, metric="jaccard", threshold_bp=0, upper=True):
+        """The index against itself (smh_index_search_self): the SearchResult of search_many of the index's own sketches
+        without the rows node == query -- and, with upper=True, without the rows node < query.  The queries are read where
+        they lie in HBM, so this works on an index downsample() returned (whose `nodes` are the uncut sketches): the node
+        positions and the sizes are those of that index.  scaled is what the index's max_hash stands for."""
+        lo, _ = self.max_hash_range
+        thr = self._threshold_common(threshold_bp, scaled_of_max_hash(lo)) if lo else 0
+        fn = self._L.smh_index_search_self
+        return self._search_result(len(self), lambda h, m, t, c, *out: fn(h, m, t, c, bool(upper), *out), self._h, SEARCH_METRICS[metric],
+                                   float(threshold), thr)
 
     def match(self, records, hits=False, stream=None):
         """Every record of a batch against the index (smh_index_match_*; the rules: include/sourmash_amd.h, "Matching

@@ -194,6 +194,24 @@ def set_gather_many_budget(pairs):
     lib().smh_gather_many_set_budget(int(pairs))
 
 
+def search_geometry():
+    """(owners of a hash the lane holding a query position walks itself, nodes of one workgroup of the select and emit
+    kernels, most queries of a chunk) of ResidentIndex.search_many"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().smh_search_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def search_many_budget():
+    return int(lib().smh_search_many_budget())
+
+
+def set_search_many_budget(pairs):
+    """the (query, node) counters one chunk of ResidentIndex.search_many / pairwise may hold (smh_search_many_set_budget);
+    0 restores the default"""
+    lib().smh_search_many_set_budget(int(pairs))
+
+
 def angular_last_stats():
     """(pairs walked, pairs given zeros without a walk) of the last angular call"""
     a, b = C.c_uint64(), C.c_uint64()
