@@ -399,6 +399,59 @@ void smh_search_many_set_budget(uint64_t pairs);
 uint64_t smh_search_many_budget(void);
 void smh_search_geometry(uint32_t *short_owners, uint32_t *node_tile, uint32_t *max_queries);
 
+/* Clustering a resident index: the pairs of smh_index_search_self stay on the device and come back as clusters, 8 bytes per
+ * node.  The reference crate has no clustering, so the rules are fixed here; restated in
+ * tests/cluster_restatement.py.
+ *   Inputs     the n resident sketches, all scaled (num == 0); a metric, threshold (double), threshold_common (0 is read as 1),
+ *              a linkage, and scores (n entries; NULL: score[v] = |S_v|).
+ *   Adjacency  u ~ v (u != v) iff the pair survives smh_index_search_self's rule -- the kernels call the same device function:
+ *              common >= max(1, threshold_common) AND one IEEE binary64 division > threshold, strictly.  Only the symmetric
+ *              metrics are taken, SMH_SEARCH_JACCARD and SMH_SEARCH_MAX_CONTAINMENT; the two directed containments are
+ *              refused (MSG): either direction exceeding a threshold is what max-containment says.
+ *   Priority   v comes before u iff score[v] > score[u], or the scores are equal and v < u.
+ *   SMH_CLUSTER_COMPONENTS  single linkage: the clusters are the connected components of ~; a cluster's representative is its
+ *              member first in priority.
+ *   SMH_CLUSTER_GREEDY      walk the nodes in priority order: v becomes a representative iff no earlier representative is
+ *              adjacent to it.  When the representatives are final, every other node joins the adjacent representative with
+ *              the greatest value (the rule's own double); ties go to the representative earlier in priority -- which may come
+ *              later than v in priority.  It does not chain.
+ *   Outputs    the caller's arrays of n entries: cluster[v] (clusters are numbered 0, 1, ... in ascending order of their
+ *              smallest member node), representative[v] (a node), rep_common[v] (nullable; GREEDY only: |S_v ^ S_rep| for a
+ *              member, |S_v| for a representative), and *n_clusters.  Every output is an integer, so parity is equality; none
+ *              depends on chunking, on any budget, on smh_cluster_rounds or on the order of atomics.  A node adjacent to
+ *              nothing (an empty sketch included) is its own cluster; n == 0 gives *n_clusters = 0.
+ *   Errors     decided before the device is touched, and nothing is written.  cluster, representative or n_clusters NULL: a
+ *              panic, as every NULL argument.  A NaN threshold, an unknown or directed metric, an unknown linkage, rep_common
+ *              with COMPONENTS: MSG.  A num sketch in the index: MSG.  Nodes that refuse each other and an index of 2^31 or
+ *              more hashes: as smh_index_search_self.
+ *   Budgets    The (query, node) counters are cut into chunks as smh_index_search_self's, under smh_search_many_set_budget.
+ *              GREEDY keeps the directed adjacency in device memory (8 bytes per entry; 16 while a chunk is collected): when
+ *              the entries exceed smh_cluster_pair_budget() the call fails with MSG -- the message names the count reached
+ *              and the budget -- as soon as a chunk's running total passes it, and nothing is written.  COMPONENTS holds
+ *              nothing proportional to the pairs.
+ * smh_cluster_set_pair_budget  0 restores the default of 2^27 directed entries -- a memory cap, not a measured optimum.
+ * smh_cluster_set_rounds       the greedy rounds queued between two 8-byte read-backs of the undecided count; 0 restores the
+ *                              default of 32 (smh_gather_rounds_per_sync's choice).  Results never depend on it.
+ * smh_cluster_geometry         lane_max: the adjacency-list length up to which one lane walks a node's list in a greedy round
+ *                              and in the assignment (longer lists: its wave); node_tile: the nodes of one workgroup of the
+ *                              linking pass (tests, tools).
+ * smh_index_sizes              sizes[v] = |S_v| of every node as the index holds it (n entries; host only, no device work):
+ *                              what turns rep_common into the metric's value on the caller's side.
+ * Works on an index smh_index_downsample returned: its nodes are the cut ones. */
+enum {
+  SMH_CLUSTER_COMPONENTS = 0,
+  SMH_CLUSTER_GREEDY = 1
+};
+int smh_index_cluster(SmhIndex *index, uint32_t metric, double threshold, uint32_t threshold_common, uint32_t linkage,
+                      const uint32_t *scores, uint32_t *cluster, uint32_t *representative, uint32_t *rep_common,
+                      uint32_t *n_clusters);
+void smh_cluster_set_pair_budget(uint64_t entries);
+uint64_t smh_cluster_pair_budget(void);
+void smh_cluster_set_rounds(uint32_t rounds);
+uint32_t smh_cluster_rounds(void);
+void smh_cluster_geometry(uint32_t *lane_max, uint32_t *node_tile);
+int smh_index_sizes(const SmhIndex *index, uint32_t *sizes);
+
 /* Angular similarity on abundances: what `sourmash compare` and `sourmash search` report by default for sketches that
  * track abundances.  The reference crate has no weighted compare, so the rules are fixed here -- DESIGN.md 3.10, restated
  * in tests/angular_restatement.py.  For two sketches A and B that both track abundances, hashes ascending and distinct, one
@@ -780,8 +833,11 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * "gather_many_probe" (a chunk's probe, counts and sizing), "gather_many_fill" (the scan and the hit lists),
  * "gather_many_rounds" (one entry per batch of smh_gather_rounds_per_sync() rounds of a chunk), "search_many_probe" (a
  * chunk's probe), "search_many_select" (the rule on every counter, the counts per tile and their scan), "search_many_emit" (the
- * rows of a chunk).  Event counters under the same call: "gather_many_chunk", "search_many_chunk" (chunks run),
- * "match_directory_built". */
+ * rows of a chunk), "cluster_probe" (a chunk's upper-triangle probe), "cluster_link" (the rule on every counter above the
+ * diagonal, a union per survivor), "cluster_finish" (labels, representatives and the numbering), "cluster_round" (one entry
+ * per greedy round), "cluster_assign" (the members' choice).  Event counters under the same call: "gather_many_chunk",
+ * "search_many_chunk", "cluster_chunk" (chunks run), "cluster_round" (greedy rounds launched; with the timers enabled their
+ * entries are that count), "match_directory_built". */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -183,6 +183,13 @@ _SIGS = {
     "smh_search_many_set_budget": (None, [C.c_uint64]),
     "smh_search_many_budget": (C.c_uint64, []),
     "smh_search_geometry": (None, [u32p, u32p, u32p]),
+    "smh_index_cluster": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p]),
+    "smh_cluster_set_pair_budget": (None, [C.c_uint64]),
+    "smh_cluster_pair_budget": (C.c_uint64, []),
+    "smh_cluster_set_rounds": (None, [C.c_uint32]),
+    "smh_cluster_rounds": (C.c_uint32, []),
+    "smh_cluster_geometry": (None, [u32p, u32p]),
+    "smh_index_sizes": (C.c_int, [C.c_void_p, u32p]),
     "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
     "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
     "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),

@@ -32,6 +32,7 @@
 #include "compare_pair.hpp"
 #include "device.hpp"
 #include "kernels.hpp"
+#include "union_find.hpp"
 
 namespace smh {
 namespace {
@@ -1870,26 +1871,6 @@ __global__ __launch_bounds__(256) void k_reassemble(const uint64_t* __restrict__
 // visited component by component and only tiles that hold same-component pairs are launched
 // (the rest of the matrix is filled by k_fill_disjoint).  All-vs-all over unrelated genomes is
 // mostly such pairs; a collection that is one big component costs what it did before.
-__device__ __forceinline__ uint32_t uf_load(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // past the per-CU cache
-}
-__device__ __forceinline__ uint32_t uf_find(uint32_t* parent, uint32_t x) {
-  uint32_t p = uf_load(parent + x);
-  while (p != x) {
-    const uint32_t gp = uf_load(parent + p);
-    if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // halving: gp is an ancestor
-    x = p; p = gp;
-  }
-  return x;
-}
-__device__ __forceinline__ void uf_union(uint32_t* parent, uint32_t x, uint32_t y) {
-  while (true) {
-    x = uf_find(parent, x); y = uf_find(parent, y);
-    if (x == y) return;
-    if (x > y) { const uint32_t t = x; x = y; y = t; }
-    if (atomicCAS(parent + y, y, x) == y) return;   // the larger root goes under the smaller: parent[v] <= v always
-  }
-}
 __global__ __launch_bounds__(256) void k_uf_init(uint32_t* parent, uint32_t m) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < m) parent[i] = i;

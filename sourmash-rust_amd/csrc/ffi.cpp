@@ -838,6 +838,33 @@ void smh_search_geometry(uint32_t* short_owners, uint32_t* node_tile, uint32_t* 
   smh::search_geometry(short_owners, node_tile, max_queries);
 }
 
+static_assert(SMH_CLUSTER_COMPONENTS == smh::kClusterComponents && SMH_CLUSTER_GREEDY == smh::kClusterGreedy, "the linkages of the header are the kernels'");
+
+int smh_index_cluster(SmhIndex* index, uint32_t metric, double threshold, uint32_t threshold_common, uint32_t linkage, const uint32_t* scores,
+                      uint32_t* cluster, uint32_t* representative, uint32_t* rep_common, uint32_t* n_clusters) {
+  return pad_code([&] {
+    // refused before the index or the device is looked at: these need neither
+    require(cluster, "cluster"); require(representative, "representative"); require(n_clusters, "n_clusters");
+    smh::check_cluster(metric, threshold, linkage, rep_common != nullptr);
+    auto& dev = smh::Device::get();
+    require(index, "index");
+    index->cluster(metric, threshold, threshold_common, linkage, scores, cluster, representative, rep_common, n_clusters, dev);
+  });
+}
+
+void smh_cluster_set_pair_budget(uint64_t entries) { smh::g_cluster_pair_budget = entries ? entries : smh::kClusterPairBudget; }
+uint64_t smh_cluster_pair_budget(void) { return smh::g_cluster_pair_budget; }
+void smh_cluster_set_rounds(uint32_t rounds) { smh::g_cluster_rounds = rounds ? rounds : smh::kClusterRoundsPerSync; }
+uint32_t smh_cluster_rounds(void) { return smh::g_cluster_rounds; }
+void smh_cluster_geometry(uint32_t* lane_max, uint32_t* node_tile) { smh::cluster_geometry(lane_max, node_tile); }
+int smh_index_sizes(const SmhIndex* index, uint32_t* sizes) {
+  return pad_code([&] {
+    require(index, "index");
+    if (index->n) require(sizes, "sizes");
+    for (uint32_t v = 0; v < index->n; v++) sizes[v] = (uint32_t)(index->h_offsets[v + 1] - index->h_offsets[v]);
+  });
+}
+
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {
   return pad_code([&] { require(rows, "rows"); require(cols, "cols"); rows->compare(*cols, jaccard, common, size, count_common, containment); });

@@ -1,6 +1,6 @@
 // index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
 // similarity on abundances (angular.cpp), matching records (match.cpp), taxonomic LCA (lca.cpp), the thresholded search of a
-// batch (search_many.cpp).  The C boundary (ffi.cpp) only checks pointers and
+// batch (search_many.cpp), clustering (cluster.cpp).  The C boundary (ffi.cpp) only checks pointers and
 // calls in here.
 #pragma once
 #include <functional>
@@ -115,6 +115,11 @@ struct ResidentIndex {
                              uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s);
   // the index against itself: the queries are read from the resident CSR in place
   SearchRow* search_self(uint32_t metric, double threshold, uint32_t threshold_common, bool upper_only, uint64_t* row_offsets, Device& dev);
+  // (cluster.cpp) The clusters of the index under a symmetric metric (the rules: include/sourmash_amd.h, smh_index_cluster).
+  // linkage: ClusterLinkage; scores (nullable, n entries): the priority, |S_v| when null.  cluster_out, representative (n
+  // entries each), rep_common (nullable, n entries; greedy only) and *n_clusters are written only when the call succeeds.
+  void cluster(uint32_t metric, double threshold, uint32_t threshold_common, uint32_t linkage, const uint32_t* scores, uint32_t* cluster_out,
+               uint32_t* representative, uint32_t* rep_common, uint32_t* n_clusters, Device& dev);
   // (lca.cpp) Taxonomic LCA (the rules: include/sourmash_amd.h, "Taxonomic LCA").  The taxonomy is kept on the host
   // (tax_parent empty: none); the first device call uploads it and computes hash_taxon, one taxon per rank of the directory,
   // kept beside it in lca_dev (counter lca_table_built) and dropped with it, and by set_taxonomy.
@@ -201,6 +206,14 @@ constexpr uint64_t kSearchManyBudget = 1ull << 26;
 extern uint64_t g_search_many_budget;
 uint32_t search_many_chunk_end(const uint64_t* q_offsets, uint32_t a, uint32_t n_queries, uint32_t n_nodes, uint64_t budget);
 void check_search(uint32_t metric, double threshold);
+
+// cluster.cpp: the directed adjacency entries the greedy linkage may hold in device memory (8 bytes each, 16 while a chunk's
+// rows are collected) -- a memory cap, not a measured optimum; the greedy rounds queued between two read-backs of the undecided
+// count; check_cluster: the refusals of the arguments alone (kMsg), needs no device.
+constexpr uint64_t kClusterPairBudget = 1ull << 27;
+extern uint64_t g_cluster_pair_budget;
+extern uint32_t g_cluster_rounds;
+void check_cluster(uint32_t metric, double threshold, uint32_t linkage, bool want_rep_common);
 
 // downsample.cpp (the rules are in include/sourmash_amd.h, "Downsampling").  `out` is a fresh sketch: it
 // receives src's parameters with max_hash / num replaced and the kept prefix.  A state that lives in HBM is cut there into a

@@ -1,6 +1,6 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
-// gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip).
+// gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -487,6 +487,40 @@ void launch_search_many_select(const SearchChunk& ck, Device& dev, hipStream_t s
 // the chunk's rows in order (query, then node), and query_rows[q] = where the rows of query q start.  Profile name
 // search_many_emit.
 void launch_search_many_emit(const SearchChunk& ck, SearchRow* rows, uint32_t* query_rows, Device& dev, hipStream_t s);
+
+// --- cluster_kernels.hip ---------------------------------------------------------------
+// Clustering a resident index (the rules are in include/sourmash_amd.h, smh_index_cluster).  Components: the
+// upper triangle of a chunk's counters is probed and every survivor of the rule is a union; greedy: the rows of the search
+// kernels stay in HBM as adjacency lists and synchronous rounds decide the representatives.
+enum ClusterLinkage : uint32_t { kClusterComponents = 0, kClusterGreedy = 1 };
+enum ClusterState : uint32_t { kClusterUndecided = 0, kClusterRep = 1, kClusterMember = 2 };
+constexpr uint32_t kClusterLaneMax = 16;         // adjacency lists up to this length are walked by the lane that holds the node
+constexpr uint32_t kClusterRoundsPerSync = 32;   // greedy rounds queued between two read-backs (kGatherRoundsPerSync's choice)
+struct ClusterAdj { uint32_t node, common; };    // one directed adjacency entry: the neighbour and |S_v ^ S_node|
+void cluster_geometry(uint32_t* lane_max, uint32_t* node_tile);
+// v[i] = i
+void launch_cluster_iota(uint32_t* v, uint32_t n, hipStream_t s);
+// the chunk's counters of the pairs with owner > query only (ck.q0 = the node that the chunk's first query is; c zeroed by the
+// caller).  Profile name cluster_probe.
+void launch_cluster_probe(const MatchDirectory& d, const SearchChunk& ck, Device& dev, hipStream_t s);
+// uf_union(parent, query, node) for every survivor of the rule under kSearchUpperOnly.  Profile name cluster_link.
+void launch_cluster_link(const SearchChunk& ck, uint32_t* parent, Device& dev, hipStream_t s);
+// Components, finishing pass.  scores (nullable: |S_v| from node_offsets); work: room for 4 n + 2 u32 (8-byte aligned);
+// out: cluster[n], representative[n], then the number of clusters.  Profile name cluster_finish.
+void launch_cluster_finish_components(uint32_t* parent, const uint32_t* scores, const uint64_t* node_offsets, uint32_t n, uint32_t* work,
+                                      uint32_t* out, Device& dev, hipStream_t s);
+// adj[base + k] = {rows[k].node, rows[k].common} for the R rows of a chunk, and start[q] = base + query_rows[q] for its nq
+// queries (query_rows null: the chunk has no rows, start[q] = base)
+void launch_cluster_pack(const SearchRow* rows, uint32_t R, const uint32_t* query_rows, uint32_t nq, uint32_t base, ClusterAdj* adj,
+                         uint32_t* start, hipStream_t s);
+// One synchronous round: st_out from st_in (ClusterState per node), start: n + 1 entries.  undecided (nullable): += the nodes
+// still undecided in st_out.
+void launch_cluster_round(const uint32_t* start, const ClusterAdj* adj, const uint32_t* rank, const uint32_t* st_in, uint32_t* st_out,
+                          uint32_t n, unsigned long long* undecided, Device& dev, hipStream_t s);
+// Greedy, members and numbering.  work: room for 2 n + 1 u32; out: cluster[n], representative[n], rep_common[n], then the
+// number of clusters.  Profile names cluster_assign, cluster_finish.
+void launch_cluster_assign(const uint32_t* start, const ClusterAdj* adj, const uint32_t* rank, const uint32_t* st, uint32_t metric,
+                           const uint64_t* node_offsets, uint32_t n, uint32_t* work, uint32_t* out, Device& dev, hipStream_t s);
 
 // --- lca_kernels.hip -------------------------------------------------------------------
 // Taxonomic LCA on a resident index (the rules are in include/sourmash_amd.h, "Taxonomic LCA").

@@ -7,6 +7,8 @@
   ResidentIndex.gather_many the same decomposition for a batch of queries in one device call (smh_index_gather_many)
   ResidentIndex.search_many the (query, node) pairs of a batch of queries over a threshold, as a sparse list (no counterpart
                             either: include/sourmash_amd.h, smh_index_search_many); pairwise is the index against itself
+  ResidentIndex.cluster     the clusters of the index's own nodes under such a threshold, made on the device (no counterpart:
+                            include/sourmash_amd.h, smh_index_cluster): connected components or greedy representatives
   ResidentIndex.match       the k-mers of every record of a batch the index knows, and each record's best node (no counterpart
                             either: include/sourmash_amd.h, "Matching records")
 
@@ -84,6 +86,37 @@ class SearchResult:
         if self.molecule != "DNA" or not self.ksize:
             raise ValueError("ani is defined for DNA sketches only (this result: %s)" % (self.molecule or "an index without nodes"))
         return getattr(self, column) ** (1.0 / self.ksize)
+
+
+# the linkages of cluster (SMH_CLUSTER_* of include/sourmash_amd.h)
+CLUSTER_LINKAGES = {"components": 0, "greedy": 1}
+
+
+class Clustering:
+    """What cluster reports.  cluster (uint32, a node each): the node's cluster, clusters numbered in ascending order of their
+    smallest member; representative (uint32): the node that represents it; n_clusters; for the greedy linkage rep_common
+    (uint32: the hashes a member shares with its representative, a representative's own size) and rep_value (float64: the
+    metric's value of (node, representative), derived here from the integers with one division, as SearchResult derives its
+    floats; 1.0 for a representative that holds a hash, NaN for an empty one) -- both None for components."""
+
+    def __init__(self, cluster, representative, n_clusters, rep_common=None, sizes=None, metric=None):
+        self.cluster, self.representative, self.n_clusters, self.rep_common = cluster, representative, int(n_clusters), rep_common
+        self.rep_value = None
+        if rep_common is not None:
+            c, lv, lr = (a.astype(np.float64) for a in (rep_common, sizes, sizes[representative]))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                self.rep_value = c / (lv + lr - c) if metric == "jaccard" else c / np.minimum(lv, lr)
+
+    def __len__(self):
+        return len(self.cluster)
+
+    def sizes(self):
+        """the nodes of every cluster (int64, n_clusters entries)"""
+        return np.bincount(self.cluster, minlength=self.n_clusters)
+
+    def members(self, c):
+        """the nodes of cluster c, ascending"""
+        return np.flatnonzero(self.cluster == c)
 
 
 def scaled_of_max_hash(max_hash):
@@ -457,6 +490,49 @@ class ResidentIndex:
         fn = self._L.smh_index_search_self
         return self._search_result(len(self), lambda h, m, t, c, *out: fn(h, m, t, c, bool(upper), *out), self._h, SEARCH_METRICS[metric],
                                    float(threshold), thr)
+
+    # --- clustering (additive ABI smh_index_cluster; the rules: include/sourmash_amd.h, smh_index_cluster)
+    def cluster(self, threshold, metric="jaccard", linkage="components", scores=None, threshold_bp=0, scaled=None, ani=False):
+        """The clusters of the index's nodes, made on the device (smh_index_cluster): a Clustering.  Two nodes are adjacent iff
+        pairwise(threshold, metric, threshold_bp) reports the pair; metric: "jaccard" or "max_containment".  linkage
+        "components": single linkage, the connected components; "greedy": the best-scored node first, everything adjacent to a
+        representative joins the closest one, and nothing chains.  scores (n integers below 2^32; default: the sketch sizes)
+        rank the nodes, ties go to the lower node.  ani=True reads `threshold` as an average nucleotide identity and clusters
+        at max_containment > threshold ** ksize: DNA sketches and metric="max_containment" only.  scaled defaults to what the
+        index's max_hash stands for.  Works on an index downsample() returned: the nodes are the cut ones."""
+        if ani:
+            first = self.nodes[0] if self.nodes else None
+            if metric != "max_containment":
+                raise ValueError("ani=True takes metric='max_containment', not %r" % (metric,))
+            if first is None or first.molecule != "DNA" or not first.ksize:
+                raise ValueError("ani is defined for DNA sketches only (this index: %s)" % (first.molecule if first else "no nodes"))
+            threshold = float(threshold) ** first.ksize
+        if metric not in ("jaccard", "max_containment"):
+            raise ValueError("cluster takes the symmetric metrics 'jaccard' and 'max_containment', not %r" % (metric,))
+        n = len(self)
+        lo, _ = self.max_hash_range
+        thr = self._threshold_common(threshold_bp, scaled if scaled is not None else scaled_of_max_hash(lo)) if lo else 0
+        greedy = CLUSTER_LINKAGES[linkage] == 1
+        sc = None
+        if scores is not None:
+            sc = np.ascontiguousarray(scores, dtype=np.uint32)
+            if sc.shape != (n,):
+                raise ValueError("scores: one per node")
+        cl, rep = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)   # (never a NULL pointer)
+        common = np.zeros(max(n, 1), dtype=np.uint32) if greedy else None
+        k = C.c_uint32()
+        call(self._L.smh_index_cluster, self._h, SEARCH_METRICS[metric], float(threshold), thr, CLUSTER_LINKAGES[linkage],
+             sc.ctypes.data_as(u32p) if sc is not None else None, cl.ctypes.data_as(u32p), rep.ctypes.data_as(u32p),
+             common.ctypes.data_as(u32p) if greedy else None, C.byref(k))
+        return Clustering(cl[:n], rep[:n], k.value, common[:n] if greedy else None, self.sizes() if greedy else None, metric)
+
+    def sizes(self):
+        """|S_v| of every node as the index holds it (uint32; smh_index_sizes): for an index downsample() returned, the sizes of
+        the cut sketches"""
+        n = len(self)
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        call(self._L.smh_index_sizes, self._h, out.ctypes.data_as(u32p))
+        return out[:n]
 
     def match(self, records, hits=False, stream=None):
         """Every record of a batch against the index (smh_index_match_*; the rules: include/sourmash_amd.h, "Matching

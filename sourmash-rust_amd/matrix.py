@@ -212,6 +212,33 @@ def set_search_many_budget(pairs):
     lib().smh_search_many_set_budget(int(pairs))
 
 
+def cluster_geometry():
+    """(adjacency-list length up to which one lane walks a node's list in a greedy round, nodes of one workgroup of the linking
+    pass) of ResidentIndex.cluster"""
+    a, b = C.c_uint32(), C.c_uint32()
+    lib().smh_cluster_geometry(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def cluster_pair_budget():
+    return int(lib().smh_cluster_pair_budget())
+
+
+def set_cluster_pair_budget(entries):
+    """the directed adjacency entries the greedy linkage of ResidentIndex.cluster may hold (smh_cluster_set_pair_budget);
+    0 restores the default"""
+    lib().smh_cluster_set_pair_budget(int(entries))
+
+
+def cluster_rounds():
+    return int(lib().smh_cluster_rounds())
+
+
+def set_cluster_rounds(rounds):
+    """the greedy rounds ResidentIndex.cluster queues between two read-backs (smh_cluster_set_rounds); 0 restores the default"""
+    lib().smh_cluster_set_rounds(int(rounds))
+
+
 def angular_last_stats():
     """(pairs walked, pairs given zeros without a walk) of the last angular call"""
     a, b = C.c_uint64(), C.c_uint64()
