@@ -452,6 +452,66 @@ uint32_t smh_cluster_rounds(void);
 void smh_cluster_geometry(uint32_t *lane_max, uint32_t *node_tile);
 int smh_index_sizes(const SmhIndex *index, uint32_t *sizes);
 
+/* Collapsing an index by groups: one sketch per group of nodes -- the union (`sig merge`), the core (`sig intersect`), the
+ * hashes at least x % of the members hold, or the hash -> number-of-members table -- made on the device from the index's
+ * hash directory, as a new resident index.  The reference crate has no counterpart, so the rules are fixed
+ * here; restated in tests/collapse_restatement.py.
+ *   Inputs     an index of n nodes; n_groups = G; group[v] for every node, each < G or SMH_COLLAPSE_DROP (the node takes no
+ *              part); min_count; min_fraction (double); an abundance mode.
+ *   m_g        the number of nodes with group[v] == g.
+ *   c_g(h)     the number of those nodes that hold hash h;  a_g(h): the exact unsigned 64-bit sum of their abundances of h.
+ *   need_g     max(1, min_count, ceil(min_fraction * m_g)).  The product and the ceiling are taken in IEEE binary64 on the
+ *              host (Python: math.ceil(min_fraction * m)); the device sees the G integers only.
+ *   Result     an index of G sketches; sketch g = { h : c_g(h) >= need_g }, ascending as unsigned 64-bit.  min_count = 1 and
+ *              min_fraction = 0 give the union, min_fraction = 1.0 the intersection.  A group with m_g == 0 or need_g > m_g is
+ *              an empty sketch; n == 0 gives G empty sketches.
+ *   SMH_COLLAPSE_FLAT   no abundances: smh_index_has_abundances is false for the result.
+ *   SMH_COLLAPSE_SUM    the abundance of h in sketch g is a_g(h).
+ *   SMH_COLLAPSE_COUNT  the abundance of h in sketch g is c_g(h), the prevalence table; it cannot overflow.
+ *   Parameters the result's nodes take node 0's ksize, molecule, seed and max_hash, and are scaled sketches; abundances are
+ *              tracked exactly when the mode is not FLAT.  (An index without nodes has no parameters to hand down: DNA,
+ *              ksize 21, seed 42, max_hash 2^64 - 1.)  The result carries NO taxonomy -- its nodes are not the parent's -- keeps
+ *              no reference to the parent, and is an index like any other: every call here takes it, this one included.
+ *   Refused    with SOURMASH_ERROR_CODE_MSG, the message names the offending entry, NULL is returned, and nothing is built:
+ *              G == 0; min_fraction outside [0, 1] or NaN; an unknown mode (these three before the index or the device is
+ *              looked at); index NULL, or group NULL for an index with nodes; a node that is not a scaled sketch
+ *              (smh_index_all_scaled); nodes that do not agree in ksize, molecule, seed and max_hash (smh_index_downsample
+ *              brings them to one max_hash); a group[v] >= G that is not SMH_COLLAPSE_DROP; SUM on an index for which
+ *              smh_index_has_abundances is false or that holds an abundance of 2^32 or more (worded as the angular calls
+ *              word it); an index of 2^31 or more hashes (the directory's own refusal); SUM where a KEPT sum is 2^32 or
+ *              more -- the message names the lowest such group.  Only that last refusal is found on the device (one
+ *              atomicMin on an error word); the work space of the call is back in the pool when it returns.
+ *   Device     the hash directory (built by the first call that needs it and kept, counter "match_directory_built") is read
+ *              twice, by a count pass and an emit pass; the survivors -- (group, rank of the hash) pairs -- are partitioned by
+ *              group with a stable sort on the group's bytes, the groups' bounds are searched among the sorted keys, and
+ *              4 G + 8 bytes come to the host.  SUM first moves the
+ *              abundances to HBM as the first angular call does.  Work space, all from the block pool and all returned: 4 B
+ *              per distinct hash of the index, 16 B per survivor (24 B with abundances) while they are partitioned, 8 G B,
+ *              4 B per node, and the lists of the long owner lists (at most 4 B per 9 resident hashes).  There is no
+ *              chunking: a call that does not fit fails with the pool's own error.  Inside one hash the survivors are
+ *              written in no fixed order -- a group appears once per hash, so the partition yields the same bytes.
+ * smh_collapse_geometry  lane_max: the owner-list length up to which one lane folds a hash's owners; wave_max: up to which
+ *                        one wave does, the owners' groups in its LDS scratch; group_tile: the groups one round of LDS
+ *                        counters covers for a longer list (tests, tools).
+ * smh_index_read         the index as it is held: offsets (n + 1 entries, from 0), hashes and abunds (offsets[n] entries
+ *                        each; the caller sizes them from smh_index_sizes).  Each of the three may be NULL.  The hashes
+ *                        come from the device CSR, the abundances from the host copy or from HBM, wherever they live.
+ *                        abunds asked of an index for which smh_index_has_abundances is false, or that holds an abundance
+ *                        of 2^32 or more: MSG, nothing written.  Works on every index: built from sketches, downsampled,
+ *                        collapsed.
+ * Timers under smh_profile_get: "collapse_count", "collapse_emit", "collapse_partition", "collapse_finish"; event counter:
+ * "index_collapsed". */
+enum {
+  SMH_COLLAPSE_FLAT = 0,
+  SMH_COLLAPSE_SUM = 1,
+  SMH_COLLAPSE_COUNT = 2
+};
+#define SMH_COLLAPSE_DROP 0xffffffffu
+SmhIndex *smh_index_collapse(SmhIndex *index, const uint32_t *group, uint32_t n_groups, uint32_t min_count, double min_fraction,
+                             uint32_t abund);
+void smh_collapse_geometry(uint32_t *lane_max, uint32_t *wave_max, uint32_t *group_tile);
+int smh_index_read(SmhIndex *index, uint64_t *offsets, uint64_t *hashes, uint32_t *abunds);
+
 /* Angular similarity on abundances: what `sourmash compare` and `sourmash search` report by default for sketches that
  * track abundances.  The reference crate has no weighted compare, so the rules are fixed here -- DESIGN.md 3.10, restated
  * in tests/angular_restatement.py.  For two sketches A and B that both track abundances, hashes ascending and distinct, one
@@ -835,9 +895,11 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * chunk's probe), "search_many_select" (the rule on every counter, the counts per tile and their scan), "search_many_emit" (the
  * rows of a chunk), "cluster_probe" (a chunk's upper-triangle probe), "cluster_link" (the rule on every counter above the
  * diagonal, a union per survivor), "cluster_finish" (labels, representatives and the numbering), "cluster_round" (one entry
- * per greedy round), "cluster_assign" (the members' choice).  Event counters under the same call: "gather_many_chunk",
+ * per greedy round), "cluster_assign" (the members' choice), "collapse_count" / "collapse_emit" (the two folds of the
+ * directory's owner lists through the groups, three launches each), "collapse_partition" (the survivors sorted by group and
+ * the groups' bounds among them), "collapse_finish" (the child's hashes and abundances from the partitioned survivors).  Event counters under the same call: "gather_many_chunk",
  * "search_many_chunk", "cluster_chunk" (chunks run), "cluster_round" (greedy rounds launched; with the timers enabled their
- * entries are that count), "match_directory_built". */
+ * entries are that count), "match_directory_built", "index_collapsed". */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

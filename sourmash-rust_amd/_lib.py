@@ -190,6 +190,9 @@ _SIGS = {
     "smh_cluster_rounds": (C.c_uint32, []),
     "smh_cluster_geometry": (None, [u32p, u32p]),
     "smh_index_sizes": (C.c_int, [C.c_void_p, u32p]),
+    "smh_index_collapse": (C.c_void_p, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32]),
+    "smh_collapse_geometry": (None, [u32p, u32p, u32p]),
+    "smh_index_read": (C.c_int, [C.c_void_p, u64p, u64p, u32p]),
     "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
     "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
     "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),

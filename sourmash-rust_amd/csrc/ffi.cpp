@@ -865,6 +865,29 @@ int smh_index_sizes(const SmhIndex* index, uint32_t* sizes) {
   });
 }
 
+// ------------------------------------------------------------------ collapsing by groups, the read-back (collapse.cpp)
+
+SmhIndex* smh_index_collapse(SmhIndex* index, const uint32_t* group, uint32_t n_groups, uint32_t min_count, double min_fraction,
+                             uint32_t abund) {
+  return pad<SmhIndex*>([&] {
+    // refused before the index or the device is looked at: these need neither
+    smh::check_collapse(n_groups, min_fraction, abund);
+    (void)smh::Device::get();
+    if (!index) throw Error(smh::kMsg, "collapse: index is NULL");   // (MSG like every refusal of this call; group: in the constructor)
+    return new SmhIndex(*index, group, n_groups, min_count, min_fraction, abund);
+  });
+}
+void smh_collapse_geometry(uint32_t* lane_max, uint32_t* wave_max, uint32_t* group_tile) {
+  smh::collapse_geometry(lane_max, wave_max, group_tile);
+}
+int smh_index_read(SmhIndex* index, uint64_t* offsets, uint64_t* hashes, uint32_t* abunds) {
+  return pad_code([&] {
+    (void)smh::Device::get();
+    require(index, "index");
+    index->read(offsets, hashes, abunds);
+  });
+}
+
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {
   return pad_code([&] { require(rows, "rows"); require(cols, "cols"); rows->compare(*cols, jaccard, common, size, count_common, containment); });

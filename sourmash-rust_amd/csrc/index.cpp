@@ -48,7 +48,11 @@ ResidentIndex::ResidentIndex(const std::vector<const KmerMinHash*>& v) {
     if (n) HIP_CHECK(hipMemcpyAsync(nums.ptr, h_nums.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamSynchronize(s));
   }
-  std::lock_guard<std::mutex> g(registry_mu());   // last: nothing above may leave a half-built index registered
+  enroll();   // last: nothing above may leave a half-built index registered
+}
+
+void ResidentIndex::enroll() {
+  std::lock_guard<std::mutex> g(registry_mu());
   registry().insert(this);
 }
 
@@ -107,8 +111,7 @@ ResidentIndex::ResidentIndex(ResidentIndex& parent, uint64_t mx) {
     HIP_CHECK(hipStreamSynchronize(s));
     dev.count("index_downsampled");
   }
-  std::lock_guard<std::mutex> g(registry_mu());
-  registry().insert(this);
+  enroll();
 }
 
 void ResidentIndex::max_hash_range(uint64_t* lo, uint64_t* hi) const {

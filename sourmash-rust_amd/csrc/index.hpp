@@ -1,7 +1,7 @@
 // index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
 // similarity on abundances (angular.cpp), matching records (match.cpp), taxonomic LCA (lca.cpp), the thresholded search of a
-// batch (search_many.cpp), clustering (cluster.cpp).  The C boundary (ffi.cpp) only checks pointers and
-// calls in here.
+// batch (search_many.cpp), clustering (cluster.cpp), collapsing by groups and the read-back (collapse.cpp).  The C boundary
+// (ffi.cpp) only checks pointers and calls in here.
 #pragma once
 #include <functional>
 
@@ -42,7 +42,16 @@ struct ResidentIndex {
   // the parent's nodes cut at max_hash, built from the parent's device arrays: nothing comes to the host
   // but the kept lengths.  Refused (kMsg) unless every node is a scaled sketch and 0 < max_hash <= every node's max_hash.
   ResidentIndex(ResidentIndex& parent, uint64_t max_hash);
+  // (collapse.cpp) the parent collapsed by groups (the rules: include/sourmash_amd.h, "Collapsing an index by groups"): node g
+  // of the new index is the hashes that at least need_g members of group g hold, made from the parent's hash directory.
+  // group: parent.n entries (nullable when the parent is empty), each below n_groups or kCollapseDrop; abund: CollapseAbund.
+  // Every refusal is kMsg and comes before anything is built; the child carries no taxonomy (its nodes are not the parent's).
+  ResidentIndex(ResidentIndex& parent, const uint32_t* group, uint32_t n_groups, uint32_t min_count, double min_fraction, uint32_t abund);
   ~ResidentIndex();
+  void enroll();   // into the registry of live indexes: the last step of every constructor
+  // (collapse.cpp) the index as it is held: offsets (n + 1, from 0), hashes and abundances (offsets[n] each); any may be null.
+  // Abundances come from the host copy or from HBM, wherever they live; asked of an index without them: kMsg.
+  void read(uint64_t* offsets_out, uint64_t* hashes_out, uint32_t* abunds_out);
   void max_hash_range(uint64_t* lo, uint64_t* hi) const;   // over the nodes; 0, 0 when empty
   SketchSet set() const { return {hashes.as<uint64_t>(), offsets.as<uint64_t>(), n, h_offsets.data()}; }
   AngularSet angular_set() const {   // after angular_ensure
@@ -214,6 +223,11 @@ constexpr uint64_t kClusterPairBudget = 1ull << 27;
 extern uint64_t g_cluster_pair_budget;
 extern uint32_t g_cluster_rounds;
 void check_cluster(uint32_t metric, double threshold, uint32_t linkage, bool want_rep_common);
+
+// collapse.cpp: the refusals of the arguments alone (kMsg; needs no device), and need_g = max(1, min_count, ceil(min_fraction *
+// m_g)), the product and the ceiling in IEEE double
+void check_collapse(uint32_t n_groups, double min_fraction, uint32_t abund);
+uint32_t collapse_need(uint32_t members, uint32_t min_count, double min_fraction);
 
 // downsample.cpp (the rules are in include/sourmash_amd.h, "Downsampling").  `out` is a fresh sketch: it
 // receives src's parameters with max_hash / num replaced and the kept prefix.  A state that lives in HBM is cut there into a

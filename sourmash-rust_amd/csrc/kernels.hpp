@@ -1,6 +1,6 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
-// gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip).
+// gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip, collapse_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -552,5 +552,46 @@ void launch_lca_keys(const uint64_t* key, const uint32_t* at, uint32_t T, uint64
 void launch_lca_records(const LcaTaxonomy& t, const uint32_t* hash_taxon, const uint32_t* rank, const MatchRow* rows,
                         const uint32_t* rec_first, uint32_t nrec, LcaRow* out, uint32_t* big_list, uint32_t* big_count, Device& dev,
                         hipStream_t s);
+
+// --- collapse_kernels.hip --------------------------------------------------------------
+// Collapsing a resident index by groups (the rules are in include/sourmash_amd.h, "Collapsing an index by
+// groups").  The owner list of every rank of the hash directory is folded through group[] to the groups that hold the hash
+// often enough; a survivor is one (group, rank) with its count or abundance sum.
+enum CollapseAbund : uint32_t { kCollapseFlat = 0, kCollapseSum = 1, kCollapseCount = 2 };
+constexpr uint32_t kCollapseDrop = 0xffffffffu;    // SMH_COLLAPSE_DROP: a node that takes no part
+constexpr uint32_t kCollapseNoError = 0xffffffffu; // what the error word holds before the emit pass may lower it
+constexpr uint32_t kCollapseLaneMax = 8;           // owner lists up to this length are folded by the lane that holds the rank (kLcaOwnerLaneMax's choice)
+constexpr uint32_t kCollapseWaveMax = 256;         // ... up to this length by one wave, the owners' groups in its LDS scratch (1 KiB per wave)
+constexpr uint32_t kCollapseGroupTile = 2048;      // longer lists: one workgroup, LDS counters over this many groups at a time (8 KiB, 24 with sums)
+struct CollapseFold {
+  MatchDirectory d;
+  const uint32_t* group = nullptr;     // n entries: the node's group or kCollapseDrop
+  const uint32_t* need = nullptr;      // n_groups entries: need_g
+  uint32_t n_groups = 0;
+  uint32_t* cnt = nullptr;             // n_hashes + 1: survivors per rank; scanned in place between the passes (the last entry: their total)
+  uint32_t* wave_list = nullptr;       // ranks with more than kCollapseLaneMax owners: room for n_pairs / (kCollapseLaneMax + 1) + 1 ...
+  uint32_t* long_list = nullptr;       // ... and with more than kCollapseWaveMax: n_pairs / (kCollapseWaveMax + 1) + 1
+  uint32_t* list_count = nullptr;      // two words, [0] wave_list's, [1] long_list's (zeroed by the count pass)
+  // the emit pass
+  uint32_t abund = kCollapseFlat;
+  const uint64_t* hashes = nullptr;    // kCollapseSum: the index's CSR and its abundances in device memory
+  const uint64_t* offsets = nullptr;
+  const uint32_t* abunds = nullptr;
+  uint64_t* key = nullptr;             // per survivor (group << 32) | rank
+  uint32_t* val = nullptr;             // per survivor c_g(h) or a_g(h); null under kCollapseFlat
+  uint32_t* err = nullptr;             // kCollapseSum: atomicMin of the groups holding a kept sum of 2^32 or more (caller: 0xff bytes)
+};
+void collapse_geometry(uint32_t* lane_max, uint32_t* wave_max, uint32_t* group_tile);
+// cnt and the two lists.  Profile name collapse_count.
+void launch_collapse_count(const CollapseFold& f, Device& dev, hipStream_t s);
+// key / val of every survivor, those of rank r at cnt[r] .. cnt[r + 1] (cnt scanned; any order inside a rank: a group appears
+// once there).  Reads the lists the count pass left.  Profile name collapse_emit.
+void launch_collapse_emit(const CollapseFold& f, Device& dev, hipStream_t s);
+// start[g] = how many of the S partitioned keys belong to groups below g, for g = 0 .. n_groups (n_groups + 1 entries)
+void launch_collapse_bounds(const uint64_t* key, uint32_t S, uint32_t n_groups, uint32_t* start, Device& dev, hipStream_t s);
+// out_hashes[i] = U[rank of key[i]], out_abunds[i] = val[i] (both nullable together) for the S partitioned survivors.  Profile
+// name collapse_finish.
+void launch_collapse_finish(const uint64_t* U, const uint64_t* key, const uint32_t* val, uint32_t S, uint64_t* out_hashes,
+                            uint32_t* out_abunds, Device& dev, hipStream_t s);
 
 }  // namespace smh

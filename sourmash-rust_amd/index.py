@@ -9,14 +9,19 @@
                             either: include/sourmash_amd.h, smh_index_search_many); pairwise is the index against itself
   ResidentIndex.cluster     the clusters of the index's own nodes under such a threshold, made on the device (no counterpart:
                             include/sourmash_amd.h, smh_index_cluster): connected components or greedy representatives
+  ResidentIndex.collapse    one sketch per group of nodes -- union, core, prevalence -- as a new resident index made on the
+                            device (no counterpart: include/sourmash_amd.h, "Collapsing an index by groups"); read / sketches
+                            bring an index's own sketches back to the host (smh_index_read)
   ResidentIndex.match       the k-mers of every record of a batch the index knows, and each record's best node (no counterpart
                             either: include/sourmash_amd.h, "Matching records")
 
 A "node" here is a KmerMinHash (the reference's Leaf wraps a Signature whose first sketch is used,
 src/index.rs:108-161)."""
 import collections
+import collections.abc
 import ctypes as C
 import math
+import weakref
 
 import numpy as np
 
@@ -117,6 +122,29 @@ class Clustering:
     def members(self, c):
         """the nodes of cluster c, ascending"""
         return np.flatnonzero(self.cluster == c)
+
+
+# the abundance modes of collapse (SMH_COLLAPSE_* of include/sourmash_amd.h) and the group of a node that takes no part
+COLLAPSE_ABUNDS = {"flat": 0, "sum": 1, "count": 2}
+COLLAPSE_DROP = 0xFFFFFFFF
+
+
+class _OwnSketches(collections.abc.Sequence):
+    """`nodes` of an index collapse() returned: its own sketches, read back from the device when one is first asked for (the
+    length is known without that)."""
+
+    def __init__(self, index):
+        self._n = len(index)
+        self._index = weakref.ref(index)   # (the index owns this object: a strong reference would make a cycle and delay its free)
+        self._list = None
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, k):
+        if self._list is None:
+            self._list = self._index().sketches()
+        return self._list[k]
 
 
 def scaled_of_max_hash(max_hash):
@@ -533,6 +561,80 @@ class ResidentIndex:
         out = np.zeros(max(n, 1), dtype=np.uint32)
         call(self._L.smh_index_sizes, self._h, out.ctypes.data_as(u32p))
         return out[:n]
+
+    # --- collapsing by groups and the read-back (additive ABI smh_index_collapse, smh_index_read; the rules:
+    # include/sourmash_amd.h, "Collapsing an index by groups")
+    def collapse(self, groups, n_groups=None, min_count=1, min_fraction=0.0, abund="flat"):
+        """One sketch per group of nodes, made on the device (smh_index_collapse): a ResidentIndex of n_groups nodes.  Sketch g
+        holds the hashes that at least max(1, min_count, ceil(min_fraction * members)) members of group g hold: the defaults
+        give the union (`sig merge`), min_fraction=1.0 the core (`sig intersect`).  groups: one int per node, None or -1 for a
+        node that takes no part -- or a Clustering, whose clusters are the groups: idx.collapse(idx.cluster(0.9,
+        metric="max_containment")) is the pangenome sketch of every cluster.  n_groups defaults to the largest group + 1.
+        abund: a key of COLLAPSE_ABUNDS -- "flat" none, "sum" the members' abundances added up, "count" the number of members
+        that hold the hash.  The result carries no taxonomy and its `nodes` are its own sketches, read back when first asked."""
+        if isinstance(groups, Clustering):
+            if n_groups is None:
+                n_groups = groups.n_clusters
+            g = np.ascontiguousarray(groups.cluster, dtype=np.uint32)
+        else:
+            wide = np.array([-1 if x is None else int(x) for x in groups], dtype=np.int64)
+            if wide.size and (wide.min() < -1 or wide.max() >= COLLAPSE_DROP):
+                raise ValueError("groups: ints in [0, 2^32 - 1), None or -1")
+            if n_groups is None:
+                n_groups = int(wide.max()) + 1 if wide.size else 0
+            g = np.where(wide < 0, COLLAPSE_DROP, wide).astype(np.uint32)
+        if g.shape != (len(self),):
+            raise ValueError("groups: one per node")
+        if g.size == 0:
+            g = np.zeros(1, dtype=np.uint32)   # (never a NULL pointer)
+        track = COLLAPSE_ABUNDS[abund] != 0
+        child = ResidentIndex((), _handle=call(self._L.smh_index_collapse, self._h, g.ctypes.data_as(u32p), int(n_groups), int(min_count),
+                                               float(min_fraction), COLLAPSE_ABUNDS[abund]))
+        first = self.nodes[0] if len(self.nodes) else None
+        lo, _ = self.max_hash_range
+        child._template = (0, first.ksize, first.molecule, first.seed, lo, track) if first is not None else \
+            (0, 21, "DNA", 42, (1 << 64) - 1, track)
+        child.nodes = _OwnSketches(child)
+        return child
+
+    def read(self):
+        """The index as it is held (smh_index_read): (offsets, hashes, abunds) -- uint64 offsets of len(self) + 1 entries from
+        0, the uint64 hashes of node v at [offsets[v], offsets[v + 1]), and their uint32 abundances, or None for an index
+        without abundances.  For an index downsample() or collapse() returned these are the cut / collapsed sketches."""
+        n = len(self)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        call(self._L.smh_index_read, self._h, off.ctypes.data_as(u64p), None, None)
+        total = int(off[-1])
+        hashes = np.zeros(max(total, 1), dtype=np.uint64)
+        abunds = np.zeros(max(total, 1), dtype=np.uint32) if self.has_abundances else None
+        call(self._L.smh_index_read, self._h, None, hashes.ctypes.data_as(u64p), abunds.ctypes.data_as(u32p) if abunds is not None else None)
+        return off, hashes[:total], abunds[:total] if abunds is not None else None
+
+    def sketches(self):
+        """The nodes as the index holds them, a list of KmerMinHash filled through smh_index_read: a node's own num, ksize,
+        molecule and seed, the max_hash of the index (for downsample()'s result: the cut one), abundances when the index has
+        them.  For collapse()'s result the parameters are those the collapsed index took from its parent."""
+        from .minhash import KmerMinHash
+        off, hashes, abunds = self.read()
+        lo, hi = self.max_hash_range
+        template = getattr(self, "_template", None)
+        out = []
+        for v in range(len(self)):
+            if template is not None:
+                num, ksize, molecule, seed, mx, track = template
+            else:
+                node = self.nodes[v]
+                num, ksize, molecule, seed, track = node.num, node.ksize, node.molecule, node.seed, abunds is not None
+                mx = lo if lo == hi else node.max_hash
+            mh = KmerMinHash(num, ksize, False, seed, mx, track, alphabet=None if molecule == "DNA" else molecule)
+            a, b = int(off[v]), int(off[v + 1])
+            if b > a and abunds is not None:
+                h64, a64 = np.ascontiguousarray(hashes[a:b]), abunds[a:b].astype(np.uint64)
+                call(self._L.smh_add_many_with_abund, mh._p, h64.ctypes.data_as(u64p), a64.ctypes.data_as(u64p), b - a)
+            elif b > a:
+                mh.add_many(hashes[a:b])
+            out.append(mh)
+        return out
 
     def match(self, records, hits=False, stream=None):
         """Every record of a batch against the index (smh_index_match_*; the rules: include/sourmash_amd.h, "Matching

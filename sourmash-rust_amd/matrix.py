@@ -220,6 +220,14 @@ def cluster_geometry():
     return a.value, b.value
 
 
+def collapse_geometry():
+    """(owner-list length up to which one lane folds a hash's owners, up to which one wave does, groups one round of LDS
+    counters covers for a longer list) of ResidentIndex.collapse"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().smh_collapse_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
 def cluster_pair_budget():
     return int(lib().smh_cluster_pair_budget())
 
