@@ -512,6 +512,73 @@ SmhIndex *smh_index_collapse(SmhIndex *index, const uint32_t *group, uint32_t n_
 void smh_collapse_geometry(uint32_t *lane_max, uint32_t *wave_max, uint32_t *group_tile);
 int smh_index_read(SmhIndex *index, uint64_t *offsets, uint64_t *hashes, uint32_t *abunds);
 
+/* Building an index from records: the records of a batch hashed, folded by group and laid out as a resident index without
+ * leaving the device -- one group of records, one node -- and the concatenation of resident indexes in HBM.
+ * The reference crate has no counterpart, so the rules are fixed here; restated in tests/index_build_restatement.py.  They
+ * are all integers: results are EQUAL, never close.
+ *   like       gives the parameters only: ksize, molecule, seed, max_hash and whether abundances are tracked.  Its contents
+ *              are not read and it is not modified.  It must be a scaled sketch (num == 0, max_hash != 0).
+ *   Groups     groups[r] < n_groups says which node record r feeds.  groups == NULL: record r is node r, and n_groups must
+ *              equal n_records (no group ids are uploaded then).  A group with no records, or whose records yield no
+ *              sampled hash, is an empty node; n_groups == 0 gives an index of 0 nodes.
+ *   SMH_INPUT_NUCLEOTIDE on a DNA `like`: node g holds exactly what smh_add_sequences_grouped(..., force = true) leaves in
+ *              a FRESH sketch of like's parameters for group g -- the hashes <= max_hash of every window of ksize bases of
+ *              the group's records, ascending and distinct; with abundances, each hash carries the number of windows of
+ *              the group's records that have it, as u32.  There is no `force` argument: windows holding a byte outside
+ *              ACGTacgt are skipped, as smh_index_match_* skips them.  On a protein / dayhoff / hp `like` it is the
+ *              translated six-frame arm of smh_add_sequences_grouped, with its errors (the UTF-8 panic of a byte >= 0x80).
+ *   SMH_INPUT_AMINO  smh_add_proteins per group: every window of ksize / 3 residues.  It needs a protein, dayhoff or hp
+ *              `like`; a DNA one is refused as smh_add_protein refuses it.
+ *   Result     every node gets like's parameters: the index is uniform and all-scaled (smh_index_all_scaled), so match,
+ *              lca, collapse and cluster take it as it is; smh_index_has_abundances is like's flag.  It carries no taxonomy,
+ *              no dictionary and no directory; they are built on first use like any index's.
+ *   Refused    with SOURMASH_ERROR_CODE_MSG, NULL is returned and no half-built index stays registered.  Before the device
+ *              is touched and with nothing written: like, offsets or seq NULL; an unknown `input`; a bottom-num `like`;
+ *              SMH_INPUT_AMINO with a DNA `like`; offsets that do not ascend or reach beyond the batch; groups[r] >=
+ *              n_groups (the message names r); groups == NULL with n_groups != n_records; a window size of 0 (ksize == 0,
+ *              or ksize / 3 == 0 off DNA: where the grouped path panics); n_groups >= 2^24 (the grouped fold tags a
+ *              candidate with its group in 24 bits; smh_index_concat joins the pieces).  After hashing: with abundances,
+ *              a (group, hash) seen in 2^32 or more windows -- the message names the lowest such group, worded as
+ *              smh_index_collapse words its SUM refusal; more than 2^31 - 1 (group, hash) pairs in the result.
+ *   Budget     smh_index_build_set_budget(candidates) bounds the work space: a fold is a stretch of the batch's position
+ *              space expected to leave that many candidates -- positions x (max_hash + 1) / 2^64, the notion of
+ *              smh_match_set_pair_budget -- cut where the grouped path cuts its chunks, inside records too.  A hash of one
+ *              group that shows up in several folds is one hash with the counts added.  THE RESULT NEVER DEPENDS ON IT.
+ *              0 restores the default, 2^26: a memory cap chosen by reasoning (about 4 GiB: 40 B of sort buffers per
+ *              candidate with their head-room, 20 B per run), not a tuned figure.
+ *   Device     per fold the hashing kernel of the arm, positions -> groups, the sort by hash and the stable sort by group,
+ *              as the grouped path runs them; then, instead of its read-back, a head count over tiles of tile_elems
+ *              candidates, a scan, an ordered emit (ballot / popcount, no cursor) and the runs' counts.  The runs of several
+ *              folds are merged by one more sort by (group, hash) and the same kernels with the counts as weights.  One
+ *              bisecting lane per group finds the offsets.  Per fold the candidate count and the run count come to the
+ *              host, per call the 8 (n_groups + 1) bytes of offsets; nothing proportional to the hashes crosses in
+ *              either direction.  Work space comes from the block pool and is back there when the call returns.
+ * smh_index_concat  a new index whose nodes are those of parts[0], then parts[1], and so on.  Parts may be any resident
+ *              indexes -- built from sketches, cut, collapsed, built here; scaled or num; of mixed parameters.  Hashes
+ *              are copied device to device, abundances from wherever each part keeps them (host copy or HBM); offsets are
+ *              rebased; parameters and nums are copied and what is decided once per index is decided again.  Abundances
+ *              are kept exactly when every part has them.  The result owns its memory -- the parts may be freed -- and
+ *              carries no taxonomy, dictionary or directory (merging built directories is not done).  Refused (MSG):
+ *              parts NULL with n_parts > 0, a NULL part, more than 2^32 - 2 nodes in all.  n_parts == 0: an empty index.
+ * smh_index_build_geometry  tile_elems: the candidates one workgroup of the head and emit passes takes; threads: its size.
+ * Timers under smh_profile_get: "index_build_heads", "index_build_emit", "index_build_merge"; event counters:
+ * "index_build_fold", "index_built", "index_concat". */
+enum {
+  SMH_INPUT_NUCLEOTIDE = 0,
+  SMH_INPUT_AMINO = 1
+};
+SmhIndex *smh_index_from_sequences(const KmerMinHash *like, int input, const char *seq, const uint64_t *offsets,
+                                   const uint32_t *groups, uint32_t n_records, uint32_t n_groups);
+SmhIndex *smh_index_from_sequences_dev(const KmerMinHash *like, int input, const void *seq_dev, uint64_t total_len,
+                                       const uint64_t *offsets, const uint32_t *groups, uint32_t n_records,
+                                       uint32_t n_groups, void *stream);
+SmhIndex *smh_index_from_records(const KmerMinHash *like, int input, const SmhRecords *r, const uint32_t *groups,
+                                 uint32_t n_groups);
+SmhIndex *smh_index_concat(SmhIndex *const *parts, uint32_t n_parts);
+void smh_index_build_set_budget(uint64_t candidates);
+uint64_t smh_index_build_budget(void);
+void smh_index_build_geometry(uint32_t *tile_elems, uint32_t *threads);
+
 /* Angular similarity on abundances: what `sourmash compare` and `sourmash search` report by default for sketches that
  * track abundances.  The reference crate has no weighted compare, so the rules are fixed here -- DESIGN.md 3.10, restated
  * in tests/angular_restatement.py.  For two sketches A and B that both track abundances, hashes ascending and distinct, one

@@ -193,6 +193,14 @@ _SIGS = {
     "smh_index_collapse": (C.c_void_p, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32]),
     "smh_collapse_geometry": (None, [u32p, u32p, u32p]),
     "smh_index_read": (C.c_int, [C.c_void_p, u64p, u64p, u32p]),
+    "smh_index_from_sequences": (C.c_void_p, [C.c_void_p, C.c_int, C.c_char_p, u64p, u32p, C.c_uint32, C.c_uint32]),
+    "smh_index_from_sequences_dev": (C.c_void_p, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, u64p, u32p, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p]),
+    "smh_index_from_records": (C.c_void_p, [C.c_void_p, C.c_int, C.c_void_p, u32p, C.c_uint32]),
+    "smh_index_concat": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_uint32]),
+    "smh_index_build_set_budget": (None, [C.c_uint64]),
+    "smh_index_build_budget": (C.c_uint64, []),
+    "smh_index_build_geometry": (None, [u32p, u32p]),
     "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
     "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
     "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),

@@ -888,6 +888,60 @@ int smh_index_read(SmhIndex* index, uint64_t* offsets, uint64_t* hashes, uint32_
   });
 }
 
+// ------------------------------------------------------------------ building an index from records, concat (index_build.cpp)
+
+static_assert(SMH_INPUT_NUCLEOTIDE == smh::kBuildNucleotide && SMH_INPUT_AMINO == smh::kBuildAmino, "the inputs of the header are index_build's");
+
+SmhIndex* smh_index_from_sequences(const KmerMinHash* like, int input, const char* seq, const uint64_t* offsets, const uint32_t* groups,
+                                   uint32_t n_records, uint32_t n_groups) {
+  return pad<SmhIndex*>([&] {
+    // every refusal of the arguments first: they need no device
+    // (host memory has no total_len: the offsets themselves say how far the batch reaches)
+    const uint64_t reach = offsets ? offsets[n_records] : 0;
+    smh::check_index_build(like, input, seq != nullptr || (offsets && reach == offsets[0]), reach, offsets, groups, n_records, n_groups);
+    const uint64_t base = offsets[0], total = reach - base;
+    std::vector<uint64_t> rel((size_t)n_records + 1, 0);
+    for (uint32_t i = 0; i <= n_records; i++) rel[i] = offsets[i] - base;
+    auto& dev = smh::Device::get();
+    auto& E = smh::Engine::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    E.seqbuf.ensure(total + 64);
+    if (total) HIP_CHECK(hipMemcpyAsync(E.seqbuf.ptr, seq + base, total, hipMemcpyHostToDevice, dev.stream()));
+    return new SmhIndex(*like, input, E.seqbuf.as<uint8_t>(), total, rel.data(), groups, n_records, n_groups, dev.stream());
+  });
+}
+SmhIndex* smh_index_from_sequences_dev(const KmerMinHash* like, int input, const void* seq_dev, uint64_t total_len, const uint64_t* offsets,
+                                       const uint32_t* groups, uint32_t n_records, uint32_t n_groups, void* stream) {
+  return pad<SmhIndex*>([&] {
+    smh::check_index_build(like, input, seq_dev != nullptr, total_len, offsets, groups, n_records, n_groups);
+    auto& dev = smh::Device::get();
+    return new SmhIndex(*like, input, (const uint8_t*)seq_dev, total_len, offsets, groups, n_records, n_groups, dev.user_stream(stream));
+  });
+}
+SmhIndex* smh_index_from_records(const KmerMinHash* like, int input, const SmhRecords* r, const uint32_t* groups, uint32_t n_groups) {
+  return pad<SmhIndex*>([&] {
+    if (!r) throw Error(smh::kMsg, "index build: records is NULL");
+    static const uint64_t none = 0;   // (a handle without records may hold no offsets)
+    const uint64_t* offsets = r->offsets || r->n ? r->offsets : &none;
+    smh::check_index_build(like, input, r->seq_dev() != nullptr, r->total, offsets, groups, r->n, n_groups);
+    auto& dev = smh::Device::get();
+    return new SmhIndex(*like, input, r->seq_dev(), r->total, offsets, groups, r->n, n_groups, dev.user_stream(nullptr));
+  });
+}
+SmhIndex* smh_index_concat(SmhIndex* const* parts, uint32_t n_parts) {
+  return pad<SmhIndex*>([&] {
+    std::vector<smh::ResidentIndex*> v;
+    if (n_parts && !parts) throw Error(smh::kMsg, "index concat: parts is NULL");
+    for (uint32_t p = 0; p < n_parts; p++) v.push_back(parts[p]);
+    smh::check_index_concat(v.data(), n_parts);
+    (void)smh::Device::get();
+    return new SmhIndex(v.data(), n_parts);
+  });
+}
+void smh_index_build_set_budget(uint64_t candidates) { smh::g_index_build_budget = candidates ? candidates : smh::kIndexBuildBudget; }
+uint64_t smh_index_build_budget(void) { return smh::g_index_build_budget; }
+void smh_index_build_geometry(uint32_t* tile_elems, uint32_t* threads) { smh::index_build_geometry(tile_elems, threads); }
+
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {
   return pad_code([&] { require(rows, "rows"); require(cols, "cols"); rows->compare(*cols, jaccard, common, size, count_common, containment); });

@@ -1,7 +1,7 @@
 // index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
 // similarity on abundances (angular.cpp), matching records (match.cpp), taxonomic LCA (lca.cpp), the thresholded search of a
-// batch (search_many.cpp), clustering (cluster.cpp), collapsing by groups and the read-back (collapse.cpp).  The C boundary
-// (ffi.cpp) only checks pointers and calls in here.
+// batch (search_many.cpp), clustering (cluster.cpp), collapsing by groups and the read-back (collapse.cpp), building one from
+// records and concatenation (index_build.cpp).  The C boundary (ffi.cpp) only checks pointers and calls in here.
 #pragma once
 #include <functional>
 
@@ -47,6 +47,16 @@ struct ResidentIndex {
   // group: parent.n entries (nullable when the parent is empty), each below n_groups or kCollapseDrop; abund: CollapseAbund.
   // Every refusal is kMsg and comes before anything is built; the child carries no taxonomy (its nodes are not the parent's).
   ResidentIndex(ResidentIndex& parent, const uint32_t* group, uint32_t n_groups, uint32_t min_count, double min_fraction, uint32_t abund);
+  // (index_build.cpp) Built from records on the device (the rules: include/sourmash_amd.h, "Building an index from records"):
+  // node g holds what the records of group g leave in a fresh scaled sketch of `like`'s parameters.  input: BuildInput; seq_dev:
+  // the batch in device memory, record r = [offsets[r], offsets[r + 1]) (host, n_records + 1 entries); groups: nullable (record r
+  // is node r).  check_index_build is run first: every refusal that needs no device.  8 (n_groups + 1) bytes of offsets come
+  // to the host, and two counts per fold; nothing proportional to the hashes crosses.
+  ResidentIndex(const KmerMinHash& like, int input, const uint8_t* seq_dev, uint64_t total_len, const uint64_t* offsets,
+                const uint32_t* groups, uint32_t n_records, uint32_t n_groups, hipStream_t s);
+  // (index_build.cpp) The nodes of parts[0], then parts[1], ...: device-to-device copies, offsets rebased, no taxonomy,
+  // dictionary or directory carried over.  The result owns its memory.
+  ResidentIndex(ResidentIndex* const* parts, uint32_t n_parts);
   ~ResidentIndex();
   void enroll();   // into the registry of live indexes: the last step of every constructor
   // (collapse.cpp) the index as it is held: offsets (n + 1, from 0), hashes and abundances (offsets[n] each); any may be null.
@@ -228,6 +238,17 @@ void check_cluster(uint32_t metric, double threshold, uint32_t linkage, bool wan
 // m_g)), the product and the ceiling in IEEE double
 void check_collapse(uint32_t n_groups, double min_fraction, uint32_t abund);
 uint32_t collapse_need(uint32_t members, uint32_t min_count, double min_fraction);
+
+// index_build.cpp: the expected candidates of one fold of a build (bytes x (max_hash + 1) / 2^64, match's notion).  The default
+// is a memory cap -- a candidate takes 32 bytes of sort buffers (40 with their head-room) and a run 20 more, about 4 GiB in
+// all -- not a measured optimum; the result never depends on it.  check_index_build: the refusals of the arguments alone
+// (kMsg; needs no device), total_len = the bytes the offsets may reach.
+enum BuildInput : int { kBuildNucleotide = 0, kBuildAmino = 1 };
+constexpr uint64_t kIndexBuildBudget = 1ull << 26;
+extern uint64_t g_index_build_budget;
+void check_index_build(const KmerMinHash* like, int input, bool have_seq, uint64_t total_len, const uint64_t* offsets, const uint32_t* groups,
+                       uint32_t n_records, uint32_t n_groups);
+void check_index_concat(ResidentIndex* const* parts, uint32_t n_parts);
 
 // downsample.cpp (the rules are in include/sourmash_amd.h, "Downsampling").  `out` is a fresh sketch: it
 // receives src's parameters with max_hash / num replaced and the kept prefix.  A state that lives in HBM is cut there into a

@@ -1,6 +1,7 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
-// gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip, collapse_kernels.hip).
+// gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip, collapse_kernels.hip,
+// index_build_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -593,5 +594,36 @@ void launch_collapse_bounds(const uint64_t* key, uint32_t S, uint32_t n_groups, 
 // name collapse_finish.
 void launch_collapse_finish(const uint64_t* U, const uint64_t* key, const uint32_t* val, uint32_t S, uint64_t* out_hashes,
                             uint32_t* out_abunds, Device& dev, hipStream_t s);
+
+// --- index_build_kernels.hip -----------------------------------------------------------
+// Building an index from records (the rules are in include/sourmash_amd.h, "Building an index from records").
+// The candidates of a fold, sorted by (group, hash), become runs -- one per distinct (group, hash) -- without a host pass:
+// heads are counted per tile, the counts are scanned, and an ordered emit numbers the heads.  An element is (hash, tag):
+// its group is tag >> shift, and with shift == kBuildCountBits the bits below hold a count (a run of an earlier fold).
+constexpr uint32_t kBuildTile = 2048;        // candidates per workgroup of the head and emit passes (256 threads, 8 each)
+constexpr uint32_t kBuildThreads = 256;
+constexpr int kBuildCountBits = 40;          // a packed run: (group << 40) | count; groups stay below 2^24 (the grouped path's limit)
+constexpr uint32_t kBuildNoError = 0xffffffffu;
+void index_build_geometry(uint32_t* tile_elems, uint32_t* threads);
+inline uint32_t index_build_tiles(uint64_t n) { return (uint32_t)((n + kBuildTile - 1) / kBuildTile); }
+// out[i] = groups ? groups[i / per] : i / per, for i < n_entries (per = 6: the segments of the translated arm)
+void launch_index_build_groups(const uint32_t* groups, uint64_t n_entries, uint32_t per, uint32_t* out, hipStream_t s);
+// tile_heads[t] = the heads among elements [t * kBuildTile, ...) of the n sorted elements.  Profile name index_build_heads.
+void launch_index_build_heads(const uint64_t* hash, const uint64_t* tag, uint64_t n, int shift, uint32_t* tile_heads, Device& dev,
+                              hipStream_t s);
+// tile_heads scanned (exclusive): run_hash[r] and run_start[r] of every head, in order.  Profile name index_build_emit.
+void launch_index_build_emit(const uint64_t* hash, const uint64_t* tag, uint64_t n, int shift, const uint32_t* tile_heads,
+                             uint64_t* run_hash, uint32_t* run_start, Device& dev, hipStream_t s);
+// run_pack[r] = (group << kBuildCountBits) | count of run r = elements [run_start[r], run_start[r + 1]) (the last ends at n):
+// their number under shift == 0, else the sum of their counts.  A count of 2^32 or more lowers *err to the run's group (the
+// word then holds the low 32 bits).  Belongs to the emit pass's timer.
+void launch_index_build_counts(const uint64_t* tag, uint64_t n, int shift, const uint32_t* run_start, uint32_t nruns, uint64_t* run_pack,
+                               uint32_t* err, Device& dev, hipStream_t s);
+// The n_runs packed runs, ascending by group: offsets[g] = base + the runs of the groups below g, for g = 0 .. n_groups (one
+// bisecting lane per group), and abunds[r] (nullable) = the count of run r.
+void launch_index_build_finish(const uint64_t* run_pack, uint32_t n_runs, uint32_t n_groups, uint64_t* offsets, uint32_t* abunds, Device& dev,
+                               hipStream_t s);
+// dst[i] = src[i] + delta for i < n (the offsets of a part of a concatenation; delta wraps like the subtraction it stands for)
+void launch_index_build_rebase(const uint64_t* src, uint64_t n, uint64_t delta, uint64_t* dst, hipStream_t s);
 
 }  // namespace smh

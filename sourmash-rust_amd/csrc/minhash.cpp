@@ -1424,6 +1424,39 @@ void add_sequences_grouped(KmerMinHash* const* mhs, uint32_t n_mh, const uint8_t
   }
 }
 
+// ------------------------------------------------------------------------------------
+// BatchSource: the sources above for index_build.cpp
+
+struct BatchSource::Impl {
+  DnaSource dna;
+  ProteinSource prot;
+  AminoSource amino;
+  HashSource* src = nullptr;
+};
+
+BatchSource::BatchSource(Kind kind, const KmerMinHash& like, const SeqBatch& b, const uint64_t* h_offsets, hipStream_t s)
+    : impl_(new Impl()) {
+  Device& dev = Device::get();
+  Engine& E = Engine::get();
+  pos_table = b.starts; pos_entries = b.nrec;
+  if (kind == kDna) {
+    impl_->dna.b = b; impl_->dna.ksize = like.ksize; impl_->dna.seed = like.seed; impl_->dna.dev = &dev;
+    impl_->src = &impl_->dna;
+  } else if (kind == kAmino) {
+    impl_->amino.b = b; impl_->amino.win = like.ksize / 3; impl_->amino.alphabet = like.molecule; impl_->amino.seed = like.seed;
+    impl_->amino.dev = &dev;
+    impl_->src = &impl_->amino;
+  } else {
+    if (!prepare_protein(b, h_offsets, b.nrec, like.ksize, like.molecule, like.seed, E, dev, s, &impl_->prot, &have_error, &err)) return;
+    impl_->prot.ensure_segments(s);   // positions are mapped to records through the segment table
+    pos_table = E.segbuf.as<uint64_t>(); pos_entries = 6 * b.nrec;
+    impl_->src = &impl_->prot;
+  }
+}
+BatchSource::~BatchSource() = default;
+HashSourceRef BatchSource::ref() const { return impl_->src; }
+uint64_t BatchSource::positions() const { return impl_->src ? impl_->src->positions() : 0; }
+
 namespace {
 constexpr size_t kLazyMaxRecord = 1u << 20;   // calls at least this long go straight to the device
 constexpr size_t kLazyFlushBytes = 8u << 20;  // queued bytes that trigger a batch

@@ -223,4 +223,25 @@ class Engine {
   Engine() = default;
 };
 
+// The position space of a multi-record batch for callers outside minhash.cpp (index_build.cpp): what the shared path of
+// add_sequences_grouped sets up -- the DNA k-mers, the translated six-frame arm of a protein / dayhoff / hp sketch, or
+// amino-acid windows -- behind one handle for Engine::run_chunk (want_pos), and the table launch_pos_to_group maps the
+// candidates' positions to records with.  b.starts are the batch's offsets in device memory (b.nrec >= 2), h_offsets the same
+// on the host; both outlive the source.  The translated arm records the reference's UTF-8 panic in `err` (have_error) when a
+// launch meets it, as add_sequences_grouped reports it after the batch.
+struct BatchSource {
+  enum Kind { kDna, kTranslated, kAmino };
+  BatchSource(Kind kind, const KmerMinHash& like, const SeqBatch& b, const uint64_t* h_offsets, hipStream_t s);
+  ~BatchSource();
+  HashSourceRef ref() const;
+  uint64_t positions() const;           // 0: nothing to hash
+  const uint64_t* pos_table = nullptr;  // device: record starts, or the segment starts of the six-frame layout
+  uint32_t pos_entries = 0;             // b.nrec, or 6 * b.nrec
+  bool have_error = false;
+  Error err{kNoError, ""};
+ private:
+  struct Impl;
+  std::unique_ptr<Impl> impl_;
+};
+
 }  // namespace smh

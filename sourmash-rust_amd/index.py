@@ -12,6 +12,9 @@
   ResidentIndex.collapse    one sketch per group of nodes -- union, core, prevalence -- as a new resident index made on the
                             device (no counterpart: include/sourmash_amd.h, "Collapsing an index by groups"); read / sketches
                             bring an index's own sketches back to the host (smh_index_read)
+  ResidentIndex.from_records  an index built straight from records on the device, one group of records a node, and
+                            ResidentIndex.concat, which joins resident indexes in HBM (no counterpart: include/sourmash_amd.h,
+                            "Building an index from records")
   ResidentIndex.match       the k-mers of every record of a batch the index knows, and each record's best node (no counterpart
                             either: include/sourmash_amd.h, "Matching records")
 
@@ -144,6 +147,36 @@ class _OwnSketches(collections.abc.Sequence):
     def __getitem__(self, k):
         if self._list is None:
             self._list = self._index().sketches()
+        return self._list[k]
+
+
+class _PartParams(collections.abc.Sequence):
+    """(num, ksize, molecule, seed, max_hash, track) of every node of concat()'s result, taken from what its parts' nodes were
+    when one is first asked for: a part contributes one tuple for all its nodes, an earlier concat()'s list, or its host
+    sketches (kept alive here; the part's index itself may be freed) with the max_hash the part held them at."""
+
+    def __init__(self, parts):
+        self._sources, self._n, self._list = [], 0, None
+        for p in parts:
+            n = len(p)
+            template, per_node = getattr(p, "_template", None), getattr(p, "_node_templates", None)
+            if per_node is not None:
+                self._sources.append(lambda per_node=per_node: list(per_node))
+            elif template is not None:
+                self._sources.append(lambda template=template, n=n: [template] * n)
+            else:
+                lo, hi = p.max_hash_range
+                self._sources.append(lambda nodes=p.nodes, lo=lo, hi=hi: [
+                    (m.num, m.ksize, m.molecule, m.seed, lo if lo == hi else m.max_hash, bool(m.track_abundance)) for m in nodes])
+            self._n += n
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, k):
+        if self._list is None:
+            self._list = [t for src in self._sources for t in src()]
+            self._sources = None
         return self._list[k]
 
 
@@ -618,9 +651,13 @@ class ResidentIndex:
         off, hashes, abunds = self.read()
         lo, hi = self.max_hash_range
         template = getattr(self, "_template", None)
+        per_node = getattr(self, "_node_templates", None)   # concat()'s result: the parameters its parts' nodes had
         out = []
         for v in range(len(self)):
-            if template is not None:
+            if per_node is not None:
+                num, ksize, molecule, seed, mx, _ = per_node[v]
+                track = abunds is not None
+            elif template is not None:
                 num, ksize, molecule, seed, mx, track = template
             else:
                 node = self.nodes[v]
@@ -635,6 +672,72 @@ class ResidentIndex:
                 mh.add_many(hashes[a:b])
             out.append(mh)
         return out
+
+    # --- building from records, concatenation (additive ABI smh_index_from_*, smh_index_concat; the rules: include/sourmash_amd.h,
+    # "Building an index from records")
+    @classmethod
+    def from_records(cls, records, like, groups=None, n_groups=None, amino=False, stream=None):
+        """An index built from the records of a batch without leaving the device (smh_index_from_*): node g holds what the
+        records of group g leave in a fresh sketch of `like`'s parameters (force=True semantics: windows with a byte outside
+        ACGT are skipped).  records: a fastx.Records, a list of bytes, or (dev_ptr, total_len, offsets), as match() takes
+        them.  like: a scaled KmerMinHash; only its parameters are read.  groups: one int per record (None: record r is node
+        r); n_groups defaults to max(groups) + 1, or to the number of records.  amino=True: the records are amino-acid
+        sequences (`like` is a protein, dayhoff or hp sketch).  The result's `nodes` are its own sketches, read back when
+        first asked."""
+        from .fastx import Records
+        L = lib()
+        if isinstance(records, Records):
+            n = len(records)
+        elif isinstance(records, tuple):
+            ptr, total, offsets = records
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = len(offsets) - 1
+        else:
+            seqs = [bytes(s) for s in records]
+            n = len(seqs)
+        g = None
+        if groups is not None:
+            wide = np.asarray(groups, dtype=np.int64)
+            if wide.shape != (n,):
+                raise ValueError("groups: one per record")
+            if wide.size and (wide.min() < 0 or wide.max() > 0xFFFFFFFF):
+                raise ValueError("groups: ints in [0, 2^32)")
+            if n_groups is None:
+                n_groups = int(wide.max()) + 1 if wide.size else 0
+            g = np.ascontiguousarray(wide, dtype=np.uint32)
+            if g.size == 0:
+                g = np.zeros(1, dtype=np.uint32)   # (never a NULL pointer: NULL means one node per record)
+        elif n_groups is None:
+            n_groups = n
+        gp = g.ctypes.data_as(u32p) if g is not None else None
+        kind = 1 if amino else 0
+        if isinstance(records, Records):
+            h = call(L.smh_index_from_records, like._p, kind, records._p, gp, int(n_groups))
+        elif isinstance(records, tuple):
+            h = call(L.smh_index_from_sequences_dev, like._p, kind, C.c_void_p(ptr), int(total), offsets.ctypes.data_as(u64p), gp, n,
+                     int(n_groups), C.c_void_p(stream or 0))
+        else:
+            offsets = np.zeros(n + 1, dtype=np.uint64)
+            np.cumsum(np.array([len(s) for s in seqs], dtype=np.uint64), out=offsets[1:])
+            h = call(L.smh_index_from_sequences, like._p, kind, b"".join(seqs), offsets.ctypes.data_as(u64p), gp, n, int(n_groups))
+        idx = cls((), _handle=h)
+        idx._template = (0, like.ksize, like.molecule, like.seed, like.max_hash, bool(like.track_abundance))
+        idx.nodes = _OwnSketches(idx)
+        return idx
+
+    @classmethod
+    def concat(cls, parts):
+        """A new index whose nodes are those of parts[0], then parts[1], ... (smh_index_concat): device-to-device copies, no
+        rebuild through the host.  Parts may be any resident indexes; abundances are kept when every part has them; no
+        taxonomy is carried over.  The result owns its memory, and its `nodes` are its own sketches, read back when first
+        asked."""
+        parts = list(parts)
+        L = lib()
+        arr = (C.c_void_p * max(len(parts), 1))(*[p._h for p in parts])
+        idx = cls((), _handle=call(L.smh_index_concat, arr, len(parts)))
+        idx._node_templates = _PartParams(parts)
+        idx.nodes = _OwnSketches(idx)
+        return idx
 
     def match(self, records, hits=False, stream=None):
         """Every record of a batch against the index (smh_index_match_*; the rules: include/sourmash_amd.h, "Matching
