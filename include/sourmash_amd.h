@@ -824,6 +824,17 @@ void smh_lca_geometry(uint32_t *owner_lane_max, uint32_t *record_lane_max, uint3
 void smh_lca_set_budget(uint64_t keys);
 uint64_t smh_lca_budget(void);
 
+/* The kernels of the resident index (gather, gather_many, match, search_many, cluster, lca, collapse, index build) that walk
+ * their items in a grid-stride loop are launched with min(ceil(items / items per workgroup), a limit of the launch's own)
+ * workgroups -- on a large device the second trip through such a loop begins only at hundreds of thousands of items.
+ * smh_set_grid_cap lowers every one of those grids to at most `workgroups`, so that tests reach the later trips, and the
+ * state the kernels carry from trip to trip, at shapes of a few hundred items: 1 makes one workgroup take every trip.
+ * 0 restores the default (no cap).  Process-wide, like the budgets; NO result depends on it -- it only slows large inputs
+ * down, so set it around small ones.  Kernels that place their work by workgroup number alone keep their grids.  Every
+ * launch whose grid the cap lowered adds one to the event counter "grid_capped" (smh_profile_get). */
+void smh_set_grid_cap(uint32_t workgroups);
+uint32_t smh_grid_cap(void);
+
 /* deterministic synthetic DNA of SURVEY.md 8d written to device memory (benchmark input) */
 int smh_synth_dna_dev(void *out_dev, uint64_t start, uint64_t len, uint64_t seed, uint64_t n_every,
                       void *stream);
@@ -966,7 +977,8 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * directory's owner lists through the groups, three launches each), "collapse_partition" (the survivors sorted by group and
  * the groups' bounds among them), "collapse_finish" (the child's hashes and abundances from the partitioned survivors).  Event counters under the same call: "gather_many_chunk",
  * "search_many_chunk", "cluster_chunk" (chunks run), "cluster_round" (greedy rounds launched; with the timers enabled their
- * entries are that count), "match_directory_built", "index_collapsed". */
+ * entries are that count), "match_directory_built", "index_collapsed", "grid_capped" (launches whose grid smh_set_grid_cap
+ * lowered). */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -238,6 +238,8 @@ _SIGS = {
     "smh_lca_geometry": (None, [u32p, u32p, u32p]),
     "smh_lca_set_budget": (None, [C.c_uint64]),
     "smh_lca_budget": (C.c_uint64, []),
+    "smh_set_grid_cap": (None, [C.c_uint32]),
+    "smh_grid_cap": (C.c_uint32, []),
     "smh_release_workspace": (C.c_int, []),
     "smh_pool_set_limit": (None, [C.c_uint64]),
     "smh_pool_bytes": (C.c_uint64, []),

@@ -224,10 +224,6 @@ __global__ __launch_bounds__(256) void k_cl_number(const uint32_t* __restrict__ 
   if (v < n) out[v] = flag[minmem[out[n + v]]];
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, Device& dev) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)dev.cu_count() * 8));
-}
 uint32_t blocks_of(uint32_t n) { return (n + 255) / 256; }
 
 }  // namespace
@@ -247,7 +243,7 @@ void launch_cluster_probe(const MatchDirectory& d, const SearchChunk& ck, Device
   uint32_t shift = 0, m = 0;
   directory_sampling(d.n_hashes, &shift, &m);
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_cl_probe, dim3(grid_for(ck.T, 256, dev)), dim3(256), 0, s, d, shift, m, ck.hashes, ck.qoff, ck.nq, ck.T, ck.n, ck.q0,
+  hipLaunchKernelGGL(k_cl_probe, dim3(grid_for(ck.T, 256, dev.grid_limit(), dev)), dim3(256), 0, s, d, shift, m, ck.hashes, ck.qoff, ck.nq, ck.T, ck.n, ck.q0,
                      ck.c);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("cluster_probe", s);
@@ -284,7 +280,7 @@ void launch_cluster_pack(const SearchRow* rows, uint32_t R, const uint32_t* quer
 
 void launch_cluster_round(const uint32_t* start, const ClusterAdj* adj, const uint32_t* rank, const uint32_t* st_in, uint32_t* st_out,
                           uint32_t n, unsigned long long* undecided, Device& dev, hipStream_t s) {
-  hipLaunchKernelGGL(k_cl_round, dim3(grid_for(n, 256, dev)), dim3(256), 0, s, start, adj, rank, st_in, st_out, n, undecided);
+  hipLaunchKernelGGL(k_cl_round, dim3(grid_for(n, 256, dev.grid_limit(), dev)), dim3(256), 0, s, start, adj, rank, st_in, st_out, n, undecided);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -294,7 +290,7 @@ void launch_cluster_assign(const uint32_t* start, const ClusterAdj* adj, const u
   uint32_t* flag = work + n;
   dev.prof_begin(s);
   HIP_CHECK(hipMemsetAsync(minmem, 0xff, (size_t)n * 4, s));
-  hipLaunchKernelGGL(k_cl_assign, dim3(grid_for(n, 256, dev)), dim3(256), 0, s, start, adj, rank, st, metric, node_offsets, n, minmem, out);
+  hipLaunchKernelGGL(k_cl_assign, dim3(grid_for(n, 256, dev.grid_limit(), dev)), dim3(256), 0, s, start, adj, rank, st, metric, node_offsets, n, minmem, out);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("cluster_assign", s);
   dev.prof_begin(s);

@@ -214,17 +214,13 @@ __global__ __launch_bounds__(256) void k_collapse_bounds(const uint64_t* __restr
   }
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, Device& dev) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)dev.cu_count() * 8));
-}
 
 template <bool EMIT>
 void launch_fold(const CollapseFold& f, Device& dev, hipStream_t s) {
   // (the long lists number at most n_pairs / (their shortest length): the grids are sized for that, the kernels read the counts)
-  hipLaunchKernelGGL(k_collapse_lane<EMIT>, dim3(grid_for(f.d.n_hashes, 256, dev)), dim3(256), 0, s, f);
-  hipLaunchKernelGGL(k_collapse_wave<EMIT>, dim3(grid_for(f.d.n_pairs / (kCollapseLaneMax + 1) + 1, 4, dev)), dim3(256), 0, s, f);
-  hipLaunchKernelGGL(k_collapse_long<EMIT>, dim3(grid_for(f.d.n_pairs / (kCollapseWaveMax + 1) + 1, 1, dev)), dim3(256), 0, s, f);
+  hipLaunchKernelGGL(k_collapse_lane<EMIT>, dim3(grid_for(f.d.n_hashes, 256, dev.grid_limit(), dev)), dim3(256), 0, s, f);
+  hipLaunchKernelGGL(k_collapse_wave<EMIT>, dim3(grid_for(f.d.n_pairs / (kCollapseLaneMax + 1) + 1, 4, dev.grid_limit(), dev)), dim3(256), 0, s, f);
+  hipLaunchKernelGGL(k_collapse_long<EMIT>, dim3(grid_for(f.d.n_pairs / (kCollapseWaveMax + 1) + 1, 1, dev.grid_limit(), dev)), dim3(256), 0, s, f);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -252,7 +248,7 @@ void launch_collapse_emit(const CollapseFold& f, Device& dev, hipStream_t s) {
 }
 
 void launch_collapse_bounds(const uint64_t* key, uint32_t S, uint32_t n_groups, uint32_t* start, Device& dev, hipStream_t s) {
-  hipLaunchKernelGGL(k_collapse_bounds, dim3(grid_for((uint64_t)n_groups + 1, 256, dev)), dim3(256), 0, s, key, S, n_groups, start);
+  hipLaunchKernelGGL(k_collapse_bounds, dim3(grid_for((uint64_t)n_groups + 1, 256, dev.grid_limit(), dev)), dim3(256), 0, s, key, S, n_groups, start);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -260,7 +256,7 @@ void launch_collapse_finish(const uint64_t* U, const uint64_t* key, const uint32
                             uint32_t* out_abunds, Device& dev, hipStream_t s) {
   if (S == 0) return;
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_collapse_finish, dim3(grid_for(S, 256, dev)), dim3(256), 0, s, U, key, val, S, out_hashes, out_abunds);
+  hipLaunchKernelGGL(k_collapse_finish, dim3(grid_for(S, 256, dev.grid_limit(), dev)), dim3(256), 0, s, U, key, val, S, out_hashes, out_abunds);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("collapse_finish", s);
 }

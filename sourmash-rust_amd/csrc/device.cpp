@@ -260,4 +260,14 @@ void Device::prof_reset() {
   times_.clear();
 }
 
+uint32_t g_grid_cap = 0;
+
+uint32_t grid_for(uint64_t items, uint32_t per_block, uint64_t limit, Device& dev) {
+  const uint64_t want = (items + per_block - 1) / per_block;
+  const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(want, limit));
+  if (g_grid_cap == 0 || grid <= g_grid_cap) return (uint32_t)grid;
+  dev.count("grid_capped");
+  return g_grid_cap;
+}
+
 }  // namespace smh

@@ -83,6 +83,7 @@ class Device {
 
   int id() const { return device_; }
   int cu_count() const { return cus_; }
+  uint64_t grid_limit() const { return (uint64_t)cus_ * 8; }   // eight workgroups per CU: the limit of most grid-stride launches (grid_for)
   // the library's own stream (ordered after work an earlier entry point left open on another stream, see leave_open)
   hipStream_t stream() { order_after_open(stream_); return stream_; }
   hipStream_t copy_stream() const { return copy_stream_; }   // host->device chunks that overlap the hashing; the block compare's fill
@@ -148,5 +149,12 @@ class Device {
   std::map<std::string, KernelTimes> times_;
   void drain();
 };
+
+// The grid of a kernel that walks its items in a gridDim-stride loop: ceil(items / per_block) workgroups, at most `limit`
+// (the launch's own: a multiple of the CU count or a constant), at least one.  g_grid_cap (smh_set_grid_cap; 0: none) lowers
+// it further, so that tests reach the loops' later trips at small shapes; every lowered grid is counted as "grid_capped".
+// Only for kernels that stride by gridDim: one that indexes by blockIdx alone needs its exact grid.
+extern uint32_t g_grid_cap;
+uint32_t grid_for(uint64_t items, uint32_t per_block, uint64_t limit, Device& dev);
 
 }  // namespace smh

@@ -1196,6 +1196,8 @@ void smh_lca_geometry(uint32_t* owner_lane_max, uint32_t* record_lane_max, uint3
 }
 void smh_lca_set_budget(uint64_t keys) { smh::g_lca_budget = keys ? keys : smh::kLcaBudget; }
 uint64_t smh_lca_budget(void) { return smh::g_lca_budget; }
+void smh_set_grid_cap(uint32_t workgroups) { smh::g_grid_cap = workgroups; }
+uint32_t smh_grid_cap(void) { return smh::g_grid_cap; }
 
 // ---- a scaled sketch's state as device arrays: the cross-rank union of partial sketches ----
 int smh_sketch_export_dev(KmerMinHash* ptr, uint64_t* mins_dev, uint64_t* abunds_dev, uint64_t capacity, uint64_t* n_out, void* stream) {

@@ -217,7 +217,7 @@ uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q
   HIP_CHECK(hipMemsetAsync(d_assigned, 0xff, (size_t)lq * 4, s));
   HIP_CHECK(hipMemsetAsync(d_st, 0, sizeof(GatherState), s));
 
-  const uint32_t grid = std::max(1u, std::min((n + 3) / 4, (uint32_t)dev.cu_count() * 8));
+  const uint32_t grid = grid_for(n, 4, dev.grid_limit(), dev);
   dev.prof_begin(s);
   hipLaunchKernelGGL(k_gather_hits, dim3(grid), dim3(256), 0, s, idx, q.hashes, lq, shift, m, hits.as<uint32_t>(), d_c0, d_c, d_invoff, d_st);
   HIP_CHECK(hipGetLastError());
@@ -237,7 +237,7 @@ uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q
     HIP_CHECK(hipGetLastError());
     dev.prof_end("gather_invert", s);
     const GatherWeights wt{q.counts, q.starts, q.total};
-    const uint32_t sub_grid = std::max(1u, std::min((std::min(max_len, lq) + 255) / 256, 256u));
+    const uint32_t sub_grid = grid_for(std::min(max_len, lq), 256, 256, dev);
     for (;;) {
       dev.prof_begin(s);
       for (uint32_t k = 0; k < kGatherRoundsPerSync; k++) {

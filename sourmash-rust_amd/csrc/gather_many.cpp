@@ -118,7 +118,7 @@ void ResidentIndex::gather_many_dev(const uint64_t* qh, const uint64_t* qab, con
       HIP_CHECK(hipMemcpyAsync(ck.st, &h_st, 8, hipMemcpyHostToDevice, s));
       launch_gather_many_fill(dir, ck, dev, s);
       // every query is done after its cap + 1 picks at the latest
-      const uint32_t sub_grid = std::max(1u, std::min((std::min(max_len, max_lq) + 1023) / 1024, 32u));
+      const uint32_t sub_grid = grid_for(std::min(max_len, max_lq), 1024, 32, dev);
       for (uint64_t queued = 0;;) {
         launch_gather_many_rounds(dir, ck, offsets.as<uint64_t>(), threshold, sub_grid, kGatherRoundsPerSync, dev, s);
         queued += kGatherRoundsPerSync;

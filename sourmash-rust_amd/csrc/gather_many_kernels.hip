@@ -170,10 +170,6 @@ __global__ __launch_bounds__(256) void k_gm_weights(const uint32_t* __restrict__
     out[p] = starts ? (uint64_t)((p + 1 < n ? starts[p + 1] : total) - starts[p]) : 1ull;
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, Device& dev) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)dev.cu_count() * 8));
-}
 
 }  // namespace
 
@@ -182,7 +178,7 @@ void launch_gather_many_probe(const MatchDirectory& d, const GatherManyChunk& ck
   uint32_t shift = 0, m = 0;
   directory_sampling(d.n_hashes, &shift, &m);
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_gm_probe, dim3(grid_for(ck.T, 256, dev)), dim3(256), 0, s, d, shift, m, ck.hashes, ck.qoff, ck.nq, ck.T, ck.n, ck.rank,
+  hipLaunchKernelGGL(k_gm_probe, dim3(grid_for(ck.T, 256, dev.grid_limit(), dev)), dim3(256), 0, s, d, shift, m, ck.hashes, ck.qoff, ck.nq, ck.T, ck.n, ck.rank,
                      ck.c0, ck.st);
   hipLaunchKernelGGL(k_gm_size, dim3(ck.nq), dim3(256), 0, s, ck.c0, ck.n, threshold, qcnt);
   HIP_CHECK(hipGetLastError());
@@ -195,7 +191,7 @@ void launch_gather_many_fill(const MatchDirectory& d, const GatherManyChunk& ck,
   HIP_CHECK(hipMemcpyAsync(ck.loff, ck.c0, pairs * 4, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemsetAsync(ck.loff + pairs, 0, 4, s));
   exclusive_scan_u32_dev(ck.loff, pairs + 1, nullptr, dev.scratch, s);
-  hipLaunchKernelGGL(k_gm_fill, dim3(grid_for(ck.T, 256, dev)), dim3(256), 0, s, d, ck.qoff, ck.nq, ck.T, ck.n, ck.rank, ck.loff, ck.c, ck.lists);
+  hipLaunchKernelGGL(k_gm_fill, dim3(grid_for(ck.T, 256, dev.grid_limit(), dev)), dim3(256), 0, s, d, ck.qoff, ck.nq, ck.T, ck.n, ck.rank, ck.loff, ck.c, ck.lists);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("gather_many_fill", s);
 }
@@ -215,7 +211,7 @@ void launch_gather_many_rounds(const MatchDirectory& d, const GatherManyChunk& c
 
 void launch_gather_many_weights(const uint32_t* starts, uint32_t total, uint32_t n, uint64_t* out, hipStream_t s) {
   if (n == 0) return;
-  hipLaunchKernelGGL(k_gm_weights, dim3(std::min<uint32_t>((n + 255) / 256, 2048)), dim3(256), 0, s, starts, total, n, out);
+  hipLaunchKernelGGL(k_gm_weights, dim3(grid_for(n, 256, 2048, Device::get())), dim3(256), 0, s, starts, total, n, out);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -29,6 +29,7 @@ namespace {
 
 constexpr uint32_t kSteps = kBuildTile / kBuildThreads;   // 8
 constexpr uint32_t kWaves = kBuildThreads / 64;           // 4
+constexpr uint64_t kFixedGrid = 2048;                     // the grid limit of the launches that are given no device: groups, rebase
 static_assert(kBuildTile % kBuildThreads == 0 && kBuildThreads % 64 == 0, "whole waves, whole steps");
 
 // bit s: element tile * kBuildTile + s * kBuildThreads + tid is a head
@@ -139,11 +140,6 @@ __global__ __launch_bounds__(256) void k_ib_rebase(const uint64_t* __restrict__ 
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) dst[i] = src[i] + delta;
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, uint32_t cus) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)cus * 8));
-}
-
 }  // namespace
 
 void index_build_geometry(uint32_t* tile_elems, uint32_t* threads) {
@@ -153,7 +149,7 @@ void index_build_geometry(uint32_t* tile_elems, uint32_t* threads) {
 
 void launch_index_build_groups(const uint32_t* groups, uint64_t n_entries, uint32_t per, uint32_t* out, hipStream_t s) {
   if (n_entries == 0) return;
-  hipLaunchKernelGGL(k_ib_groups, dim3(grid_for(n_entries, 256, 256)), dim3(256), 0, s, groups, n_entries, per, out);
+  hipLaunchKernelGGL(k_ib_groups, dim3(grid_for(n_entries, 256, kFixedGrid, Device::get())), dim3(256), 0, s, groups, n_entries, per, out);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -179,7 +175,7 @@ void launch_index_build_counts(const uint64_t* tag, uint64_t n, int shift, const
                                uint32_t* err, Device& dev, hipStream_t s) {
   if (nruns == 0) return;
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_ib_counts, dim3(grid_for(nruns, 256, dev.cu_count())), dim3(256), 0, s, tag, n, shift, run_start, nruns, run_pack, err);
+  hipLaunchKernelGGL(k_ib_counts, dim3(grid_for(nruns, 256, dev.grid_limit(), dev)), dim3(256), 0, s, tag, n, shift, run_start, nruns, run_pack, err);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("index_build_emit", s);
 }
@@ -187,13 +183,13 @@ void launch_index_build_counts(const uint64_t* tag, uint64_t n, int shift, const
 void launch_index_build_finish(const uint64_t* run_pack, uint32_t n_runs, uint32_t n_groups, uint64_t* offsets, uint32_t* abunds, Device& dev,
                                hipStream_t s) {
   const uint64_t items = std::max<uint64_t>((uint64_t)n_groups + 1, abunds ? n_runs : 0);
-  hipLaunchKernelGGL(k_ib_finish, dim3(grid_for(items, 256, dev.cu_count())), dim3(256), 0, s, run_pack, n_runs, n_groups, offsets, abunds);
+  hipLaunchKernelGGL(k_ib_finish, dim3(grid_for(items, 256, dev.grid_limit(), dev)), dim3(256), 0, s, run_pack, n_runs, n_groups, offsets, abunds);
   HIP_CHECK(hipGetLastError());
 }
 
 void launch_index_build_rebase(const uint64_t* src, uint64_t n, uint64_t delta, uint64_t* dst, hipStream_t s) {
   if (n == 0) return;
-  hipLaunchKernelGGL(k_ib_rebase, dim3(grid_for(n, 256, 256)), dim3(256), 0, s, src, n, delta, dst);
+  hipLaunchKernelGGL(k_ib_rebase, dim3(grid_for(n, 256, kFixedGrid, Device::get())), dim3(256), 0, s, src, n, delta, dst);
   HIP_CHECK(hipGetLastError());
 }
 

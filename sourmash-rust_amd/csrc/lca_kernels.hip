@@ -184,10 +184,6 @@ __global__ __launch_bounds__(256) void k_lca_records_long(const uint2* __restric
   }
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, Device& dev) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)dev.cu_count() * 8));
-}
 
 }  // namespace
 
@@ -203,10 +199,10 @@ void launch_lca_table(const MatchDirectory& d, const LcaTaxonomy& t, uint32_t* h
   const uint2* tax = reinterpret_cast<const uint2*>(t.tax);
   dev.prof_begin(s);
   HIP_CHECK(hipMemsetAsync(long_count, 0, 4, s));
-  hipLaunchKernelGGL(k_lca_table, dim3(grid_for(d.n_hashes, 256, dev)), dim3(256), 0, s, d, tax, t.node_taxon, hash_taxon, long_list,
+  hipLaunchKernelGGL(k_lca_table, dim3(grid_for(d.n_hashes, 256, dev.grid_limit(), dev)), dim3(256), 0, s, d, tax, t.node_taxon, hash_taxon, long_list,
                      long_count);
   // (the long lists number at most n_pairs / (kLcaOwnerLaneMax + 1): the grid is sized for that, the kernel reads the count)
-  hipLaunchKernelGGL(k_lca_table_long, dim3(grid_for(d.n_pairs / (kLcaOwnerLaneMax + 1) + 1, 4, dev)), dim3(256), 0, s, d, tax,
+  hipLaunchKernelGGL(k_lca_table_long, dim3(grid_for(d.n_pairs / (kLcaOwnerLaneMax + 1) + 1, 4, dev.grid_limit(), dev)), dim3(256), 0, s, d, tax,
                      t.node_taxon, hash_taxon, long_list, long_count);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("lca_table", s);
@@ -218,7 +214,7 @@ void launch_lca_probe(const MatchDirectory& d, const uint32_t* hash_taxon, const
   uint32_t shift = 0, m = 0;
   directory_sampling(d.n_hashes, &shift, &m);
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_lca_probe, dim3(grid_for(T, 256, dev)), dim3(256), 0, s, d, shift, m, hash_taxon, hashes, qoff, nq, T, taxon_out,
+  hipLaunchKernelGGL(k_lca_probe, dim3(grid_for(T, 256, dev.grid_limit(), dev)), dim3(256), 0, s, d, shift, m, hash_taxon, hashes, qoff, nq, T, taxon_out,
                      key_out, flag_out);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("lca_probe", s);
@@ -226,7 +222,7 @@ void launch_lca_probe(const MatchDirectory& d, const uint32_t* hash_taxon, const
 
 void launch_lca_keys(const uint64_t* key, const uint32_t* at, uint32_t T, uint64_t* out, Device& dev, hipStream_t s) {
   if (T == 0) return;
-  hipLaunchKernelGGL(k_lca_keys, dim3(grid_for(T, 256, dev)), dim3(256), 0, s, key, at, T, out);
+  hipLaunchKernelGGL(k_lca_keys, dim3(grid_for(T, 256, dev.grid_limit(), dev)), dim3(256), 0, s, key, at, T, out);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -237,9 +233,9 @@ void launch_lca_records(const LcaTaxonomy& t, const uint32_t* hash_taxon, const 
   const uint2* tax = reinterpret_cast<const uint2*>(t.tax);
   dev.prof_begin(s);
   HIP_CHECK(hipMemsetAsync(big_count, 0, 4, s));
-  hipLaunchKernelGGL(k_lca_records, dim3(grid_for(nrec, 256, dev)), dim3(256), 0, s, tax, hash_taxon, rank, rows, rec_first, nrec, out,
+  hipLaunchKernelGGL(k_lca_records, dim3(grid_for(nrec, 256, dev.grid_limit(), dev)), dim3(256), 0, s, tax, hash_taxon, rank, rows, rec_first, nrec, out,
                      big_list, big_count);
-  hipLaunchKernelGGL(k_lca_records_long, dim3(grid_for(nrec, 4, dev)), dim3(256), 0, s, tax, hash_taxon, rank, rows, rec_first, out,
+  hipLaunchKernelGGL(k_lca_records_long, dim3(grid_for(nrec, 4, dev.grid_limit(), dev)), dim3(256), 0, s, tax, hash_taxon, rank, rows, rec_first, out,
                      big_list, big_count);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("lca_records", s);

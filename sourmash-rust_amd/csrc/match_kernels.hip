@@ -208,10 +208,6 @@ __global__ __launch_bounds__(256) void k_match_hit_scatter(const uint64_t* __res
     if (rank[i] != kMatchMiss) out[at[i]] = run_hash[i];
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, Device& dev) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)dev.cu_count() * 8));
-}
 
 }  // namespace
 
@@ -223,7 +219,7 @@ void match_geometry(uint32_t* lds_pairs, uint32_t* threads_per_record, uint32_t*
 
 void launch_match_owner_ids(const uint64_t* offsets_dev, uint32_t n, uint64_t total, uint32_t* ids, Device& dev, hipStream_t s) {
   if (total == 0) return;
-  hipLaunchKernelGGL(k_match_owner_ids, dim3(grid_for(total, 256, dev)), dim3(256), 0, s, offsets_dev, n, total, ids);
+  hipLaunchKernelGGL(k_match_owner_ids, dim3(grid_for(total, 256, dev.grid_limit(), dev)), dim3(256), 0, s, offsets_dev, n, total, ids);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -234,7 +230,7 @@ void launch_match_probe(const MatchDirectory& d, const uint64_t* run_hash, const
   uint32_t shift = 0, m = 0;
   directory_sampling(d.n_hashes, &shift, &m);
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_match_probe, dim3(grid_for(nruns, 256, dev)), dim3(256), 0, s, d, shift, m, run_hash, run_rec, run_start, nruns,
+  hipLaunchKernelGGL(k_match_probe, dim3(grid_for(nruns, 256, dev.grid_limit(), dev)), dim3(256), 0, s, d, shift, m, run_hash, run_rec, run_start, nruns,
                      ncand, rec0, rows, rec_first, rec_pairs, rank_out, hit_flag);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("match_probe", s);
@@ -245,7 +241,7 @@ void launch_match_tally(const MatchDirectory& d, const uint32_t* rank, MatchRow*
                         hipStream_t s) {
   if (nrec == 0) return;
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_match_tally, dim3(grid_for(nrec, 4, dev)), dim3(256), 0, s, d, rank, rows, rec_first, rec_pairs, nrec, big_list,
+  hipLaunchKernelGGL(k_match_tally, dim3(grid_for(nrec, 4, dev.grid_limit(), dev)), dim3(256), 0, s, d, rank, rows, rec_first, rec_pairs, nrec, big_list,
                      big_count);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("match_tally", s);
@@ -255,9 +251,10 @@ void launch_match_dense(const MatchDirectory& d, const uint32_t* rank, MatchRow*
                         uint32_t nbig, uint32_t n_nodes, uint32_t* slab, Device& dev, hipStream_t s) {
   if (nbig == 0) return;
   constexpr uint32_t kBlocksPerRecord = 16;
+  const uint32_t blocks_per_rec = grid_for(kBlocksPerRecord, 1, kBlocksPerRecord, dev);   // (16 unless the grid cap is lower)
   dev.prof_begin(s);
   HIP_CHECK(hipMemsetAsync(slab, 0, (size_t)nbig * n_nodes * 4, s));
-  hipLaunchKernelGGL(k_match_dense_count, dim3(nbig * kBlocksPerRecord), dim3(256), 0, s, d, rank, rows, rec_first, big, kBlocksPerRecord,
+  hipLaunchKernelGGL(k_match_dense_count, dim3(nbig * blocks_per_rec), dim3(256), 0, s, d, rank, rows, rec_first, big, blocks_per_rec,
                      n_nodes, slab);
   hipLaunchKernelGGL(k_match_dense_pick, dim3(nbig), dim3(256), 0, s, slab, n_nodes, big, rows);
   HIP_CHECK(hipGetLastError());
@@ -267,7 +264,7 @@ void launch_match_dense(const MatchDirectory& d, const uint32_t* rank, MatchRow*
 void launch_match_hit_scatter(const uint64_t* run_hash, const uint32_t* rank, const uint32_t* at, uint32_t nruns, uint64_t* out, Device& dev,
                               hipStream_t s) {
   if (nruns == 0) return;
-  hipLaunchKernelGGL(k_match_hit_scatter, dim3(grid_for(nruns, 256, dev)), dim3(256), 0, s, run_hash, rank, at, nruns, out);
+  hipLaunchKernelGGL(k_match_hit_scatter, dim3(grid_for(nruns, 256, dev.grid_limit(), dev)), dim3(256), 0, s, run_hash, rank, at, nruns, out);
   HIP_CHECK(hipGetLastError());
 }
 

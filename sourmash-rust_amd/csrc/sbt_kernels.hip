@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void k_ng_get(const uint32_t* __restrict__ bin
   }
 }
 
-uint32_t grid_for(uint64_t n) {
+uint32_t sbt_grid(uint64_t n) {
   const uint64_t g = (n + 255) / 256;
   return (uint32_t)(g < 4096 ? (g ? g : 1) : 4096);
 }
@@ -256,7 +256,7 @@ uint32_t grid_for(uint64_t n) {
 
 void launch_sbt_bins(const uint64_t* hashes, uint64_t n, const DeviceLayout& L, uint32_t* bins, hipStream_t s) {
   if (n == 0 || L.T == 0) return;
-  hipLaunchKernelGGL(k_sbt_bins, dim3(grid_for(n)), dim3(256), 0, s, hashes, n, L.sizes, L.magic, L.T, bins);
+  hipLaunchKernelGGL(k_sbt_bins, dim3(sbt_grid(n)), dim3(256), 0, s, hashes, n, L.sizes, L.magic, L.T, bins);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -264,7 +264,7 @@ void launch_ng_count_many(const uint64_t* hashes, uint64_t n, const DeviceLayout
                           uint32_t* minidx, const uint64_t* bit_base, unsigned long long* counters, uint8_t* out_new, hipStream_t s) {
   (void)hashes;
   if (n == 0) return;
-  const dim3 g(grid_for(n)), b(256);
+  const dim3 g(sbt_grid(n)), b(256);
   hipLaunchKernelGGL(k_ng_minidx_init, g, b, 0, s, bins, n, L.T, bit_base, minidx);
   hipLaunchKernelGGL(k_ng_minidx, g, b, 0, s, bins, n, L.T, bit_base, minidx);
   hipLaunchKernelGGL(k_ng_new, g, b, 0, s, bins, n, L.T, bit_base, minidx, L.woff, words, counters, out_new);
@@ -274,7 +274,7 @@ void launch_ng_count_many(const uint64_t* hashes, uint64_t n, const DeviceLayout
 
 void launch_ng_get_many(const uint32_t* bins, uint64_t n, const DeviceLayout& L, const uint64_t* words, uint8_t* out, hipStream_t s) {
   if (n == 0) return;
-  hipLaunchKernelGGL(k_ng_get, dim3(grid_for(n)), dim3(256), 0, s, bins, n, L.T, L.woff, words, out);
+  hipLaunchKernelGGL(k_ng_get, dim3(sbt_grid(n)), dim3(256), 0, s, bins, n, L.T, L.woff, words, out);
   HIP_CHECK(hipGetLastError());
 }
 

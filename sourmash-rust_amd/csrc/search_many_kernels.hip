@@ -90,10 +90,6 @@ __global__ __launch_bounds__(kTileThreads) void k_sm_emit(Rule r, const uint32_t
   }
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, Device& dev) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)dev.cu_count() * 8));
-}
 
 Rule rule_of(const SearchChunk& ck) { return {ck.node_offsets, ck.threshold, ck.metric, ck.self, ck.threshold_common}; }
 
@@ -109,7 +105,7 @@ void launch_search_many_probe(const MatchDirectory& d, const SearchChunk& ck, De
   uint32_t shift = 0, m = 0;
   directory_sampling(d.n_hashes, &shift, &m);
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_sm_probe, dim3(grid_for(ck.T, 256, dev)), dim3(256), 0, s, d, shift, m, ck.hashes, ck.qoff, ck.nq, ck.T, ck.n, ck.c);
+  hipLaunchKernelGGL(k_sm_probe, dim3(grid_for(ck.T, 256, dev.grid_limit(), dev)), dim3(256), 0, s, d, shift, m, ck.hashes, ck.qoff, ck.nq, ck.T, ck.n, ck.c);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("search_many_probe", s);
 }

@@ -2033,7 +2033,7 @@ __global__ __launch_bounds__(256) void k_synth_dna(uint8_t* __restrict__ out, ui
   }
 }
 
-inline int grid_for(uint64_t items, int per_block, int cap) {
+inline int sketch_grid(uint64_t items, int per_block, int cap) {
   uint64_t g = (items + per_block - 1) / per_block;
   if (g < 1) g = 1;
   if (g > (uint64_t)cap) g = cap;
@@ -2210,7 +2210,7 @@ void launch_dna_hash(const SeqBatch& b_in, const HashParams& p, const CandSink& 
     dev.prof_end("dna_rolling", s);
   } else {
     dev.prof_begin(s);
-    hipLaunchKernelGGL(k_dna_generic, dim3(grid_for(span, 256, dev.cu_count() * 16)), dim3(256), 0, s,
+    hipLaunchKernelGGL(k_dna_generic, dim3(sketch_grid(span, 256, dev.cu_count() * 16)), dim3(256), 0, s,
                        b_in, p, sink);
     HIP_CHECK(hipGetLastError());
     dev.prof_end("dna_generic", s);
@@ -2236,21 +2236,21 @@ __global__ __launch_bounds__(256) void k_record_stats(const uint64_t* __restrict
 }
 void launch_record_stats(const uint64_t* starts, uint32_t nrec, uint32_t ksize, uint64_t* out2, hipStream_t s) {
   HIP_CHECK(hipMemsetAsync(out2, 0, 16, s));
-  hipLaunchKernelGGL(k_record_stats, dim3(grid_for(nrec, 256, 2048)), dim3(256), 0, s, starts, nrec, ksize,
+  hipLaunchKernelGGL(k_record_stats, dim3(sketch_grid(nrec, 256, 2048)), dim3(256), 0, s, starts, nrec, ksize,
                      reinterpret_cast<unsigned long long*>(out2));
   HIP_CHECK(hipGetLastError());
 }
 
 void launch_first_bad_record(const uint64_t* starts, const uint64_t* vends, uint32_t nrec, uint32_t ksize, uint64_t* out, hipStream_t s) {
   HIP_CHECK(hipMemsetAsync(out, 0xff, 8, s));
-  hipLaunchKernelGGL(k_first_bad_record, dim3(grid_for(nrec, 256, 2048)), dim3(256), 0, s, starts, vends, nrec, ksize,
+  hipLaunchKernelGGL(k_first_bad_record, dim3(sketch_grid(nrec, 256, 2048)), dim3(256), 0, s, starts, vends, nrec, ksize,
                      reinterpret_cast<unsigned long long*>(out));
   HIP_CHECK(hipGetLastError());
 }
 
 void launch_first_invalid(const SeqBatch& b, uint64_t* vends_out, hipStream_t s) {
   if (b.len == 0) return;
-  hipLaunchKernelGGL(k_first_invalid, dim3(grid_for(b.len + 32, 256 * 16, 8192)), dim3(256), 0, s, b,
+  hipLaunchKernelGGL(k_first_invalid, dim3(sketch_grid(b.len + 32, 256 * 16, 8192)), dim3(256), 0, s, b,
                      vends_out);
   HIP_CHECK(hipGetLastError());
 }
@@ -2258,7 +2258,7 @@ void launch_first_invalid(const SeqBatch& b, uint64_t* vends_out, hipStream_t s)
 void launch_translate(const SeqBatch& b, const uint64_t* seg_off, uint32_t nseg, uint64_t total, uint32_t ksize, uint32_t alphabet,
                       uint8_t* residues, uint32_t* bad_utf8, hipStream_t s) {
   if (total == 0) return;
-  hipLaunchKernelGGL(k_translate, dim3(grid_for(b.len, kTrTile, 16384)), dim3(kTrThreads), 0, s, b, seg_off, nseg, ksize, alphabet,
+  hipLaunchKernelGGL(k_translate, dim3(sketch_grid(b.len, kTrTile, 16384)), dim3(kTrThreads), 0, s, b, seg_off, nseg, ksize, alphabet,
                      residues, bad_utf8);
   HIP_CHECK(hipGetLastError());
 }
@@ -2304,7 +2304,7 @@ void launch_hash_windows(const uint8_t* bytes, uint64_t total, const uint64_t* s
   if (p.range_hi <= p.range_lo) return;
   const uint32_t stage_cap = 1024;
   const size_t lds = 16 + (size_t)stage_cap * 8 * (sink.pos ? 2 : 1);
-  const dim3 grid(grid_for((p.range_hi - p.range_lo + kWinRun - 1) / kWinRun, 256, 16384));
+  const dim3 grid(sketch_grid((p.range_hi - p.range_lo + kWinRun - 1) / kWinRun, 256, 16384));
 #define SMH_HW(W_) hipLaunchKernelGGL(k_hash_windows<W_>, grid, dim3(256), lds, s, bytes, seg_offsets, nseg, win, p, sink, stage_cap)
   // the usual protein k-mer sizes (ksize 21 / 27 / 30 nucleotides) get static instantiations
   if (win == 7) SMH_HW(7); else if (win == 9) SMH_HW(9); else if (win == 10) SMH_HW(10); else SMH_HW(0);
@@ -2325,7 +2325,7 @@ void launch_amino_hash(const SeqBatch& b_in, uint32_t win, const HashParams& p, 
   const uint64_t span = hi - p.range_lo;
   dev.prof_begin(s);
   if (win > (uint32_t)kAmMaxWin) {
-    hipLaunchKernelGGL(k_amino_generic, dim3(grid_for(span, 256, dev.cu_count() * 16)), dim3(256), 0, s, b_in, p, sink, win);
+    hipLaunchKernelGGL(k_amino_generic, dim3(sketch_grid(span, 256, dev.cu_count() * 16)), dim3(256), 0, s, b_in, p, sink, win);
     HIP_CHECK(hipGetLastError());
     dev.prof_end("amino_generic", s);
     return;
@@ -2354,7 +2354,7 @@ void launch_hash_segments(const uint8_t* bytes, const uint64_t* seg_offsets, uin
 
 void launch_filter_hashes(const uint64_t* hashes, const HashParams& p, const CandSink& sink, hipStream_t s) {
   if (p.range_hi <= p.range_lo) return;
-  hipLaunchKernelGGL(k_filter_hashes, dim3(grid_for(p.range_hi - p.range_lo, 256, 4096)), dim3(256), 0, s, hashes, p, sink);
+  hipLaunchKernelGGL(k_filter_hashes, dim3(sketch_grid(p.range_hi - p.range_lo, 256, 4096)), dim3(256), 0, s, hashes, p, sink);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2362,7 +2362,7 @@ void launch_synth_dna(uint8_t* out, uint64_t start, uint64_t len, uint64_t seed,
                       hipStream_t s) {
   if (len == 0) return;
   if (start & 31) throw_internal("synth_dna: start must be a multiple of 32");
-  hipLaunchKernelGGL(k_synth_dna, dim3(grid_for((len + 31) / 32, 256, 8192)), dim3(256), 0, s, out,
+  hipLaunchKernelGGL(k_synth_dna, dim3(sketch_grid((len + 31) / 32, 256, 8192)), dim3(256), 0, s, out,
                      start, len, seed, n_every);
   HIP_CHECK(hipGetLastError());
 }

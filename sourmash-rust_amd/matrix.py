@@ -184,6 +184,16 @@ def set_lca_budget(keys):
     lib().smh_lca_set_budget(int(keys))
 
 
+def grid_cap():
+    return int(lib().smh_grid_cap())
+
+
+def set_grid_cap(workgroups):
+    """at most this many workgroups for the resident-index kernels that loop by the grid (smh_set_grid_cap): a test knob that
+    brings the loops' later trips to small shapes -- no result depends on it; 0 restores the default (no cap)"""
+    lib().smh_set_grid_cap(int(workgroups))
+
+
 def gather_many_budget():
     return int(lib().smh_gather_many_budget())
 

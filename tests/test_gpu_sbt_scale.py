@@ -19,7 +19,7 @@ import sbt_restatement as R
 
 V5_SIZES = [99991, 99989, 99971, 99961]
 LDS_BYTES = 64 * 1024        # k_sbt_nodes stages a node's tables, k_sbt_leaves a (leaf, query) pair, up to this size
-GRID_THREADS = 4096 * 256    # grid_for's cap: the grid-stride kernels take a second turn beyond this many items
+GRID_THREADS = 4096 * 256    # sbt_grid's cap: the grid-stride kernels take a second turn beyond this many items
 CHUNK_ENTRIES = 8 << 20      # Sbt::find_many: queries per chunk = 8 Mi / max(widest level of internal nodes, leaves)
 
 

@@ -169,3 +169,18 @@ def test_signature_scaled_quirk_q9(pkg, sbt_subset_sketches):
     assert mh.num == 0 and mh.max_hash == 9223372036854776 and mh.track_abundance
     assert mh.mins == d[key][0]["signatures"][0]["mins"]          # kept in file order, like the reference
     assert mh.abunds == d[key][0]["signatures"][0]["abundances"]
+
+
+def test_grid_cap_needs_no_device(pkg):
+    """the knob of tests/test_gpu_grid_trips.py: no cap after load, set and get round-trip, 0 restores the default"""
+    L = pkg.lib()
+    assert L.smh_grid_cap() == 0 and pkg.matrix.grid_cap() == 0
+    try:
+        for cap in (1, 3, 2048, (1 << 32) - 1):
+            pkg.matrix.set_grid_cap(cap)
+            assert pkg.matrix.grid_cap() == cap == L.smh_grid_cap()
+        L.smh_set_grid_cap(7)
+        assert pkg.matrix.grid_cap() == 7
+    finally:
+        pkg.matrix.set_grid_cap(0)
+    assert pkg.matrix.grid_cap() == 0 and L.smh_grid_cap() == 0
