@@ -58,8 +58,7 @@ void ResidentIndex::cluster(uint32_t metric, double threshold, uint32_t threshol
   uint32_t max_q = 0;
   for (uint32_t a = 0, b = 0; a < n; a = b) {
     b = search_many_chunk_end(qoff, a, n, n, g_search_many_budget);
-    chunks.push_back({a, b, rel.size()});
-    for (uint32_t k = a; k <= b; k++) rel.push_back((uint32_t)(qoff[k] - qoff[a]));
+    chunks.push_back({a, b, append_chunk_offsets(qoff, a, b, &rel)});
     max_q = std::max(max_q, b - a);
   }
   const size_t out_words = (size_t)n * (greedy ? 3 : 2) + 1;
@@ -69,16 +68,10 @@ void ResidentIndex::cluster(uint32_t metric, double threshold, uint32_t threshol
   HIP_CHECK(hipMemcpyAsync(d_rel.ptr, rel.data(), rel.size() * 4, hipMemcpyHostToDevice, s));
   if (scores && !greedy) HIP_CHECK(hipMemcpyAsync(d_scores.ptr, scores, (size_t)n * 4, hipMemcpyHostToDevice, s));
   auto chunk_of = [&](const Chunk& c) {
-    SearchChunk ck;
-    ck.hashes = hashes.as<uint64_t>() + qoff[c.a];
+    SearchChunk ck = search_chunk(hashes.as<uint64_t>(), qoff, c.a, c.b, metric, threshold, threshold_common,
+                                  greedy ? kSearchNoDiagonal : kSearchUpperOnly);
     ck.qoff = d_rel.as<uint32_t>() + c.rel_at;
-    ck.nq = c.b - c.a; ck.T = (uint32_t)(qoff[c.b] - qoff[c.a]); ck.n = n;
-    ck.q0 = c.a;
     ck.c = d_c.as<uint32_t>();
-    ck.tiles = tiles;
-    ck.node_offsets = offsets.as<uint64_t>();
-    ck.metric = metric; ck.threshold_common = threshold_common; ck.threshold = threshold;
-    ck.self = greedy ? kSearchNoDiagonal : kSearchUpperOnly;
     return ck;
   };
   auto fetch = [&] {
@@ -121,13 +114,7 @@ void ResidentIndex::cluster(uint32_t metric, double threshold, uint32_t threshol
       held[k].R = 0;
       if (ck.T == 0) continue;
       ck.tile_rows = d_tiles.as<uint32_t>();
-      const size_t cells = (size_t)ck.nq * tiles;
-      HIP_CHECK(hipMemsetAsync(ck.c, 0, (size_t)ck.nq * n * 4, s));
-      launch_search_many_probe(dir, ck, dev, s);
-      launch_search_many_select(ck, dev, s);
-      uint32_t R = 0;
-      HIP_CHECK(hipMemcpyAsync(&R, ck.tile_rows + cells, 4, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
+      const uint32_t R = search_chunk_rows(dir, ck, dev, s);
       total += R;
       if (total > g_cluster_pair_budget)
         throw Error(kMsg, "cluster: the greedy linkage holds the directed adjacency in device memory; it has reached " + std::to_string(total) +

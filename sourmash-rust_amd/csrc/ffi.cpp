@@ -112,6 +112,14 @@ T** leak_array(std::vector<T*>& v, uintptr_t* size) {
   return arr;
 }
 
+// the queries of a batch call as the checked array the index takes
+std::vector<const smh::KmerMinHash*> require_queries(const KmerMinHash* const* queries, uint32_t n) {
+  if (n) require(queries, "queries");
+  std::vector<const smh::KmerMinHash*> v(n);
+  for (uint32_t q = 0; q < n; q++) { require(queries[q], "queries[q]"); v[q] = queries[q]; }
+  return v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -735,6 +743,12 @@ int smh_index_gather(SmhIndex* index, const KmerMinHash* query, uint32_t thresho
 uint32_t smh_gather_rounds_per_sync(void) { return smh::kGatherRoundsPerSync; }
 
 namespace {
+// a CSR carries no parameters: the index must speak for itself with one voice
+void require_uniform_scaled(const SmhIndex* index, const char* op) {
+  if (!(index->uniform && index->all_scaled))
+    throw Error(smh::kMsg, std::string(op) + ": the device form needs an index whose nodes are scaled sketches with the same ksize, molecule, "
+                                             "seed and max_hash");
+}
 // the rows handed out the way match hands out hit_hashes: malloc'ed, one element at least
 void gather_many_rows_out(const std::vector<smh::GatherRow>& got, SmhGatherRow** rows) {
   SmhGatherRow* out = (SmhGatherRow*)malloc((got.empty() ? 1 : got.size()) * sizeof(SmhGatherRow));
@@ -749,9 +763,7 @@ int smh_index_gather_many(SmhIndex* index, const KmerMinHash* const* queries, ui
   return pad_code([&] {
     auto& dev = smh::Device::get();   // first: without a device the call says so, whatever it was handed
     require(index, "index"); require(row_offsets, "row_offsets"); require(rows, "rows");
-    if (n_queries) require(queries, "queries");
-    std::vector<const smh::KmerMinHash*> v(n_queries);
-    for (uint32_t q = 0; q < n_queries; q++) { require(queries[q], "queries[q]"); v[q] = queries[q]; }
+    const std::vector<const smh::KmerMinHash*> v = require_queries(queries, n_queries);
     std::vector<smh::GatherRow> got;
     index->gather_many(v.data(), n_queries, threshold_common, rows_capacity, row_offsets, &got, query_offsets, assigned, dev);
     gather_many_rows_out(got, rows);
@@ -764,10 +776,7 @@ int smh_index_gather_block_dev(SmhIndex* index, const uint64_t* q_hashes_dev, co
   return pad_code([&] {
     auto& dev = smh::Device::get();
     require(index, "index"); require(row_offsets, "row_offsets"); require(rows, "rows"); require(q_offsets, "q_offsets");
-    // a CSR carries no parameters: the index must speak for itself with one voice
-    if (!(index->uniform && index->all_scaled))
-      throw Error(smh::kMsg, "gather_many: the device form needs an index whose nodes are scaled sketches with the same ksize, molecule, "
-                             "seed and max_hash");
+    require_uniform_scaled(index, "gather_many");
     if (n_queries && q_offsets[n_queries] != q_offsets[0]) require(q_hashes_dev, "q_hashes_dev");
     std::vector<smh::GatherRow> got;
     index->gather_many_dev(q_hashes_dev, q_abunds_dev, q_offsets, n_queries, threshold_common, rows_capacity, row_offsets, &got, assigned,
@@ -799,9 +808,7 @@ int smh_index_search_many(SmhIndex* index, const KmerMinHash* const* queries, ui
     search_require(metric, threshold, row_offsets, rows);
     auto& dev = smh::Device::get();
     require(index, "index");
-    if (n_queries) require(queries, "queries");
-    std::vector<const smh::KmerMinHash*> v(n_queries);
-    for (uint32_t q = 0; q < n_queries; q++) { require(queries[q], "queries[q]"); v[q] = queries[q]; }
+    const std::vector<const smh::KmerMinHash*> v = require_queries(queries, n_queries);
     *rows = reinterpret_cast<SmhSearchRow*>(index->search_many(v.data(), n_queries, metric, threshold, threshold_common, row_offsets, dev));
   });
 }
@@ -812,10 +819,7 @@ int smh_index_search_block_dev(SmhIndex* index, const uint64_t* q_hashes_dev, co
     search_require(metric, threshold, row_offsets, rows);
     auto& dev = smh::Device::get();
     require(index, "index"); require(q_offsets, "q_offsets");
-    // a CSR carries no parameters: the index must speak for itself with one voice
-    if (!(index->uniform && index->all_scaled))
-      throw Error(smh::kMsg, "search_many: the device form needs an index whose nodes are scaled sketches with the same ksize, molecule, "
-                             "seed and max_hash");
+    require_uniform_scaled(index, "search_many");
     if (n_queries && q_offsets[n_queries] != q_offsets[0]) require(q_hashes_dev, "q_hashes_dev");
     *rows = reinterpret_cast<SmhSearchRow*>(index->search_many_dev(q_hashes_dev, q_offsets, n_queries, metric, threshold, threshold_common,
                                                                    smh::kSearchNotSelf, row_offsets, dev, dev.user_stream(stream)));
@@ -1131,9 +1135,7 @@ int smh_index_lca_many(SmhIndex* index, const KmerMinHash* const* queries, uint3
   return pad_code([&] {
     auto& dev = smh::Device::get();   // first: without a device the call says so, whatever it was handed
     require(index, "index"); require(count_offsets, "count_offsets"); require(taxa, "taxa"); require(counts, "counts");
-    if (n_queries) require(queries, "queries");
-    std::vector<const smh::KmerMinHash*> v(n_queries);
-    for (uint32_t q = 0; q < n_queries; q++) { require(queries[q], "queries[q]"); v[q] = queries[q]; }
+    const std::vector<const smh::KmerMinHash*> v = require_queries(queries, n_queries);
     std::vector<uint32_t> t;
     std::vector<uint64_t> c;
     index->lca_many(v.data(), n_queries, count_offsets, &t, &c, query_offsets, hash_taxon, dev);

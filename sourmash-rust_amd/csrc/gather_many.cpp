@@ -1,9 +1,9 @@
 // gather_many.cpp -- ResidentIndex::gather_many (the rules are in include/sourmash_amd.h,
-// smh_index_gather_many): the checks of every query, the staging of a batch of sketches into one CSR in device memory, the
-// chunks cut at query boundaries, and per chunk the probe, the sizing, the fill, the rounds and the read-back.  The kernels
-// are in gather_many_kernels.hip; the hash directory is the index's (index.cpp), shared with match.
+// smh_index_gather_many): the chunks cut at query boundaries, and per chunk the probe, the sizing, the fill, the rounds and
+// the read-back.  The checks of every query and the staging of a batch of sketches into one CSR in device memory are
+// query_batch.cpp's.  The kernels are in gather_many_kernels.hip; the hash directory is the index's (index.cpp), shared with
+// match.
 #include <algorithm>
-#include <memory>
 #include <string>
 
 #include "index.hpp"
@@ -27,10 +27,7 @@ void ResidentIndex::gather_many_dev(const uint64_t* qh, const uint64_t* qab, con
                                     uint32_t capacity, uint64_t* row_offsets, std::vector<GatherRow>* rows_out, uint32_t* assigned,
                                     Device& dev, hipStream_t s) {
   if (threshold == 0) threshold = 1;
-  for (uint32_t q = 0; q < nq; q++) {
-    if (qoff[q + 1] < qoff[q]) throw Error(kMsg, "gather_many: offsets must ascend (query " + std::to_string(q) + ")");
-    if (qoff[q + 1] - qoff[q] >= 0xffffffffull) throw_internal("gather_many: a query of 2^32 - 1 or more hashes");
-  }
+  check_query_offsets("gather_many", qoff, nq, kQueryLimit32);
   check_directory_size("gather_many");
   const uint64_t total = nq ? qoff[nq] - qoff[0] : 0;
   std::vector<uint64_t> roff((size_t)nq + 1, 0);
@@ -75,9 +72,7 @@ void ResidentIndex::gather_many_dev(const uint64_t* qh, const uint64_t* qab, con
       ck.rowoff = d_rowoff.as<uint64_t>();
       ck.qs = d_qs.as<GatherManyQuery>();
       ck.st = d_st.as<GatherManyState>();
-      rel.resize((size_t)Qc + 1);
-      for (uint32_t k = 0; k <= Qc; k++) rel[k] = (uint32_t)(qoff[a + k] - qoff[a]);
-      HIP_CHECK(hipMemcpyAsync(d_qoff.ptr, rel.data(), ((size_t)Qc + 1) * 4, hipMemcpyHostToDevice, s));
+      upload_chunk_offsets(qoff, a, b, &rel, d_qoff.as<uint32_t>(), s);   // (the stream is waited for below, on every way on)
       HIP_CHECK(hipMemsetAsync(ck.c0, 0, pairs * 8, s));   // c0 and c
       HIP_CHECK(hipMemsetAsync(ck.assigned, 0xff, T * 4, s));
       HIP_CHECK(hipMemsetAsync(ck.st, 0, sizeof(GatherManyState), s));
@@ -146,92 +141,12 @@ void ResidentIndex::gather_many_dev(const uint64_t* qh, const uint64_t* qab, con
 
 void ResidentIndex::gather_many(const KmerMinHash* const* queries, uint32_t nq, uint32_t threshold, uint32_t capacity, uint64_t* row_offsets,
                                 std::vector<GatherRow>* rows, uint64_t* query_offsets, uint32_t* assigned, Device& dev) {
-  // every query as gather() checks it; the lowest failing query decides, and the message names it
-  for (uint32_t q = 0; q < nq; q++) {
-    const std::string who = "gather_many: query " + std::to_string(q);
-    if (queries[q]->num != 0) throw Error(kMsg, who + " is a num sketch; only scaled sketches (num == 0) can be gathered");
-    if (any_num) throw Error(kMsg, who + ": the index holds a num sketch; only scaled sketches (num == 0) can be gathered");
-    try {
-      check_sketch(*queries[q]);
-    } catch (const Error& e) {
-      throw Error(e.code, who + ": " + e.message);
-    }
-  }
+  check_queries("gather_many", "can be gathered", queries, nq);
   check_directory_size("gather_many");
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-  hipStream_t s = dev.stream();
-  // the batch as one CSR in device memory: a state that lives in HBM is copied there device to device, the host states go up
-  // in one upload (straight into place when no query lives in HBM)
-  std::vector<uint64_t> qoff((size_t)nq + 1, 0);
-  bool any_abund = false, any_dev = false;
-  uint64_t host_total = 0;
-  for (uint32_t q = 0; q < nq; q++) {
-    const KmerMinHash& Q = *queries[q];
-    Q.flush_pending();
-    const uint64_t lq = Q.dev ? Q.dev->n : Q.mins.size();
-    if (!Q.dev && Q.has_abunds && Q.abunds.size() != lq)
-      throw_internal("gather_many: the abundance vector of query " + std::to_string(q) + " does not match its hashes (quirks Q5/Q6)");
-    if (Q.dev && Q.has_abunds && !Q.dev->has_counts && !Q.dev->has_runs)
-      throw_internal("gather_many: the device state of query " + std::to_string(q) + " carries no abundances");
-    if (lq >= 0xffffffffull) throw_internal("gather_many: a query of 2^32 - 1 or more hashes");
-    qoff[q + 1] = qoff[q] + lq;
-    any_abund |= Q.has_abunds;
-    any_dev |= Q.dev != nullptr;
-    if (!Q.dev) host_total += lq;
-  }
-  const uint64_t total = qoff[nq];
-  const size_t words = any_abund ? 2 : 1;
-  PoolBlock csr(total * 8 * words);
-  uint64_t* d_h = csr.as<uint64_t>();
-  uint64_t* d_a = any_abund ? d_h + total : nullptr;
-  std::unique_ptr<PoolBlock> up;
-  std::vector<uint64_t> stage;
-  if (!any_dev) {
-    stage.resize(total * words);
-    for (uint32_t q = 0; q < nq; q++) {
-      const KmerMinHash& Q = *queries[q];
-      std::copy(Q.mins.begin(), Q.mins.end(), stage.begin() + qoff[q]);
-      if (!any_abund) continue;
-      if (Q.has_abunds) std::copy(Q.abunds.begin(), Q.abunds.end(), stage.begin() + total + qoff[q]);
-      else std::fill(stage.begin() + total + qoff[q], stage.begin() + total + qoff[q + 1], 1ull);
-    }
-    if (total) HIP_CHECK(hipMemcpyAsync(d_h, stage.data(), total * 8 * words, hipMemcpyHostToDevice, s));
-  } else {
-    // host states: [hashes, abundances] of each, one after another
-    stage.reserve(host_total * words);
-    for (uint32_t q = 0; q < nq; q++) {
-      const KmerMinHash& Q = *queries[q];
-      if (Q.dev) continue;
-      stage.insert(stage.end(), Q.mins.begin(), Q.mins.end());
-      if (!any_abund) continue;
-      if (Q.has_abunds) stage.insert(stage.end(), Q.abunds.begin(), Q.abunds.end());
-      else stage.insert(stage.end(), Q.mins.size(), 1ull);
-    }
-    up = std::make_unique<PoolBlock>(stage.size() * 8);
-    if (!stage.empty()) HIP_CHECK(hipMemcpyAsync(up->ptr, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
-    uint64_t at = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-      const KmerMinHash& Q = *queries[q];
-      const uint64_t lq = qoff[q + 1] - qoff[q];
-      if (lq == 0) continue;
-      if (!Q.dev) {
-        HIP_CHECK(hipMemcpyAsync(d_h + qoff[q], up->as<uint64_t>() + at, lq * 8, hipMemcpyDeviceToDevice, s));
-        if (any_abund) HIP_CHECK(hipMemcpyAsync(d_a + qoff[q], up->as<uint64_t>() + at + lq, lq * 8, hipMemcpyDeviceToDevice, s));
-        at += lq * words;
-        continue;
-      }
-      const DeviceSketch& S = *Q.dev;
-      HIP_CHECK(hipMemcpyAsync(d_h + qoff[q], S.uniq.ptr, lq * 8, hipMemcpyDeviceToDevice, s));
-      if (!any_abund) continue;
-      if (Q.has_abunds && S.has_counts) HIP_CHECK(hipMemcpyAsync(d_a + qoff[q], S.counts.ptr, lq * 8, hipMemcpyDeviceToDevice, s));
-      else launch_gather_many_weights(Q.has_abunds ? S.starts.as<uint32_t>() : nullptr, (uint32_t)S.total, (uint32_t)lq, d_a + qoff[q], s);
-    }
-  }
-  HIP_CHECK(hipStreamSynchronize(s));   // (`stage` is read by the upload)
-  csr.synced = true;
-  if (up) up->synced = true;
-  gather_many_dev(d_h, d_a, qoff.data(), nq, threshold, capacity, row_offsets, rows, assigned, dev, s);
-  if (query_offsets) std::copy(qoff.begin(), qoff.end(), query_offsets);
+  const QueryBatch batch(queries, nq, "gather_many", kQueryLimit32, true, dev);
+  gather_many_dev(batch.hashes(), batch.abunds(), batch.offsets(), nq, threshold, capacity, row_offsets, rows, assigned, dev, dev.stream());
+  if (query_offsets) std::copy_n(batch.offsets(), (size_t)nq + 1, query_offsets);
 }
 
 }  // namespace smh

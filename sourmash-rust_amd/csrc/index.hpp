@@ -1,9 +1,11 @@
 // index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
-// similarity on abundances (angular.cpp), matching records (match.cpp), taxonomic LCA (lca.cpp), the thresholded search of a
-// batch (search_many.cpp), clustering (cluster.cpp), collapsing by groups and the read-back (collapse.cpp), building one from
-// records and concatenation (index_build.cpp).  The C boundary (ffi.cpp) only checks pointers and calls in here.
+// similarity on abundances (angular.cpp), matching records (match.cpp), gather of a batch (gather_many.cpp), taxonomic LCA
+// (lca.cpp), the thresholded search of a batch (search_many.cpp), clustering (cluster.cpp) -- the four share query_batch.cpp
+// -- collapsing by groups and the read-back (collapse.cpp), building one from records and concatenation (index_build.cpp).
+// The C boundary (ffi.cpp) only checks pointers and calls in here.
 #pragma once
 #include <functional>
+#include <memory>
 
 #include "minhash.hpp"
 
@@ -113,6 +115,14 @@ struct ResidentIndex {
   void check_directory_size(const char* who) const;
   MatchDirectory ensure_directory(const char* who, Device& dev, hipStream_t s);
   void drop_match_dir();
+  // (query_batch.cpp) What the calls on the directory share in front of their kernels.  check_queries: every query as gather()
+  // checks it -- a num sketch as query, a num sketch in the index, check_sketch -- the lowest failing query decides and the
+  // message names it ("<who>: query q ..."); `can` is the operation's own phrase ("can be gathered").
+  void check_queries(const char* who, const char* can, const KmerMinHash* const* queries, uint32_t n_queries) const;
+  // the search kernels' view of the queries [a, b) of a CSR in device memory (self: SearchSelf); qoff, c and tile_rows are
+  // the caller's blocks
+  SearchChunk search_chunk(const uint64_t* q_hashes_dev, const uint64_t* q_offsets, uint32_t a, uint32_t b, uint32_t metric, double threshold,
+                           uint32_t threshold_common, uint32_t self) const;
   // (gather_many.cpp) Gather of a batch of queries (the rules: include/sourmash_amd.h, smh_index_gather_many).  row_offsets
   // (n_queries + 1), *rows (row_offsets[n_queries] rows) and query_offsets (nullable, n_queries + 1) are written only when
   // the call succeeds; assigned (nullable, the queries' positions one after another) is filled chunk by chunk, after every
@@ -205,6 +215,35 @@ void fetch_rows(const void* d_rows, void* out, size_t n, Engine& E, hipStream_t 
 void lca_check_taxonomy(const uint32_t* parent, uint32_t n_taxa, const uint32_t* node_taxon, uint32_t n_nodes, uint32_t index_len);
 constexpr uint64_t kLcaBudget = 1ull << 26;
 extern uint64_t g_lca_budget;
+
+// query_batch.cpp: a batch of sketches as one CSR in device memory ("Staging a batch"), for the length of one
+// call.  A state that lives in HBM is copied there device to device and is not brought to the host; the host states go up in
+// one upload, straight into place when no query lives in HBM.  limit: kQueryLimit32 or kQueryLimit31, what one query may not
+// reach.  want_abunds: the abundances behind the hashes when any query tracks them (a query that does not weighs 1 per hash).
+// The caller holds the device's lock.  The constructor flushes every query's pending records and returns with the stream
+// waited for; its refusals (kInternal, the message begins with `who`) come before anything is allocated.
+constexpr uint64_t kQueryLimit32 = 0xffffffffull, kQueryLimit31 = 1ull << 31;
+struct QueryBatch {
+  QueryBatch(const KmerMinHash* const* queries, uint32_t n_queries, const char* who, uint64_t limit, bool want_abunds, Device& dev);
+  const uint64_t* hashes() const { return csr->as<uint64_t>(); }
+  const uint64_t* abunds() const { return with_abunds ? csr->as<uint64_t>() + qoff.back() : nullptr; }   // null: every hash weighs 1
+  const uint64_t* offsets() const { return qoff.data(); }   // n_queries + 1, from 0
+ private:
+  std::unique_ptr<PoolBlock> csr, up;   // [hashes | abundances]; the host states on their way there when a query lives in HBM
+  std::vector<uint64_t> qoff;
+  bool with_abunds = false;
+};
+// the refusals of a CSR's offsets: "offsets must ascend (query q)" (kMsg), a query of `limit` or more hashes (kInternal)
+void check_query_offsets(const char* who, const uint64_t* q_offsets, uint32_t n_queries, uint64_t limit);
+// The u32 offsets a chunk's kernels read, those of the queries [a, b) relative to query a (b - a + 1 entries): appended to
+// `rel` (returns where they start), or `rel` rewritten with them and uploaded to `dst`.  The upload reads `rel`
+// asynchronously: the caller waits for the stream before the next chunk rewrites it (who cannot lays all chunks out first
+// and uploads once, as cluster does).
+size_t append_chunk_offsets(const uint64_t* q_offsets, uint32_t a, uint32_t b, std::vector<uint32_t>* rel);
+void upload_chunk_offsets(const uint64_t* q_offsets, uint32_t a, uint32_t b, std::vector<uint32_t>* rel, uint32_t* dst, hipStream_t s);
+// the front half of a search chunk: c zeroed, the probe, the select, and the chunk's row count read back (the stream has been
+// waited for when it returns)
+uint32_t search_chunk_rows(const MatchDirectory& dir, const SearchChunk& ck, Device& dev, hipStream_t s);
 
 // gather_many.cpp: the (query, node) counters one chunk of a batch may hold (three u32 arrays of that size: 768 MiB at the
 // default) -- a memory cap, not a measured optimum.  gather_many_chunk_end: the chunk that starts at query `a` ends in front

@@ -1,6 +1,6 @@
 // lca.cpp -- taxonomic LCA on a resident index (the rules are in include/sourmash_amd.h, "Taxonomic LCA"):
 // the taxonomy's checks and its copy, the upload and the per-hash table kept beside the hash directory, the sketch route
-// (staging, chunks cut at query boundaries, per chunk the probe, the compaction, the sort and the run-length pass) and the
+// (query_batch.cpp's staging, chunks cut at query boundaries, per chunk the probe, the compaction, the sort and the run-length pass) and the
 // records route (match's front half, then the fold of the join per record).  The kernels are in lca_kernels.hip.
 #include <algorithm>
 #include <memory>
@@ -80,10 +80,7 @@ void ResidentIndex::check_lca_sketches(const char* who) const {
 void ResidentIndex::lca_many_dev(const uint64_t* qh, const uint64_t* qoff, uint32_t nq, uint64_t* count_offsets, std::vector<uint32_t>* taxa_out,
                                  std::vector<uint64_t>* counts_out, uint32_t* hash_taxon, Device& dev, hipStream_t s) {
   check_lca_sketches("lca_many");
-  for (uint32_t q = 0; q < nq; q++) {
-    if (qoff[q + 1] < qoff[q]) throw Error(kMsg, "lca_many: offsets must ascend (query " + std::to_string(q) + ")");
-    if (qoff[q + 1] - qoff[q] >= (1ull << 31)) throw_internal("lca_many: a query of 2^31 or more hashes");
-  }
+  check_query_offsets("lca_many", qoff, nq, kQueryLimit31);
   check_directory_size("lca_many");
   const uint64_t total = nq ? qoff[nq] - qoff[0] : 0, base0 = nq ? qoff[0] : 0;
   std::vector<uint64_t> coff((size_t)nq + 1, 0);
@@ -115,9 +112,7 @@ void ResidentIndex::lca_many_dev(const uint64_t* qh, const uint64_t* qoff, uint3
     for (uint32_t q = a; q < b; q++) coff[q + 1] = coff[q];
     if (T == 0) continue;
     PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_tax((size_t)T * 4), d_key((size_t)T * 8), d_flag(((size_t)T + 1) * 4);
-    rel.resize((size_t)Qc + 1);
-    for (uint32_t k = 0; k <= Qc; k++) rel[k] = (uint32_t)(qoff[a + k] - qoff[a]);
-    HIP_CHECK(hipMemcpyAsync(d_qoff.ptr, rel.data(), ((size_t)Qc + 1) * 4, hipMemcpyHostToDevice, s));
+    upload_chunk_offsets(qoff, a, b, &rel, d_qoff.as<uint32_t>(), s);
     launch_lca_probe(dir, L.hash_taxon, qh + qoff[a], d_qoff.as<uint32_t>(), Qc, T, d_tax.as<uint32_t>(), d_key.as<uint64_t>(),
                      d_flag.as<uint32_t>(), dev, s);
     if (hash_taxon) HIP_CHECK(hipMemcpyAsync(hash_taxon + (qoff[a] - base0), d_tax.ptr, (size_t)T * 4, hipMemcpyDeviceToHost, s));
@@ -156,53 +151,12 @@ void ResidentIndex::lca_many_dev(const uint64_t* qh, const uint64_t* qoff, uint3
 void ResidentIndex::lca_many(const KmerMinHash* const* queries, uint32_t nq, uint64_t* count_offsets, std::vector<uint32_t>* taxa,
                              std::vector<uint64_t>* counts, uint64_t* query_offsets, uint32_t* hash_taxon, Device& dev) {
   check_lca_sketches("lca_many");
-  // every query as gather_many checks it; the lowest failing query decides, and the message names it
-  for (uint32_t q = 0; q < nq; q++) {
-    const std::string who = "lca_many: query " + std::to_string(q);
-    if (queries[q]->num != 0) throw Error(kMsg, who + " is a num sketch; only scaled sketches (num == 0) have lca counts");
-    try {
-      check_sketch(*queries[q]);
-    } catch (const Error& e) {
-      throw Error(e.code, who + ": " + e.message);
-    }
-  }
+  check_queries("lca_many", "have lca counts", queries, nq);   // (the index holds no num sketch: check_lca_sketches)
   check_directory_size("lca_many");
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-  hipStream_t s = dev.stream();
-  // the batch as one CSR in device memory: a state that lives in HBM is copied there device to device, the host states go up
-  // in one upload
-  std::vector<uint64_t> qoff((size_t)nq + 1, 0);
-  for (uint32_t q = 0; q < nq; q++) {
-    const KmerMinHash& Q = *queries[q];
-    Q.flush_pending();
-    const uint64_t lq = Q.dev ? Q.dev->n : Q.mins.size();
-    if (lq >= (1ull << 31)) throw_internal("lca_many: a query of 2^31 or more hashes");
-    qoff[q + 1] = qoff[q] + lq;
-  }
-  const uint64_t total = qoff[nq];
-  PoolBlock csr(total * 8);
-  uint64_t* d_h = csr.as<uint64_t>();
-  std::vector<uint64_t> stage;
-  std::vector<uint64_t> stage_at((size_t)nq, 0);
-  for (uint32_t q = 0; q < nq; q++) {
-    const KmerMinHash& Q = *queries[q];
-    if (Q.dev) continue;
-    stage_at[q] = stage.size();
-    stage.insert(stage.end(), Q.mins.begin(), Q.mins.end());
-  }
-  PoolBlock up(stage.size() * 8);
-  if (!stage.empty()) HIP_CHECK(hipMemcpyAsync(up.ptr, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
-  for (uint32_t q = 0; q < nq; q++) {
-    const KmerMinHash& Q = *queries[q];
-    const uint64_t lq = qoff[q + 1] - qoff[q];
-    if (lq == 0) continue;
-    const void* src = Q.dev ? Q.dev->uniq.ptr : (const void*)(up.as<uint64_t>() + stage_at[q]);
-    HIP_CHECK(hipMemcpyAsync(d_h + qoff[q], src, lq * 8, hipMemcpyDeviceToDevice, s));
-  }
-  HIP_CHECK(hipStreamSynchronize(s));   // (`stage` is read by the upload)
-  csr.synced = up.synced = true;
-  lca_many_dev(d_h, qoff.data(), nq, count_offsets, taxa, counts, hash_taxon, dev, s);
-  if (query_offsets) std::copy(qoff.begin(), qoff.end(), query_offsets);
+  const QueryBatch batch(queries, nq, "lca_many", kQueryLimit31, false, dev);
+  lca_many_dev(batch.hashes(), batch.offsets(), nq, count_offsets, taxa, counts, hash_taxon, dev, dev.stream());
+  if (query_offsets) std::copy_n(batch.offsets(), (size_t)nq + 1, query_offsets);
 }
 
 void ResidentIndex::lca_records(const uint8_t* seq_dev, uint64_t total_len, const uint64_t* off, uint32_t nrec, LcaRow* rows, hipStream_t s) {

@@ -1,12 +1,11 @@
 // search_many.cpp -- ResidentIndex::search_many / search_self (the rules are in include/sourmash_amd.h,
-// smh_index_search_many): the checks of every query, the staging of a batch of sketches into one CSR in device memory, the
-// chunks cut at query boundaries, and per chunk the probe, the select, the sizing read-back, the emit and the rows' way into
-// the caller's array.  The kernels are in search_many_kernels.hip; the hash directory is the index's (index.cpp), shared with
-// match, gather_many and the LCA.
+// smh_index_search_many): the chunks cut at query boundaries, and per chunk the emit and the rows' way into the caller's
+// array.  The checks of every query, the staging of a batch of sketches into one CSR in device memory and a chunk's front half
+// (the probe, the select, the sizing read-back) are query_batch.cpp's.  The kernels are in search_many_kernels.hip; the hash
+// directory is the index's (index.cpp), shared with match, gather_many and the LCA.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <memory>
 #include <string>
 
 #include "index.hpp"
@@ -48,10 +47,7 @@ SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qo
   check_search(metric, threshold);
   if (any_num) throw Error(kMsg, "search_many: the index holds a num sketch; only scaled sketches (num == 0) can be searched");
   if (threshold_common == 0) threshold_common = 1;
-  for (uint32_t q = 0; q < nq; q++) {
-    if (qoff[q + 1] < qoff[q]) throw Error(kMsg, "search_many: offsets must ascend (query " + std::to_string(q) + ")");
-    if (qoff[q + 1] - qoff[q] >= 0xffffffffull) throw_internal("search_many: a query of 2^32 - 1 or more hashes");
-  }
+  check_query_offsets("search_many", qoff, nq, kQueryLimit32);
   check_directory_size("search_many");
   if (n > 0xffffffffu - 2 * kSearchTile) throw_internal("search_many: too many nodes");
   const uint64_t total = nq ? qoff[nq] - qoff[0] : 0;
@@ -78,27 +74,13 @@ SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qo
     for (uint32_t q = a; q < b; q++) roff[q + 1] = base;
     dev.count("search_many_chunk");
     if (T == 0) continue;
-    const size_t pairs = (size_t)Qc * n, cells = (size_t)Qc * tiles;
-    PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_c(pairs * 4), d_tiles((cells + 1) * 4), d_qrows((size_t)Qc * 4);
-    SearchChunk ck;
-    ck.hashes = qh + qoff[a];
+    PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_c((size_t)Qc * n * 4), d_tiles(((size_t)Qc * tiles + 1) * 4), d_qrows((size_t)Qc * 4);
+    SearchChunk ck = search_chunk(qh, qoff, a, b, metric, threshold, threshold_common, self);
     ck.qoff = d_qoff.as<uint32_t>();
-    ck.nq = Qc; ck.T = (uint32_t)T; ck.n = n;
-    ck.q0 = self ? a : 0;
     ck.c = d_c.as<uint32_t>();
     ck.tile_rows = d_tiles.as<uint32_t>();
-    ck.tiles = tiles;
-    ck.node_offsets = offsets.as<uint64_t>();
-    ck.metric = metric; ck.self = self; ck.threshold_common = threshold_common; ck.threshold = threshold;
-    rel.resize((size_t)Qc + 1);
-    for (uint32_t k = 0; k <= Qc; k++) rel[k] = (uint32_t)(qoff[a + k] - qoff[a]);
-    HIP_CHECK(hipMemcpyAsync(d_qoff.ptr, rel.data(), ((size_t)Qc + 1) * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemsetAsync(ck.c, 0, pairs * 4, s));
-    launch_search_many_probe(dir, ck, dev, s);
-    launch_search_many_select(ck, dev, s);
-    uint32_t R = 0;
-    HIP_CHECK(hipMemcpyAsync(&R, ck.tile_rows + cells, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    upload_chunk_offsets(qoff, a, b, &rel, d_qoff.as<uint32_t>(), s);
+    const uint32_t R = search_chunk_rows(dir, ck, dev, s);
     d_qoff.synced = d_c.synced = d_tiles.synced = d_qrows.synced = true;
     if (R == 0) continue;
     SearchRow* dst = out.room(R);   // (before the device rows: a refusal leaves only blocks that go back by themselves)
@@ -119,60 +101,11 @@ SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qo
 SearchRow* ResidentIndex::search_many(const KmerMinHash* const* queries, uint32_t nq, uint32_t metric, double threshold,
                                       uint32_t threshold_common, uint64_t* row_offsets, Device& dev) {
   check_search(metric, threshold);
-  // every query as gather_many checks it; the lowest failing query decides, and the message names it
-  for (uint32_t q = 0; q < nq; q++) {
-    const std::string who = "search_many: query " + std::to_string(q);
-    if (queries[q]->num != 0) throw Error(kMsg, who + " is a num sketch; only scaled sketches (num == 0) can be searched");
-    if (any_num) throw Error(kMsg, who + ": the index holds a num sketch; only scaled sketches (num == 0) can be searched");
-    try {
-      check_sketch(*queries[q]);
-    } catch (const Error& e) {
-      throw Error(e.code, who + ": " + e.message);
-    }
-  }
+  check_queries("search_many", "can be searched", queries, nq);
   check_directory_size("search_many");
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-  hipStream_t s = dev.stream();
-  // the batch as one CSR in device memory: a state that lives in HBM is copied there device to device, the host states go up
-  // in one upload (straight into place when no query lives in HBM)
-  std::vector<uint64_t> qoff((size_t)nq + 1, 0);
-  bool any_dev = false;
-  uint64_t host_total = 0;
-  for (uint32_t q = 0; q < nq; q++) {
-    const KmerMinHash& Q = *queries[q];
-    Q.flush_pending();
-    const uint64_t lq = Q.dev ? Q.dev->n : Q.mins.size();
-    if (lq >= 0xffffffffull) throw_internal("search_many: a query of 2^32 - 1 or more hashes");
-    qoff[q + 1] = qoff[q] + lq;
-    any_dev |= Q.dev != nullptr;
-    if (!Q.dev) host_total += lq;
-  }
-  const uint64_t total = qoff[nq];
-  PoolBlock csr(total * 8);
-  uint64_t* d_h = csr.as<uint64_t>();
-  std::unique_ptr<PoolBlock> up;
-  std::vector<uint64_t> stage;
-  stage.reserve(host_total);
-  for (uint32_t q = 0; q < nq; q++)
-    if (!queries[q]->dev) stage.insert(stage.end(), queries[q]->mins.begin(), queries[q]->mins.end());
-  if (!any_dev) {
-    if (total) HIP_CHECK(hipMemcpyAsync(d_h, stage.data(), total * 8, hipMemcpyHostToDevice, s));
-  } else {
-    up = std::make_unique<PoolBlock>(stage.size() * 8);
-    if (!stage.empty()) HIP_CHECK(hipMemcpyAsync(up->ptr, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
-    uint64_t at = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-      const KmerMinHash& Q = *queries[q];
-      const uint64_t lq = qoff[q + 1] - qoff[q];
-      if (lq == 0) continue;
-      HIP_CHECK(hipMemcpyAsync(d_h + qoff[q], Q.dev ? Q.dev->uniq.ptr : (void*)(up->as<uint64_t>() + at), lq * 8, hipMemcpyDeviceToDevice, s));
-      if (!Q.dev) at += lq;
-    }
-  }
-  HIP_CHECK(hipStreamSynchronize(s));   // (`stage` is read by the upload)
-  csr.synced = true;
-  if (up) up->synced = true;
-  return search_many_dev(d_h, qoff.data(), nq, metric, threshold, threshold_common, kSearchNotSelf, row_offsets, dev, s);
+  const QueryBatch batch(queries, nq, "search_many", kQueryLimit32, false, dev);
+  return search_many_dev(batch.hashes(), batch.offsets(), nq, metric, threshold, threshold_common, kSearchNotSelf, row_offsets, dev, dev.stream());
 }
 
 SearchRow* ResidentIndex::search_self(uint32_t metric, double threshold, uint32_t threshold_common, bool upper_only, uint64_t* row_offsets,

@@ -373,6 +373,15 @@ class ResidentIndex:
         common = min(qmx, lo) if len(self) else qmx
         return self._at(common), query if qmx == common else query.downsample_max_hash(common)
 
+    def _meet_groups(self, queries):
+        """the queries grouped by the index at which each meets this one: (index, positions in `queries`, the cut queries)"""
+        met = [self._meet_sketch(q) for q in queries]
+        groups = {}
+        for k, (idx, _) in enumerate(met):
+            groups.setdefault(id(idx), (idx, []))[1].append(k)
+        for idx, members in groups.values():
+            yield idx, members, [met[k][1] for k in members]
+
     def _meet_index(self, other):
         if other is self:
             lo, _ = self._scaled_range("the index")
@@ -435,14 +444,9 @@ class ResidentIndex:
         the index; every group is one call."""
         queries = list(queries)
         if downsample:
-            met = [self._meet_sketch(q) for q in queries]
-            groups = {}
-            for k, (idx, _) in enumerate(met):
-                groups.setdefault(id(idx), (idx, []))[1].append(k)
             out = [None] * len(queries)
-            for idx, members in groups.values():
-                got = idx.gather_many([met[k][1] for k in members], threshold_bp, scaled, max_rows, abund_stats)
-                for k, res in zip(members, got):
+            for idx, members, cut in self._meet_groups(queries):
+                for k, res in zip(members, idx.gather_many(cut, threshold_bp, scaled, max_rows, abund_stats)):
                     out[k] = res
             return out
         nqs = len(queries)
@@ -501,13 +505,9 @@ class ResidentIndex:
         max_hash at which each meets the index; every group is one call, and the sizes are those of the cut sketches."""
         queries = list(queries)
         if downsample:
-            met = [self._meet_sketch(q) for q in queries]
-            groups = {}
-            for k, (idx, _) in enumerate(met):
-                groups.setdefault(id(idx), (idx, []))[1].append(k)
             parts = {}
-            for idx, members in groups.values():
-                got = idx.search_many([met[k][1] for k in members], threshold, metric, threshold_bp, scaled)
+            for idx, members, cut in self._meet_groups(queries):
+                got = idx.search_many(cut, threshold, metric, threshold_bp, scaled)
                 for j, k in enumerate(members):
                     parts[k] = (got, got.rows_of(j))
             offsets = np.zeros(len(queries) + 1, dtype=np.uint64)
@@ -795,13 +795,9 @@ class ResidentIndex:
         at which each meets the index, every group is one call; per_hash then runs over the hashes of the cut query."""
         queries = list(queries)
         if downsample:
-            met = [self._meet_sketch(q) for q in queries]
-            groups = {}
-            for k, (idx, _) in enumerate(met):
-                groups.setdefault(id(idx), (idx, []))[1].append(k)
             out = [None] * len(queries)
-            for idx, members in groups.values():
-                for k, res in zip(members, idx.lca_counts([met[k][1] for k in members], hash_taxon)):
+            for idx, members, cut in self._meet_groups(queries):
+                for k, res in zip(members, idx.lca_counts(cut, hash_taxon)):
                     out[k] = res
             return out
         nqs = len(queries)
