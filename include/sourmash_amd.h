@@ -579,6 +579,66 @@ void smh_index_build_set_budget(uint64_t candidates);
 uint64_t smh_index_build_budget(void);
 void smh_index_build_geometry(uint32_t *tile_elems, uint32_t *threads);
 
+/* Filtering an index: a new resident index that holds a subset of each node of its parent -- `sig subtract`, `sig intersect`
+ * against a mask, `sig inflate`, `sig filter` (an abundance window), `sig flatten`, the hashes held by exactly one / at most x
+ * / at least x nodes -- and a new index that holds a subset of the parent's nodes, both made on the device.
+ * The reference crate has no counterpart, so the rules are fixed here; restated in tests/filter_restatement.py.  They are all
+ * integers: results are EQUAL, never close.
+ * smh_index_filter  The child has the parent's n nodes, in order, with the parent's parameters.  Node i of the child holds,
+ *              ascending, the hashes h of parent node i for which ALL three conditions hold.  Each condition is evaluated on
+ *              the PARENT: the conditions do not see each other's effect.
+ *   Operand    SMH_FILTER_KEEP_IN: h is in the operand.  SMH_FILTER_DROP_IN: h is not in the operand.
+ *              SMH_FILTER_OPERAND_NONE: always true; the operand may then be NULL and is not looked at.
+ *   Abundance  min_abund <= a <= max_abund, a the node's own abundance of h.  0, 0xffffffff: no window.
+ *   Owners     min_owners <= owners(h) <= max_owners, owners(h) the number of parent nodes that hold h: the length of h's
+ *              owner list in the hash directory.  min_owners 0 or 1 with max_owners 0xffffffff: no window.  max_owners = 1
+ *              gives every node its private hashes, min_owners = 2 the shared ones.  The directory is built (counter
+ *              "match_directory_built") ONLY when this window is not trivial and the index holds a hash.
+ *   Abundances of the child.  SMH_FILTER_ABUND_OWN: the parent's, for the kept hashes; the child has abundances iff the parent
+ *              has.  SMH_FILTER_ABUND_FLAT: none.  SMH_FILTER_ABUND_OPERAND: the operand's abundance of h (`sig inflate`); it
+ *              needs KEEP_IN and an operand that tracks abundances.
+ *   Result     carries the parent's taxonomy (same nodes, same order), no compare dictionary and no hash directory of its
+ *              own; its abundances, when it has them, are resident in HBM.  It is an index like any other.
+ *   Refused    with SOURMASH_ERROR_CODE_MSG and a message that begins with "filter:" -- except an operand incompatible with
+ *              the nodes, which is 101-104 as smh_check_compatible reports them -- NULL is returned, and every refusal is
+ *              decided before anything is built: rule NULL; an unknown operand_mode or abund_out; min > max in either
+ *              window; OPERAND without KEEP_IN (these before the index or the device is looked at); index NULL; a node that
+ *              is not a scaled sketch; operand NULL when operand_mode is not NONE; an operand that is not a scaled sketch;
+ *              OPERAND with an operand that tracks no abundances; an abundance window on an index for which
+ *              smh_index_has_abundances is false; abundances involved (an abundance window, or OWN on an index with
+ *              abundances) and a node holding an abundance of 2^32 or more -- the message names the node; OPERAND with an
+ *              operand abundance of 2^32 or more, or whose abundance vector does not match its hashes; an owner window on
+ *              an index of 2^31 or more hashes (the directory's own refusal); an operand of 2^31 or more hashes.
+ *   Empty      an empty index, empty nodes, an empty operand, a rule that keeps nothing: zero-length nodes, no error.
+ *   Device     an operand whose state lives in HBM is read there ("sketch_to_host" does not move), a host operand goes up in
+ *              one upload.  Parent abundances still on the host are uploaded for the call, those in HBM are read in place.
+ *              A flag pass gives every resident hash its verdict -- the operand and the directory are searched per hash,
+ *              their sampled tops in LDS -- as one bit, and counts the survivors per tile of `tile` hashes; the counts are
+ *              scanned 64 bits wide (an index promises no total below 2^32); one lane per node finds its new offset; an emit
+ *              pass writes the survivors in order.  Under OPERAND the emit pass searches the operand again for the survivors
+ *              (no position is stored per hash).  8 (n + 1) bytes of offsets come to the host; nothing proportional to the
+ *              hashes does.  Work space, from the block pool and returned: 256 B of mask per tile (one bit per hash, rounded
+ *              up to whole tiles) and 8 B per tile + 8; 4 B per hash more when the parent's abundances are uploaded.
+ * smh_index_select  Node j of the child is node ids[j] of the parent, whole: any order, repeats allowed, n_ids may be 0.  It
+ *              works on ANY index, num sketches included: it only copies, device to device.  Carried: the per-node
+ *              parameters and nums, the abundances wherever the parent has them (host or HBM), the taxonomy (the same
+ *              parents, the nodes' taxa permuted).  Refused (MSG, "select:"): index NULL; ids NULL with n_ids > 0; an
+ *              id >= n -- the message names its position.
+ * smh_filter_geometry  tile: the hashes one workgroup trip of the flag and emit passes takes; operand_samples: the sampled
+ *              top of the operand the search keeps in LDS (an operand up to that size is searched in LDS alone); threads:
+ *              the workgroup's size (tests, tools).
+ * Timers under smh_profile_get: "filter_flag", "filter_emit"; event counters: "index_filtered", "index_selected". */
+enum { SMH_FILTER_OPERAND_NONE = 0, SMH_FILTER_KEEP_IN = 1, SMH_FILTER_DROP_IN = 2 };
+enum { SMH_FILTER_ABUND_OWN = 0, SMH_FILTER_ABUND_FLAT = 1, SMH_FILTER_ABUND_OPERAND = 2 };
+typedef struct SmhFilter {
+  uint32_t operand_mode, abund_out;
+  uint32_t min_abund, max_abund;     /* 0, 0xffffffff: no window */
+  uint32_t min_owners, max_owners;   /* 0 or 1, 0xffffffff: no window */
+} SmhFilter;
+SmhIndex *smh_index_filter(SmhIndex *index, const KmerMinHash *operand, const SmhFilter *rule);
+SmhIndex *smh_index_select(SmhIndex *index, const uint32_t *ids, uint32_t n_ids);
+void smh_filter_geometry(uint32_t *tile, uint32_t *operand_samples, uint32_t *threads);
+
 /* Angular similarity on abundances: what `sourmash compare` and `sourmash search` report by default for sketches that
  * track abundances.  The reference crate has no weighted compare, so the rules are fixed here -- DESIGN.md 3.10, restated
  * in tests/angular_restatement.py.  For two sketches A and B that both track abundances, hashes ascending and distinct, one
@@ -975,10 +1035,12 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * diagonal, a union per survivor), "cluster_finish" (labels, representatives and the numbering), "cluster_round" (one entry
  * per greedy round), "cluster_assign" (the members' choice), "collapse_count" / "collapse_emit" (the two folds of the
  * directory's owner lists through the groups, three launches each), "collapse_partition" (the survivors sorted by group and
- * the groups' bounds among them), "collapse_finish" (the child's hashes and abundances from the partitioned survivors).  Event counters under the same call: "gather_many_chunk",
+ * the groups' bounds among them), "collapse_finish" (the child's hashes and abundances from the partitioned survivors),
+ * "filter_flag" (a filter's verdict per resident hash and the survivors per tile), "filter_emit" (its survivors written in
+ * order).  Event counters under the same call: "gather_many_chunk",
  * "search_many_chunk", "cluster_chunk" (chunks run), "cluster_round" (greedy rounds launched; with the timers enabled their
- * entries are that count), "match_directory_built", "index_collapsed", "grid_capped" (launches whose grid smh_set_grid_cap
- * lowered). */
+ * entries are that count), "match_directory_built", "index_collapsed", "index_filtered", "index_selected", "grid_capped"
+ * (launches whose grid smh_set_grid_cap lowered). */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

@@ -50,6 +50,11 @@ class SmhLcaRow(C.Structure):
                 ("taxon", C.c_uint32), ("status", C.c_uint32)]
 
 
+class SmhFilter(C.Structure):
+    _fields_ = [("operand_mode", C.c_uint32), ("abund_out", C.c_uint32), ("min_abund", C.c_uint32), ("max_abund", C.c_uint32),
+                ("min_owners", C.c_uint32), ("max_owners", C.c_uint32)]
+
+
 def build(force=False):
     """Compile the HIP/C++ sources in-tree (hipcc --offload-arch=gfx950)."""
     src = os.path.join(HERE, "csrc")
@@ -201,6 +206,9 @@ _SIGS = {
     "smh_index_build_set_budget": (None, [C.c_uint64]),
     "smh_index_build_budget": (C.c_uint64, []),
     "smh_index_build_geometry": (None, [u32p, u32p]),
+    "smh_index_filter": (C.c_void_p, [C.c_void_p, C.c_void_p, C.POINTER(SmhFilter)]),
+    "smh_index_select": (C.c_void_p, [C.c_void_p, u32p, C.c_uint32]),
+    "smh_filter_geometry": (None, [u32p, u32p, u32p]),
     "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
     "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
     "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),

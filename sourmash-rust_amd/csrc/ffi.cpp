@@ -946,6 +946,33 @@ void smh_index_build_set_budget(uint64_t candidates) { smh::g_index_build_budget
 uint64_t smh_index_build_budget(void) { return smh::g_index_build_budget; }
 void smh_index_build_geometry(uint32_t* tile_elems, uint32_t* threads) { smh::index_build_geometry(tile_elems, threads); }
 
+// ------------------------------------------------------------------ filtering an index, taking a subset of its nodes (filter.cpp)
+
+static_assert(SMH_FILTER_OPERAND_NONE == smh::kFilterOperandNone && SMH_FILTER_KEEP_IN == smh::kFilterKeepIn &&
+              SMH_FILTER_DROP_IN == smh::kFilterDropIn && SMH_FILTER_ABUND_OWN == smh::kFilterAbundOwn &&
+              SMH_FILTER_ABUND_FLAT == smh::kFilterAbundFlat && SMH_FILTER_ABUND_OPERAND == smh::kFilterAbundOperand,
+              "the modes of the header are filter's");
+static_assert(sizeof(SmhFilter) == 24 && sizeof(smh::FilterRule) == sizeof(SmhFilter), "SmhFilter is FilterRule: six u32");
+
+SmhIndex* smh_index_filter(SmhIndex* index, const KmerMinHash* operand, const SmhFilter* rule) {
+  return pad<SmhIndex*>([&] {
+    // the rule's own refusals before the index or the device is looked at: they need neither
+    smh::check_filter_rule(reinterpret_cast<const smh::FilterRule*>(rule));
+    (void)smh::Device::get();
+    if (!index) throw Error(smh::kMsg, "filter: index is NULL");   // (MSG like every refusal of this call)
+    const smh::FilterRule r{rule->operand_mode, rule->abund_out, rule->min_abund, rule->max_abund, rule->min_owners, rule->max_owners};
+    return new SmhIndex(*index, operand, r);
+  });
+}
+SmhIndex* smh_index_select(SmhIndex* index, const uint32_t* ids, uint32_t n_ids) {
+  return pad<SmhIndex*>([&] {
+    (void)smh::Device::get();
+    if (!index) throw Error(smh::kMsg, "select: index is NULL");
+    return new SmhIndex(*index, ids, n_ids);
+  });
+}
+void smh_filter_geometry(uint32_t* tile, uint32_t* operand_samples, uint32_t* threads) { smh::filter_geometry(tile, operand_samples, threads); }
+
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {
   return pad_code([&] { require(rows, "rows"); require(cols, "cols"); rows->compare(*cols, jaccard, common, size, count_common, containment); });

@@ -1,7 +1,8 @@
 // index.hpp -- a set of sketches resident in HBM and what is asked of it: block compares and gather (index.cpp), angular
 // similarity on abundances (angular.cpp), matching records (match.cpp), gather of a batch (gather_many.cpp), taxonomic LCA
 // (lca.cpp), the thresholded search of a batch (search_many.cpp), clustering (cluster.cpp) -- the four share query_batch.cpp
-// -- collapsing by groups and the read-back (collapse.cpp), building one from records and concatenation (index_build.cpp).
+// -- collapsing by groups and the read-back (collapse.cpp), building one from records and concatenation (index_build.cpp),
+// filtering its nodes and taking a subset of them (filter.cpp).
 // The C boundary (ffi.cpp) only checks pointers and calls in here.
 #pragma once
 #include <functional>
@@ -59,6 +60,18 @@ struct ResidentIndex {
   // (index_build.cpp) The nodes of parts[0], then parts[1], ...: device-to-device copies, offsets rebased, no taxonomy,
   // dictionary or directory carried over.  The result owns its memory.
   ResidentIndex(ResidentIndex* const* parts, uint32_t n_parts);
+  // (filter.cpp) The parent filtered (the rules: include/sourmash_amd.h, "Filtering an index"): the parent's nodes, in order and
+  // with its parameters and taxonomy, each holding the hashes of the parent's node that pass the rule -- a verdict per
+  // resident hash and an ordered compaction, made on the device.  operand: nullable under kFilterOperandNone; read where it
+  // lives (a state in HBM is not brought to the host).  check_filter is run first, and the refusals that need the operand's
+  // state (its abundances of 2^32 or more) come before anything is built.  8 (n + 1) bytes of offsets come to the host.  No
+  // dictionary or directory is carried; the child's abundances, when it has them, are resident in HBM.
+  ResidentIndex(ResidentIndex& parent, const KmerMinHash* operand, const FilterRule& rule);
+  // (filter.cpp) Node j of the new index is node ids[j] of the parent, whole: any order, repeats allowed, n_ids may be 0.  Works on
+  // every index (it only copies: device to device, balanced over the output by downsample_copy).  Carries the per-node
+  // parameters and nums, the abundances wherever the parent has them (host or HBM), wide_pos / wide_node remapped and the
+  // taxonomy with node_taxon permuted.  An id >= parent.n is refused (kMsg, the message names its position).
+  ResidentIndex(ResidentIndex& parent, const uint32_t* ids, uint32_t n_ids);
   ~ResidentIndex();
   void enroll();   // into the registry of live indexes: the last step of every constructor
   // (collapse.cpp) the index as it is held: offsets (n + 1, from 0), hashes and abundances (offsets[n] each); any may be null.
@@ -288,6 +301,13 @@ extern uint64_t g_index_build_budget;
 void check_index_build(const KmerMinHash* like, int input, bool have_seq, uint64_t total_len, const uint64_t* offsets, const uint32_t* groups,
                        uint32_t n_records, uint32_t n_groups);
 void check_index_concat(ResidentIndex* const* parts, uint32_t n_parts);
+
+// filter.cpp: every refusal of a filter that needs no device (kMsg, the message begins with "filter:"; an operand that is
+// incompatible with the nodes: 101-104 from check_sketch).  check_filter_rule: those of the rule alone (a null rule, an unknown
+// mode, min > max, OPERAND without KEEP_IN), for callers that have no index yet; check_filter runs it first.
+void check_filter_rule(const FilterRule* rule);
+void check_filter(const ResidentIndex& index, const KmerMinHash* operand, const FilterRule* rule);
+void check_index_select(const ResidentIndex& index, const uint32_t* ids, uint32_t n_ids);
 
 // downsample.cpp (the rules are in include/sourmash_amd.h, "Downsampling").  `out` is a fresh sketch: it
 // receives src's parameters with max_hash / num replaced and the kept prefix.  A state that lives in HBM is cut there into a

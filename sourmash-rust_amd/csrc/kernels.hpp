@@ -1,7 +1,7 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
 // gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip, collapse_kernels.hip,
-// index_build_kernels.hip).
+// index_build_kernels.hip, filter_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -625,5 +625,44 @@ void launch_index_build_finish(const uint64_t* run_pack, uint32_t n_runs, uint32
                                hipStream_t s);
 // dst[i] = src[i] + delta for i < n (the offsets of a part of a concatenation; delta wraps like the subtraction it stands for)
 void launch_index_build_rebase(const uint64_t* src, uint64_t n, uint64_t delta, uint64_t* dst, hipStream_t s);
+
+// --- filter_kernels.hip ----------------------------------------------------------------
+// Filtering a resident index (the rules are in include/sourmash_amd.h, "Filtering an index"): a verdict per
+// resident hash, then an ordered compaction per node.  Element t of the index is hashes[t] (the caller passes the CSR from
+// offsets[0] on); a tile is kFilterTile consecutive elements and may span any number of nodes.
+enum FilterOperand : uint32_t { kFilterOperandNone = 0, kFilterKeepIn = 1, kFilterDropIn = 2 };
+enum FilterAbund : uint32_t { kFilterAbundOwn = 0, kFilterAbundFlat = 1, kFilterAbundOperand = 2 };
+constexpr uint32_t kFilterTile = 2048;        // elements per workgroup trip of the flag and emit passes (256 threads, 8 each)
+constexpr uint32_t kFilterThreads = 256;
+constexpr uint32_t kFilterSamples = 2048;     // sampled top of the operand's hashes: 16 KiB of LDS per workgroup
+constexpr uint32_t kFilterWords = kFilterTile / 64;   // mask words of a tile: one per wave and step
+struct FilterRule {                           // SmhFilter
+  uint32_t operand_mode, abund_out, min_abund, max_abund, min_owners, max_owners;
+  __host__ __device__ bool abund_window() const { return !(min_abund == 0 && max_abund == 0xffffffffu); }
+  __host__ __device__ bool owner_window() const { return !(min_owners <= 1 && max_owners == 0xffffffffu); }
+};
+struct FilterPass {
+  const uint64_t* hashes = nullptr;      // total elements
+  const uint32_t* abunds = nullptr;      // total abundances: the window's and OWN's; null when neither is asked
+  uint64_t total = 0;
+  const uint64_t* operand = nullptr;     // n_operand ascending distinct hashes (operand_mode != NONE)
+  const uint32_t* operand_abunds = nullptr;   // OPERAND: one per operand hash
+  uint32_t n_operand = 0;
+  MatchDirectory dir;                    // the owner window's; read only when the rule has one
+  FilterRule rule;
+  uint64_t* mask = nullptr;              // filter_tiles(total) * kFilterWords words: bit t = element t is kept
+  uint64_t* tile_at = nullptr;           // filter_tiles(total) + 1: survivors per tile; scanned in place (exclusive, the last: their total)
+};
+void filter_geometry(uint32_t* tile, uint32_t* operand_samples, uint32_t* threads);
+inline uint64_t filter_tiles(uint64_t total) { return (total + kFilterTile - 1) / kFilterTile; }
+// mask and tile_at (counts) of every tile.  Profile name filter_flag.
+void launch_filter_flag(const FilterPass& f, Device& dev, hipStream_t s);
+// tile_at[0 .. tiles] scanned in place, 64 bits wide: one workgroup, a carry from block to block
+void launch_filter_scan(uint64_t* tile_at, uint64_t tiles, hipStream_t s);
+// new_off[i] = the survivors in front of element offsets[i] - offsets[0], for i = 0 .. n (one lane per node)
+void launch_filter_offsets(const FilterPass& f, const uint64_t* offsets_dev, uint32_t n, uint64_t* new_off, Device& dev, hipStream_t s);
+// the survivors in order: out_hashes, and out_abunds (nullable) from f.abunds (OWN) or f.operand_abunds (OPERAND: the
+// operand is searched again for the survivors).  Profile name filter_emit.
+void launch_filter_emit(const FilterPass& f, uint64_t* out_hashes, uint32_t* out_abunds, Device& dev, hipStream_t s);
 
 }  // namespace smh

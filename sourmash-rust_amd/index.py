@@ -15,6 +15,11 @@
   ResidentIndex.from_records  an index built straight from records on the device, one group of records a node, and
                             ResidentIndex.concat, which joins resident indexes in HBM (no counterpart: include/sourmash_amd.h,
                             "Building an index from records")
+  ResidentIndex.filter      the same nodes cut down to the hashes that pass a rule -- kept in / dropped from an operand sketch,
+                            an abundance window, a window on the number of nodes that hold the hash -- as a new resident
+                            index made on the device; subtract / intersect / inflate / flatten are spelled through it, and
+                            select takes whole nodes in any order (no counterpart: include/sourmash_amd.h, "Filtering an
+                            index")
   ResidentIndex.match       the k-mers of every record of a batch the index knows, and each record's best node (no counterpart
                             either: include/sourmash_amd.h, "Matching records")
 
@@ -28,7 +33,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import SmhGatherRow, SmhLcaRow, SmhMatchRow, SmhSearchRow, lib, u32p, u64p
+from ._lib import SmhFilter, SmhGatherRow, SmhLcaRow, SmhMatchRow, SmhSearchRow, lib, u32p, u64p
 from .errors import SourmashError, call
 
 UNASSIGNED = 0xFFFFFFFF
@@ -132,6 +137,12 @@ COLLAPSE_ABUNDS = {"flat": 0, "sum": 1, "count": 2}
 COLLAPSE_DROP = 0xFFFFFFFF
 
 
+# the operand modes and the abundances of the result of filter (SMH_FILTER_* of include/sourmash_amd.h)
+FILTER_MODES = {None: 0, "keep": 1, "drop": 2}
+FILTER_ABUNDS = {"own": 0, "flat": 1, "operand": 2}
+FILTER_NO_MAX = 0xFFFFFFFF
+
+
 class _OwnSketches(collections.abc.Sequence):
     """`nodes` of an index collapse() returned: its own sketches, read back from the device when one is first asked for (the
     length is known without that)."""
@@ -178,6 +189,19 @@ class _PartParams(collections.abc.Sequence):
             self._list = [t for src in self._sources for t in src()]
             self._sources = None
         return self._list[k]
+
+
+class _PickedParams(collections.abc.Sequence):
+    """the per-node parameters of select()'s result: those of the parent's nodes ids[0], ids[1], ..."""
+
+    def __init__(self, parent_params, ids):
+        self._parent, self._ids = parent_params, [int(v) for v in ids]
+
+    def __len__(self):
+        return len(self._ids)
+
+    def __getitem__(self, k):
+        return self._parent[self._ids[k]]
 
 
 def scaled_of_max_hash(max_hash):
@@ -738,6 +762,65 @@ class ResidentIndex:
         idx._node_templates = _PartParams(parts)
         idx.nodes = _OwnSketches(idx)
         return idx
+
+    # --- filtering the nodes, taking a subset of them (additive ABI smh_index_filter, smh_index_select; the rules:
+    # include/sourmash_amd.h, "Filtering an index")
+    def filter(self, operand=None, mode=None, abund="own", min_abund=0, max_abund=None, min_owners=0, max_owners=None, downsample=False):
+        """This index with every node cut down to the hashes that pass a rule, made on the device (smh_index_filter): a
+        ResidentIndex of the same nodes in the same order, with this index's taxonomy.  A hash of a node is kept when all of
+        these hold, each judged on THIS index: mode "keep" -- it is in `operand`, "drop" -- it is not (None: no operand);
+        min_abund <= the node's abundance of it <= max_abund; min_owners <= the nodes of this index that hold it <= max_owners
+        (max_owners=1: every node's private hashes; min_owners=2: the shared ones).  abund: a key of FILTER_ABUNDS -- "own" the
+        kept hashes keep their abundances, "flat" none, "operand" the operand's abundance of the hash (mode "keep").
+        downsample=True: operand and index meet at the coarser max_hash of the two.  The result's `nodes` are its own
+        sketches, read back when first asked."""
+        if mode not in FILTER_MODES or (mode is None) != (operand is None):
+            raise ValueError("mode: 'keep' or 'drop' with an operand, None without")
+        if downsample and operand is not None:
+            idx, q = self._meet_sketch(operand)
+            return idx.filter(q, mode, abund, min_abund, max_abund, min_owners, max_owners)
+        rule = SmhFilter(FILTER_MODES[mode], FILTER_ABUNDS[abund], int(min_abund), FILTER_NO_MAX if max_abund is None else int(max_abund),
+                         int(min_owners), FILTER_NO_MAX if max_owners is None else int(max_owners))
+        child = ResidentIndex((), _handle=call(self._L.smh_index_filter, self._h, operand._p if operand is not None else None, C.byref(rule)))
+        child._node_templates = _PartParams([self])
+        child.nodes = _OwnSketches(child)
+        return child
+
+    def subtract(self, query, downsample=False):
+        """every node without the hashes of `query` (`sig subtract`)"""
+        return self.filter(query, "drop", downsample=downsample)
+
+    def intersect(self, query, downsample=False):
+        """every node restricted to the hashes of `query` (`sig intersect` against a mask)"""
+        return self.filter(query, "keep", downsample=downsample)
+
+    def inflate(self, query, downsample=False):
+        """every node restricted to the hashes of `query`, with query's abundances (`sig inflate`)"""
+        return self.filter(query, "keep", abund="operand", downsample=downsample)
+
+    def flatten(self):
+        """the same nodes without abundances (`sig flatten`)"""
+        return self.filter(abund="flat")
+
+    def select(self, ids):
+        """A new index whose node j is node ids[j] of this one, whole, copied on the device (smh_index_select): any order,
+        repeats allowed; or a boolean mask of len(self) entries (the nodes where it is True, in order).  Works on every index;
+        abundances and the taxonomy go with the nodes.  The result's `nodes` are its own sketches, read back when first
+        asked."""
+        arr = np.asarray(ids)
+        if arr.dtype == np.bool_:
+            if arr.shape != (len(self),):
+                raise ValueError("select: a boolean mask has one entry per node")
+            arr = np.flatnonzero(arr)
+        wide = arr.astype(np.int64).reshape(-1)
+        if wide.size and (wide.min() < 0 or wide.max() > 0xFFFFFFFF):
+            raise ValueError("select: ids are ints in [0, 2^32)")
+        v = np.ascontiguousarray(wide, dtype=np.uint32)
+        child = ResidentIndex((), _handle=call(self._L.smh_index_select, self._h, (v if v.size else np.zeros(1, np.uint32)).ctypes.data_as(u32p),
+                                               int(v.size)))
+        child._node_templates = _PickedParams(_PartParams([self]), v)
+        child.nodes = _OwnSketches(child)
+        return child
 
     def match(self, records, hits=False, stream=None):
         """Every record of a batch against the index (smh_index_match_*; the rules: include/sourmash_amd.h, "Matching

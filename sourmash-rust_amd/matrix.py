@@ -238,6 +238,14 @@ def collapse_geometry():
     return a.value, b.value, c.value
 
 
+def filter_geometry():
+    """(resident hashes one workgroup trip of the flag and emit passes takes, sampled top of the operand the search keeps in
+    LDS, threads of the workgroup) of ResidentIndex.filter"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().smh_filter_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
 def cluster_pair_budget():
     return int(lib().smh_cluster_pair_budget())
 
