@@ -962,6 +962,18 @@ int smh_release_workspace(void);
  * smh_release_workspace() empties the pool together with the workspace. */
 void smh_pool_set_limit(uint64_t bytes);
 uint64_t smh_pool_bytes(void);
+/* A test knob for what device work space holds before the library writes it.  Every byte of device memory the library
+ * uses comes from that pool's allocator: new memory reads zero, a recycled block reads whatever it last held -- usually
+ * the values the same operation left there, which are often right by accident.  With byte = 0 .. 255 every block the
+ * allocator hands out, fresh or recycled, and every block it parks is first filled with that byte over its whole size
+ * (hipMemset and a wait for the device: slow, for tests only); each fill adds one to the event counter "pool_filled"
+ * (smh_profile_get).  -1 (any value outside 0 .. 255) turns it off, the default; then allocation takes exactly the path it
+ * takes without this knob.  Process-wide; nothing reads an environment variable.  NO result depends on it: a result that
+ * changes under a fill byte has read work space nobody wrote, or memory that was given back.  Blocks that are already in
+ * use when the knob is set keep their content: smh_release_workspace() first, then the fill, then new objects, leaves no
+ * library-owned block unfilled. */
+void smh_set_pool_fill(int32_t byte);
+int32_t smh_pool_fill(void);
 
 /* Nodegraph (reference src/index/nodegraph.rs): a khmer-style bloom filter of n_tables bit tables, hash h sets bit
  * h % tablesize of each.  Single-hash calls and file I/O run on the host; count_many / get_many on the device.

@@ -248,6 +248,8 @@ _SIGS = {
     "smh_lca_budget": (C.c_uint64, []),
     "smh_set_grid_cap": (None, [C.c_uint32]),
     "smh_grid_cap": (C.c_uint32, []),
+    "smh_set_pool_fill": (None, [C.c_int32]),
+    "smh_pool_fill": (C.c_int32, []),
     "smh_release_workspace": (C.c_int, []),
     "smh_pool_set_limit": (None, [C.c_uint64]),
     "smh_pool_bytes": (C.c_uint64, []),

@@ -45,22 +45,35 @@ int current_device() {
   (void)hipGetDevice(&d);
   return d;
 }
+
+// The test pattern of smh_set_pool_fill (g_pool_fill >= 0).  The library's streams are non-blocking, so the null stream's
+// order orders nothing against them: the device is waited for behind the memset, before anybody can use or reuse the block.
+void pool_fill(void* p, size_t cap) {
+  HIP_CHECK(hipMemset(p, g_pool_fill, cap));
+  HIP_CHECK(hipDeviceSynchronize());
+  Device::get().count("pool_filled");
+}
 }  // namespace
+
+int32_t g_pool_fill = -1;
 
 void* device_pool_alloc(size_t need, size_t* cap) {
   const size_t c = size_class(need);
+  void* p = nullptr;
   {
     std::lock_guard<std::mutex> lock(g_pool_mu);
     auto it = g_pool.find({current_device(), c});
     if (it != g_pool.end() && !it->second.empty()) {
-      void* p = it->second.back();
+      p = it->second.back();
       it->second.pop_back();
       g_pool_bytes -= c;
       *cap = c;
-      return p;
     }
   }
-  void* p = nullptr;
+  if (p) {
+    if (g_pool_fill >= 0) pool_fill(p, c);                // a recycled block: the whole of it, not only `need`
+    return p;
+  }
   hipError_t e = hipMalloc(&p, c);
   if (e == hipErrorOutOfMemory) {                         // give the pooled blocks back and try once more
     (void)hipGetLastError();
@@ -69,6 +82,7 @@ void* device_pool_alloc(size_t need, size_t* cap) {
   }
   HIP_CHECK(e);
   *cap = c;
+  if (g_pool_fill >= 0) pool_fill(p, c);
   return p;
 }
 
@@ -78,8 +92,14 @@ void device_pool_free(void* ptr, size_t cap, bool sync) {
   // another stream at once, so the callers whose block may still be in use keep that wait
   if (sync) (void)hipDeviceSynchronize();
   if (cap >= 4096 && size_class(cap) == cap) {
+    // a block that is parked is filled as well (behind the wait above): a pointer somebody kept into it reads the pattern,
+    // not the old -- and right -- data.  A failed fill must not throw out of a destructor: the block is freed instead.
+    bool filled = true;
+    if (g_pool_fill >= 0) {
+      try { pool_fill(ptr, cap); } catch (const Error&) { filled = false; }
+    }
     std::lock_guard<std::mutex> lock(g_pool_mu);
-    if (g_pool_bytes + cap <= g_pool_limit) {
+    if (filled && g_pool_bytes + cap <= g_pool_limit) {
       g_pool[{current_device(), cap}].push_back(ptr);
       g_pool_bytes += cap;
       return;

@@ -31,6 +31,12 @@ void device_pool_free(void* ptr, size_t cap, bool sync);
 void device_pool_trim();   // hipFree everything the pool holds
 void device_pool_set_limit(size_t bytes);   // cap on the bytes parked in the pool (default 1 GiB, SOURMASH_AMD_POOL_MB)
 size_t device_pool_bytes();
+// A test knob (smh_set_pool_fill; -1: off, the default): with a byte 0 .. 255 every block device_pool_alloc hands out, fresh
+// or recycled, and every block device_pool_free parks is first filled with that byte over its whole size, and counted as
+// "pool_filled".  Work space that is read before it is written, and pointers kept into a block that was given back, then
+// read the pattern instead of zeros or the last call's -- often right -- values.  Off, the two functions do nothing more
+// than test this word.
+extern int32_t g_pool_fill;
 
 // a block of the device pool for the length of one call
 struct PoolBlock {
@@ -118,6 +124,10 @@ class Device {
   // if a future caller were to spread a call's launches over several streams.
   static constexpr uint32_t kTileCounters = 64;
   uint32_t* tile_counter(hipStream_t s);
+  // Gives the ring back (smh_release_workspace; the caller holds mutex() and has waited for the device).  The next
+  // tile_counter() allocates it anew; that is safe whatever the new block holds, because every word is zeroed on the
+  // launch's stream in front of the launch that uses it and no word is read otherwise.
+  void release_tile_counters() { tile_counters_.release_after_sync(); tile_counter_next_ = 0; }
 
   // HIP-event timing of named kernels (enabled by smh_profile_enable)
   void profile_enable(bool on);

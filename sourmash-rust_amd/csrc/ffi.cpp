@@ -1227,6 +1227,8 @@ void smh_lca_set_budget(uint64_t keys) { smh::g_lca_budget = keys ? keys : smh::
 uint64_t smh_lca_budget(void) { return smh::g_lca_budget; }
 void smh_set_grid_cap(uint32_t workgroups) { smh::g_grid_cap = workgroups; }
 uint32_t smh_grid_cap(void) { return smh::g_grid_cap; }
+void smh_set_pool_fill(int32_t byte) { smh::g_pool_fill = byte >= 0 && byte <= 255 ? byte : -1; }
+int32_t smh_pool_fill(void) { return smh::g_pool_fill; }
 
 // ---- a scaled sketch's state as device arrays: the cross-rank union of partial sketches ----
 int smh_sketch_export_dev(KmerMinHash* ptr, uint64_t* mins_dev, uint64_t* abunds_dev, uint64_t capacity, uint64_t* n_out, void* stream) {

@@ -1587,8 +1587,9 @@ void Engine::release_workspace() {
   HIP_CHECK(hipDeviceSynchronize());
   for (DeviceBuffer* b : {&cand_hash[0], &cand_hash[1], &cand_pos[0], &cand_pos[1], &counter, &uniq, &uniq2, &starts, &red_b,
                           &misc, &seqbuf, &offbuf, &vendbuf, &vendbuf2, &grpbuf, &resbuf, &segbuf, &badbuf, &cmp_a, &cmp_b,
-                          &cmp_oa, &cmp_ob, &cmp_out, &pair_out, &dev.scratch})
+                          &cmp_oa, &cmp_ob, &cmp_out, &pair_out, &union_tmp, &dev.scratch, &dev.tile_rec})
     b->release();
+  dev.release_tile_counters();
   release_compare_scratch();
   device_pool_trim();
 }

@@ -194,6 +194,17 @@ def set_grid_cap(workgroups):
     lib().smh_set_grid_cap(int(workgroups))
 
 
+def pool_fill():
+    return int(lib().smh_pool_fill())
+
+
+def set_pool_fill(byte):
+    """fill every device block the library's pool hands out or parks with this byte, 0 .. 255 (smh_set_pool_fill): a test
+    knob that puts a known pattern where work space would read zeros or the last call's values -- no result depends on it;
+    -1 restores the default (off)"""
+    lib().smh_set_pool_fill(int(byte))
+
+
 def gather_many_budget():
     return int(lib().smh_gather_many_budget())
 

@@ -33,6 +33,7 @@ def test_library_exports_every_declared_symbol(pkg):
     missing = declared_symbols() - exported
     assert not missing, missing
     assert declared_symbols() == set(pkg.exported_symbols())
+    assert {"smh_set_grid_cap", "smh_grid_cap", "smh_set_pool_fill", "smh_pool_fill"} <= exported   # the test knobs
 
 
 def test_loads_and_scalar_calls_work_without_gpu(pkg):

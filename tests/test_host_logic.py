@@ -184,3 +184,23 @@ def test_grid_cap_needs_no_device(pkg):
     finally:
         pkg.matrix.set_grid_cap(0)
     assert pkg.matrix.grid_cap() == 0 and L.smh_grid_cap() == 0
+
+
+def test_pool_fill_needs_no_device(pkg):
+    """the knob of tests/test_gpu_pool_fill.py: off after load, set and get round-trip, -1 restores the default, and a value
+    that is no byte turns it off instead of reaching hipMemset"""
+    L = pkg.lib()
+    assert L.smh_pool_fill() == -1 and pkg.matrix.pool_fill() == -1
+    try:
+        for byte in (0x00, 0x5A, 0xFF, 1):
+            pkg.matrix.set_pool_fill(byte)
+            assert pkg.matrix.pool_fill() == byte == L.smh_pool_fill()
+        L.smh_set_pool_fill(7)
+        assert pkg.matrix.pool_fill() == 7
+        for off in (-1, 256, -2):
+            L.smh_set_pool_fill(0x5A)
+            pkg.matrix.set_pool_fill(off)
+            assert pkg.matrix.pool_fill() == -1 == L.smh_pool_fill()
+    finally:
+        pkg.matrix.set_pool_fill(-1)
+    assert pkg.matrix.pool_fill() == -1 and L.smh_pool_fill() == -1
