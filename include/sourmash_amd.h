@@ -399,6 +399,48 @@ void smh_search_many_set_budget(uint64_t pairs);
 uint64_t smh_search_many_budget(void);
 void smh_search_geometry(uint32_t *short_owners, uint32_t *node_tile, uint32_t *max_queries);
 
+/* Nearest neighbours: per query the best k nodes, best first -- a bounded, ordered result that needs no guessed threshold
+ * (`search --best-only`, `--num-results N`, classifying by the closest reference, the k-nearest-neighbour graph of a
+ * collection).  The reference crate has no such call, so the rules are fixed here; restated in
+ * tests/nearest_restatement.py.
+ *   Rows of q  the rows smh_index_search_many reports for query q under the same metric, threshold and threshold_common: the
+ *              same rule, through the same device function -- the comparison is strict, common >= max(1, threshold_common),
+ *              and a pair that shares nothing is never a neighbour, whatever the threshold is (a threshold below 0 keeps
+ *              every pair that shares a hash).
+ *   Order      by value DESCENDING, where the value is the ONE IEEE binary64 division that "Per pair" above defines for the
+ *              metric; then by node ASCENDING among rows whose values are equal AS DOUBLES.  Two different fractions that
+ *              round to the same double (1/2 and 2/4 always do; so may two near-equal fractions of large integers) are a
+ *              tie, and the node decides it.  The value is positive, so its bit pattern read as an unsigned 64-bit integer
+ *              is its order: the device sorts by the key (value bits, ~node), descending.
+ *   Result     the first min(k, rows) rows of that order.
+ *   Outputs    row_offsets (the caller's, n_queries + 1 entries) and *rows, a malloc'ed array of row_offsets[n_queries]
+ *              SmhSearchRow (at least one element is allocated; the caller frees it with free()): the struct, and the integers
+ *              in it, are exactly what smh_index_search_many returns for the pair.  The rows of a query are in the order
+ *              above (NOT by node).  No row depends on chunking, the budget (smh_search_many_set_budget governs the chunks
+ *              here too), the grid or the order of atomics: a node appears once per query, so no two keys are equal.
+ *   Errors     decided before the device is touched, and nothing is written: everything smh_index_search_many refuses, in the
+ *              same order; behind the NaN threshold and the unknown metric, k == 0 and k > max_k (MSG; the message names
+ *              the limit, which smh_nearest_geometry reports).
+ * smh_index_nearest_many       the queries are sketches, staged as smh_index_search_many stages them.
+ * smh_index_nearest_block_dev  the CSR / device form, with the contract of smh_index_search_block_dev.
+ * smh_index_nearest_self       the k-nearest-neighbour graph: the queries are the index's own nodes, read from the resident CSR
+ *                              in place; row_offsets has smh_index_len(index) + 1 entries.  node == query is never reported
+ *                              (and takes none of the k places).  Works on an index smh_index_downsample returned.
+ * smh_nearest_geometry         the sizes at which the kernels' branches change: the largest k (256), the nodes of one workgroup
+ *                              of the tile kernel (smh_search_geometry's), and the keys the merge sorts at once -- a query
+ *                              whose kept candidates exceed merge_slots - k takes more than one merge step (tests, tools).
+ * Per chunk the work is smh_index_search_many's up to the select; then, instead of 16 bytes per surviving pair, a sort in LDS
+ * of every tile that holds a survivor, 12 bytes of work space per kept candidate (at most k per tile), and 16 bytes per
+ * reported row, at most k per query. */
+int smh_index_nearest_many(SmhIndex *index, const KmerMinHash *const *queries, uint32_t n_queries, uint32_t k, uint32_t metric,
+                           double threshold, uint32_t threshold_common, uint64_t *row_offsets, SmhSearchRow **rows);
+int smh_index_nearest_block_dev(SmhIndex *index, const uint64_t *q_hashes_dev, const uint64_t *q_offsets, uint32_t n_queries,
+                                uint32_t k, uint32_t metric, double threshold, uint32_t threshold_common, uint64_t *row_offsets,
+                                SmhSearchRow **rows, void *stream);
+int smh_index_nearest_self(SmhIndex *index, uint32_t k, uint32_t metric, double threshold, uint32_t threshold_common,
+                           uint64_t *row_offsets, SmhSearchRow **rows);
+void smh_nearest_geometry(uint32_t *max_k, uint32_t *node_tile, uint32_t *merge_slots);
+
 /* Clustering a resident index: the pairs of smh_index_search_self stay on the device and come back as clusters, 8 bytes per
  * node.  The reference crate has no clustering, so the rules are fixed here; restated in
  * tests/cluster_restatement.py.
@@ -1049,8 +1091,10 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * directory's owner lists through the groups, three launches each), "collapse_partition" (the survivors sorted by group and
  * the groups' bounds among them), "collapse_finish" (the child's hashes and abundances from the partitioned survivors),
  * "filter_flag" (a filter's verdict per resident hash and the survivors per tile), "filter_emit" (its survivors written in
- * order).  Event counters under the same call: "gather_many_chunk",
- * "search_many_chunk", "cluster_chunk" (chunks run), "cluster_round" (greedy rounds launched; with the timers enabled their
+ * order), "nearest_clamp" (the candidates kept per tile and the rows per query, and their scan), "nearest_tile" (a tile's
+ * survivors sorted in LDS, its best k kept), "nearest_merge" (a query's candidates folded into its best k, and its rows).
+ * Event counters under the same call: "gather_many_chunk",
+ * "search_many_chunk", "nearest_chunk", "cluster_chunk" (chunks run), "cluster_round" (greedy rounds launched; with the timers enabled their
  * entries are that count), "match_directory_built", "index_collapsed", "index_filtered", "index_selected", "grid_capped"
  * (launches whose grid smh_set_grid_cap lowered). */
 void smh_profile_enable(int on);

@@ -188,6 +188,13 @@ _SIGS = {
     "smh_search_many_set_budget": (None, [C.c_uint64]),
     "smh_search_many_budget": (C.c_uint64, []),
     "smh_search_geometry": (None, [u32p, u32p, u32p]),
+    "smh_index_nearest_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                         u64p, C.POINTER(C.POINTER(SmhSearchRow))]),
+    "smh_index_nearest_block_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                              u64p, C.POINTER(C.POINTER(SmhSearchRow)), C.c_void_p]),
+    "smh_index_nearest_self": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, u64p,
+                                         C.POINTER(C.POINTER(SmhSearchRow))]),
+    "smh_nearest_geometry": (None, [u32p, u32p, u32p]),
     "smh_index_cluster": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p]),
     "smh_cluster_set_pair_budget": (None, [C.c_uint64]),
     "smh_cluster_pair_budget": (C.c_uint64, []),

@@ -842,6 +842,49 @@ void smh_search_geometry(uint32_t* short_owners, uint32_t* node_tile, uint32_t* 
   smh::search_geometry(short_owners, node_tile, max_queries);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Nearest neighbours: the best k of those pairs per query (additive ABI)
+
+int smh_index_nearest_many(SmhIndex* index, const KmerMinHash* const* queries, uint32_t n_queries, uint32_t k, uint32_t metric,
+                           double threshold, uint32_t threshold_common, uint64_t* row_offsets, SmhSearchRow** rows) {
+  return pad_code([&] {
+    search_require(metric, threshold, row_offsets, rows);
+    smh::check_nearest_k(k);
+    auto& dev = smh::Device::get();
+    require(index, "index");
+    const std::vector<const smh::KmerMinHash*> v = require_queries(queries, n_queries);
+    *rows = reinterpret_cast<SmhSearchRow*>(index->nearest_many(v.data(), n_queries, k, metric, threshold, threshold_common, row_offsets, dev));
+  });
+}
+
+int smh_index_nearest_block_dev(SmhIndex* index, const uint64_t* q_hashes_dev, const uint64_t* q_offsets, uint32_t n_queries, uint32_t k,
+                                uint32_t metric, double threshold, uint32_t threshold_common, uint64_t* row_offsets, SmhSearchRow** rows,
+                                void* stream) {
+  return pad_code([&] {
+    search_require(metric, threshold, row_offsets, rows);
+    smh::check_nearest_k(k);
+    auto& dev = smh::Device::get();
+    require(index, "index"); require(q_offsets, "q_offsets");
+    require_uniform_scaled(index, "nearest_many");
+    if (n_queries && q_offsets[n_queries] != q_offsets[0]) require(q_hashes_dev, "q_hashes_dev");
+    *rows = reinterpret_cast<SmhSearchRow*>(index->nearest_dev(q_hashes_dev, q_offsets, n_queries, k, metric, threshold, threshold_common,
+                                                               smh::kSearchNotSelf, row_offsets, dev, dev.user_stream(stream)));
+  });
+}
+
+int smh_index_nearest_self(SmhIndex* index, uint32_t k, uint32_t metric, double threshold, uint32_t threshold_common, uint64_t* row_offsets,
+                           SmhSearchRow** rows) {
+  return pad_code([&] {
+    search_require(metric, threshold, row_offsets, rows);
+    smh::check_nearest_k(k);
+    auto& dev = smh::Device::get();
+    require(index, "index");
+    *rows = reinterpret_cast<SmhSearchRow*>(index->nearest_self(k, metric, threshold, threshold_common, row_offsets, dev));
+  });
+}
+
+void smh_nearest_geometry(uint32_t* max_k, uint32_t* node_tile, uint32_t* merge_slots) { smh::nearest_geometry(max_k, node_tile, merge_slots); }
+
 static_assert(SMH_CLUSTER_COMPONENTS == smh::kClusterComponents && SMH_CLUSTER_GREEDY == smh::kClusterGreedy, "the linkages of the header are the kernels'");
 
 int smh_index_cluster(SmhIndex* index, uint32_t metric, double threshold, uint32_t threshold_common, uint32_t linkage, const uint32_t* scores,

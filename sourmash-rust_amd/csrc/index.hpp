@@ -5,6 +5,7 @@
 // filtering its nodes and taking a subset of them (filter.cpp).
 // The C boundary (ffi.cpp) only checks pointers and calls in here.
 #pragma once
+#include <cstdlib>
 #include <functional>
 #include <memory>
 
@@ -157,6 +158,14 @@ struct ResidentIndex {
                              uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s);
   // the index against itself: the queries are read from the resident CSR in place
   SearchRow* search_self(uint32_t metric, double threshold, uint32_t threshold_common, bool upper_only, uint64_t* row_offsets, Device& dev);
+  // (nearest.cpp) Of those pairs, per query the best k by (value descending, node ascending) (the rules:
+  // include/sourmash_amd.h, smh_index_nearest_many).  The three forms, the returned rows and row_offsets are search_many's,
+  // but for the order of a query's rows; nearest_self leaves the diagonal out and nothing else.
+  SearchRow* nearest_many(const KmerMinHash* const* queries, uint32_t n_queries, uint32_t k, uint32_t metric, double threshold,
+                          uint32_t threshold_common, uint64_t* row_offsets, Device& dev);
+  SearchRow* nearest_dev(const uint64_t* q_hashes_dev, const uint64_t* q_offsets, uint32_t n_queries, uint32_t k, uint32_t metric,
+                         double threshold, uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s);
+  SearchRow* nearest_self(uint32_t k, uint32_t metric, double threshold, uint32_t threshold_common, uint64_t* row_offsets, Device& dev);
   // (cluster.cpp) The clusters of the index under a symmetric metric (the rules: include/sourmash_amd.h, smh_index_cluster).
   // linkage: ClusterLinkage; scores (nullable, n entries): the priority, |S_v| when null.  cluster_out, representative (n
   // entries each), rep_common (nullable, n entries; greedy only) and *n_clusters are written only when the call succeeds.
@@ -277,6 +286,22 @@ constexpr uint64_t kSearchManyBudget = 1ull << 26;
 extern uint64_t g_search_many_budget;
 uint32_t search_many_chunk_end(const uint64_t* q_offsets, uint32_t a, uint32_t n_queries, uint32_t n_nodes, uint64_t budget);
 void check_search(uint32_t metric, double threshold);
+// the rows of a search on their way to the caller: malloc'ed (the caller frees them with free()), grown chunk by chunk, one
+// element at least; `who` begins the message of the refusal when memory runs out
+struct SearchRowsOut {
+  const char* who;
+  SearchRow* p = nullptr;
+  size_t len = 0, cap = 0;
+  explicit SearchRowsOut(const char* who_) : who(who_) {}
+  SearchRowsOut(const SearchRowsOut&) = delete; SearchRowsOut& operator=(const SearchRowsOut&) = delete;
+  ~SearchRowsOut() { free(p); }
+  SearchRow* room(size_t more);   // `more` rows behind the ones held
+  SearchRow* release() { room(0); SearchRow* r = p; p = nullptr; return r; }
+};
+
+// nearest.cpp: the refusal of a k alone (kMsg: 0, or more than kNearestMaxK); needs no device.  The chunks are search_many's,
+// under its budget.
+void check_nearest_k(uint32_t k);
 
 // cluster.cpp: the directed adjacency entries the greedy linkage may hold in device memory (8 bytes each, 16 while a chunk's
 // rows are collected) -- a memory cap, not a measured optimum; the greedy rounds queued between two read-backs of the undecided

@@ -1,7 +1,7 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
 // gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip, collapse_kernels.hip,
-// index_build_kernels.hip, filter_kernels.hip).
+// index_build_kernels.hip, filter_kernels.hip, nearest_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -488,6 +488,29 @@ void launch_search_many_select(const SearchChunk& ck, Device& dev, hipStream_t s
 // the chunk's rows in order (query, then node), and query_rows[q] = where the rows of query q start.  Profile name
 // search_many_emit.
 void launch_search_many_emit(const SearchChunk& ck, SearchRow* rows, uint32_t* query_rows, Device& dev, hipStream_t s);
+
+// --- nearest_kernels.hip ---------------------------------------------------------------
+// The best k rows of every query by (value descending, node ascending) (the rules are in
+// include/sourmash_amd.h, smh_index_nearest_many).  A chunk is search_many's, and so is its front half: these come behind
+// launch_search_many_select.
+constexpr uint32_t kNearestMaxK = 256;           // the largest k: a merge step then still takes kNearestSlots - 256 candidates
+constexpr uint32_t kNearestSlots = 1024;         // keys the merge sorts in LDS at once (12 KiB); a tile's survivors fit them
+struct NearestChunk {
+  uint32_t k = 0;
+  uint32_t* cand_at = nullptr;   // nq x tiles + 1: candidates kept per (query, tile); after the scan where each tile's start
+  uint32_t* row_at = nullptr;    // = cand_at + nq x tiles + 1; nq + 1: rows per query; after the scan row_at[q] - row_at[0] is where
+                                 // query q's rows start (one scan runs over both arrays: row_at[0] is the chunk's candidates)
+  uint64_t* cand_v = nullptr;    // per kept candidate: the value's bits ...
+  uint32_t* cand_n = nullptr;    // ... and the node
+};
+void nearest_geometry(uint32_t* max_k, uint32_t* node_tile, uint32_t* merge_slots);
+// cand_at and row_at from ck.tile_rows (scanned), scanned in place as one array: cand_at[nq * tiles] is the chunk's
+// candidates, row_at[nq] its candidates + its rows.  Profile name nearest_clamp.
+void launch_nearest_clamp(const SearchChunk& ck, const NearestChunk& nc, Device& dev, hipStream_t s);
+// every tile's best candidates, in order, at its place in cand_v / cand_n.  Profile name nearest_tile.
+void launch_nearest_tile(const SearchChunk& ck, const NearestChunk& nc, Device& dev, hipStream_t s);
+// the chunk's rows: query q's at row_at[q] - row_at[0], in order.  Profile name nearest_merge.
+void launch_nearest_merge(const SearchChunk& ck, const NearestChunk& nc, SearchRow* rows, Device& dev, hipStream_t s);
 
 // --- cluster_kernels.hip ---------------------------------------------------------------
 // Clustering a resident index (the rules are in include/sourmash_amd.h, smh_index_cluster).  Components: the

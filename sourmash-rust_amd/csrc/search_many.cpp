@@ -23,24 +23,15 @@ void check_search(uint32_t metric, double threshold) {
   if (metric > kSearchMaxContainment) throw Error(kMsg, "search_many: unknown metric " + std::to_string(metric));
 }
 
-namespace {
-// the rows on their way to the caller: malloc'ed (the caller frees them with free()), grown chunk by chunk, one element at least
-struct RowsOut {
-  SearchRow* p = nullptr;
-  size_t len = 0, cap = 0;
-  ~RowsOut() { free(p); }
-  SearchRow* room(size_t more) {   // `more` rows behind the ones held
-    if (len + more > cap || !p) {
-      const size_t want = std::max<size_t>({len + more, cap * 2, 1});
-      SearchRow* np = (SearchRow*)realloc(p, want * sizeof(SearchRow));
-      if (!np) throw Error(kMsg, "search_many: out of memory for " + std::to_string(want) + " rows");
-      p = np; cap = want;
-    }
-    return p + len;
+SearchRow* SearchRowsOut::room(size_t more) {
+  if (len + more > cap || !p) {
+    const size_t want = std::max<size_t>({len + more, cap * 2, 1});
+    SearchRow* np = (SearchRow*)realloc(p, want * sizeof(SearchRow));
+    if (!np) throw Error(kMsg, std::string(who) + ": out of memory for " + std::to_string(want) + " rows");
+    p = np; cap = want;
   }
-  SearchRow* release() { room(0); SearchRow* r = p; p = nullptr; return r; }
-};
-}  // namespace
+  return p + len;
+}
 
 SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qoff, uint32_t nq, uint32_t metric, double threshold,
                                           uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s) {
@@ -52,7 +43,7 @@ SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qo
   if (n > 0xffffffffu - 2 * kSearchTile) throw_internal("search_many: too many nodes");
   const uint64_t total = nq ? qoff[nq] - qoff[0] : 0;
   std::vector<uint64_t> roff((size_t)nq + 1, 0);
-  RowsOut out;
+  SearchRowsOut out("search_many");
   auto finish = [&] {
     SearchRow* r = out.release();   // (may refuse: nothing has been written then)
     std::copy(roff.begin(), roff.end(), row_offsets);

@@ -1,6 +1,7 @@
 // search_rule.hpp -- the rule of the thresholded search on one (query, node) pair and the pass of a workgroup over one tile of
-// a query's counters (include/sourmash_amd.h, smh_index_search_many), shared by search_many_kernels.hip and
-// cluster_kernels.hip: clustering's adjacency IS this rule, through this device function.
+// a query's counters (include/sourmash_amd.h, smh_index_search_many), shared by search_many_kernels.hip,
+// cluster_kernels.hip and nearest_kernels.hip: clustering's adjacency and a query's neighbours ARE this rule, through this
+// device function.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,11 +21,9 @@ struct Rule {
   uint32_t metric, self, threshold_common;
 };
 
-// the rule of the header on one pair: node i (of size ls) and the query that is node `me` in the self modes (of size lq)
-__device__ __forceinline__ bool survives(const Rule& r, uint32_t common, uint32_t lq, uint32_t ls, uint32_t i, uint32_t me) {
-  if (common < r.threshold_common) return false;   // (threshold_common >= 1: a pair that shares nothing ends here)
-  if (r.self == kSearchNoDiagonal && i == me) return false;
-  if (r.self == kSearchUpperOnly && i <= me) return false;
+// the metric's value of a pair with common >= 1: the ONE division of the header (the thresholded search compares it, the
+// nearest-neighbour kernels order by its bit pattern)
+__device__ __forceinline__ double metric_value(const Rule& r, uint32_t common, uint32_t lq, uint32_t ls) {
   uint64_t den;
   switch (r.metric) {
     case kSearchJaccard: den = (uint64_t)lq + ls - common; break;   // (>= 1: common >= 1)
@@ -32,7 +31,15 @@ __device__ __forceinline__ bool survives(const Rule& r, uint32_t common, uint32_
     case kSearchContainmentQuery: den = lq; break;
     default: den = lq < ls ? lq : ls; break;
   }
-  return (double)common / (double)den > r.threshold;
+  return (double)common / (double)den;
+}
+
+// the rule of the header on one pair: node i (of size ls) and the query that is node `me` in the self modes (of size lq)
+__device__ __forceinline__ bool survives(const Rule& r, uint32_t common, uint32_t lq, uint32_t ls, uint32_t i, uint32_t me) {
+  if (common < r.threshold_common) return false;   // (threshold_common >= 1: a pair that shares nothing ends here)
+  if (r.self == kSearchNoDiagonal && i == me) return false;
+  if (r.self == kSearchUpperOnly && i <= me) return false;
+  return metric_value(r, common, lq, ls) > r.threshold;
 }
 
 // What a thread finds at its kSteps nodes of tile blockIdx.x of query blockIdx.y: common[k], size[k] and bit k of the

@@ -7,6 +7,8 @@
   ResidentIndex.gather_many the same decomposition for a batch of queries in one device call (smh_index_gather_many)
   ResidentIndex.search_many the (query, node) pairs of a batch of queries over a threshold, as a sparse list (no counterpart
                             either: include/sourmash_amd.h, smh_index_search_many); pairwise is the index against itself
+  ResidentIndex.nearest     of those pairs the best k per query, best first (smh_index_nearest_many); knn is the index against
+                            itself: the k-nearest-neighbour graph
   ResidentIndex.cluster     the clusters of the index's own nodes under such a threshold, made on the device (no counterpart:
                             include/sourmash_amd.h, smh_index_cluster): connected components or greedy representatives
   ResidentIndex.collapse    one sketch per group of nodes -- union, core, prevalence -- as a new resident index made on the
@@ -68,7 +70,8 @@ class SearchResult:
     """The pairs search_many / pairwise report.  offsets (uint64, queries + 1): the rows of query q are
     [offsets[q], offsets[q + 1]); node, common, node_size, query_size (uint32, a row each) are the device's integers, ordered
     by query, then node; jaccard, containment_node, containment_query and max_containment (float64, a row each) are derived
-    here from the integers, one division each, as the rule of the header derives the value it thresholds."""
+    here from the integers, one division each, as the rule of the header derives the value it thresholds.  Rows from nearest /
+    nearest_block_dev / knn are ordered by query, then by the metric's value descending, then node."""
 
     def __init__(self, offsets, rows, ksize=None, molecule=None):
         self.offsets = offsets
@@ -521,6 +524,35 @@ class ResidentIndex:
     def _threshold_common(threshold_bp, scaled):
         return int(math.ceil(threshold_bp / scaled))
 
+    def _search_by_groups(self, queries, one_group):
+        """the SearchResult of a batch whose queries meet the index at different max_hash: one_group(index, cut queries) per
+        group, the rows put back in the batch's order"""
+        parts = {}
+        for idx, members, cut in self._meet_groups(queries):
+            got = one_group(idx, cut)
+            for j, k in enumerate(members):
+                parts[k] = (got, got.rows_of(j))
+        offsets = np.zeros(len(queries) + 1, dtype=np.uint64)
+        rows = np.zeros(sum(sl.stop - sl.start for _, sl in parts.values()), dtype=_SEARCH_ROW)
+        for k in range(len(queries)):
+            got, sl = parts[k]
+            a = int(offsets[k])
+            offsets[k + 1] = a + sl.stop - sl.start
+            for name in _SEARCH_ROW.names:
+                rows[name][a:int(offsets[k + 1])] = getattr(got, name)[sl]
+        first = self.nodes[0] if self.nodes else None
+        return SearchResult(offsets, rows, first.ksize if first else None, first.molecule if first else None)
+
+    def _batch_threshold_common(self, who, queries, threshold_bp, scaled):
+        """ceil(threshold_bp / scaled) of a batch; scaled defaults to what the queries' max_hash stands for"""
+        thrs = set()
+        for q in queries:
+            mx = q.max_hash
+            thrs.add(self._threshold_common(threshold_bp, scaled if scaled is not None else scaled_of_max_hash(mx) if mx else 1))
+        if len(thrs) > 1:   # (queries the call accepts share their max_hash)
+            raise ValueError("%s: the queries differ in max_hash; give scaled, or downsample=True" % who)
+        return thrs.pop() if thrs else 0
+
     def search_many(self, queries, threshold, metric="jaccard", threshold_bp=0, scaled=None, downsample=False):
         """The (query, node) pairs with metric > threshold and at least ceil(threshold_bp / scaled) hashes in common (one
         at least), from one device call (smh_index_search_many): a SearchResult.  metric: a key of SEARCH_METRICS.  scaled
@@ -529,31 +561,11 @@ class ResidentIndex:
         max_hash at which each meets the index; every group is one call, and the sizes are those of the cut sketches."""
         queries = list(queries)
         if downsample:
-            parts = {}
-            for idx, members, cut in self._meet_groups(queries):
-                got = idx.search_many(cut, threshold, metric, threshold_bp, scaled)
-                for j, k in enumerate(members):
-                    parts[k] = (got, got.rows_of(j))
-            offsets = np.zeros(len(queries) + 1, dtype=np.uint64)
-            rows = np.zeros(sum(sl.stop - sl.start for _, sl in parts.values()), dtype=_SEARCH_ROW)
-            for k in range(len(queries)):
-                got, sl = parts[k]
-                a = int(offsets[k])
-                offsets[k + 1] = a + sl.stop - sl.start
-                for name in _SEARCH_ROW.names:
-                    rows[name][a:int(offsets[k + 1])] = getattr(got, name)[sl]
-            first = self.nodes[0] if self.nodes else None
-            return SearchResult(offsets, rows, first.ksize if first else None, first.molecule if first else None)
+            return self._search_by_groups(queries, lambda idx, cut: idx.search_many(cut, threshold, metric, threshold_bp, scaled))
         nqs = len(queries)
-        thrs = set()
-        for q in queries:
-            mx = q.max_hash
-            thrs.add(self._threshold_common(threshold_bp, scaled if scaled is not None else scaled_of_max_hash(mx) if mx else 1))
-        if len(thrs) > 1:   # (queries the call accepts share their max_hash)
-            raise ValueError("search_many: the queries differ in max_hash; give scaled, or downsample=True")
         arr = (C.c_void_p * max(nqs, 1))(*[q._p for q in queries])
         return self._search_result(nqs, self._L.smh_index_search_many, self._h, arr, nqs, SEARCH_METRICS[metric], float(threshold),
-                                   thrs.pop() if thrs else 0)
+                                   self._batch_threshold_common("search_many", queries, threshold_bp, scaled))
 
     def search_block_dev(self, hashes_dev, offsets, threshold, metric="jaccard", threshold_common=0, stream=None):
         """search_many of a CSR in device memory (smh_index_search_block_dev): query q is the hashes [offsets[q], offsets[q + 1])
@@ -575,6 +587,38 @@ class ResidentIndex:
         fn = self._L.smh_index_search_self
         return self._search_result(len(self), lambda h, m, t, c, *out: fn(h, m, t, c, bool(upper), *out), self._h, SEARCH_METRICS[metric],
                                    float(threshold), thr)
+
+    # --- the best k of those pairs per query (additive ABI smh_index_nearest_*; the rules: include/sourmash_amd.h,
+    # smh_index_nearest_many)
+    def nearest(self, queries, k, metric="jaccard", threshold=0.0, threshold_bp=0, scaled=None, downsample=False):
+        """Per query the k nearest nodes, best first, from one device call (smh_index_nearest_many): of the rows
+        search_many(queries, threshold, metric, threshold_bp, scaled) reports for the query, the first k by the metric's value
+        descending, then node ascending -- a SearchResult whose rows are in that order.  A node that shares no hash with the
+        query is never a neighbour, so a query may get fewer than k rows.  1 <= k <= matrix.nearest_geometry()[0].
+        downsample=True groups the queries as search_many does."""
+        queries = list(queries)
+        if downsample:
+            return self._search_by_groups(queries, lambda idx, cut: idx.nearest(cut, k, metric, threshold, threshold_bp, scaled))
+        nqs = len(queries)
+        arr = (C.c_void_p * max(nqs, 1))(*[q._p for q in queries])
+        return self._search_result(nqs, self._L.smh_index_nearest_many, self._h, arr, nqs, int(k), SEARCH_METRICS[metric], float(threshold),
+                                   self._batch_threshold_common("nearest", queries, threshold_bp, scaled))
+
+    def nearest_block_dev(self, hashes_dev, offsets, k, metric="jaccard", threshold=0.0, threshold_common=0, stream=None):
+        """nearest of a CSR in device memory (smh_index_nearest_block_dev), with the contract of search_block_dev"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nqs = len(offsets) - 1
+        return self._search_result(nqs, lambda *a: self._L.smh_index_nearest_block_dev(*a, C.c_void_p(stream or 0)), self._h,
+                                   C.c_void_p(hashes_dev), offsets.ctypes.data_as(u64p), nqs, int(k), SEARCH_METRICS[metric], float(threshold),
+                                   int(threshold_common))
+
+    def knn(self, k, metric="jaccard", threshold=0.0, threshold_bp=0):
+        """The k-nearest-neighbour graph of the index (smh_index_nearest_self): nearest of the index's own sketches, read where
+        they lie in HBM, without the rows node == query.  Works on an index downsample() returned, as pairwise does; scaled is
+        what the index's max_hash stands for."""
+        lo, _ = self.max_hash_range
+        thr = self._threshold_common(threshold_bp, scaled_of_max_hash(lo)) if lo else 0
+        return self._search_result(len(self), self._L.smh_index_nearest_self, self._h, int(k), SEARCH_METRICS[metric], float(threshold), thr)
 
     # --- clustering (additive ABI smh_index_cluster; the rules: include/sourmash_amd.h, smh_index_cluster)
     def cluster(self, threshold, metric="jaccard", linkage="components", scores=None, threshold_bp=0, scaled=None, ani=False):

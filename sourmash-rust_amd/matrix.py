@@ -223,6 +223,14 @@ def search_geometry():
     return a.value, b.value, c.value
 
 
+def nearest_geometry():
+    """(largest k, nodes of one workgroup of the tile kernel, keys the merge sorts at once) of ResidentIndex.nearest / knn
+    (smh_nearest_geometry): a query with more than merge_slots - k kept candidates takes more than one merge step"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().smh_nearest_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
 def search_many_budget():
     return int(lib().smh_search_many_budget())
 
