@@ -1096,7 +1096,8 @@ int smh_sbt_find_many(SmhSbt *sbt, KmerMinHash *const *queries, uint32_t n, doub
  * Event counters under the same call: "gather_many_chunk",
  * "search_many_chunk", "nearest_chunk", "cluster_chunk" (chunks run), "cluster_round" (greedy rounds launched; with the timers enabled their
  * entries are that count), "match_directory_built", "index_collapsed", "index_filtered", "index_selected", "grid_capped"
- * (launches whose grid smh_set_grid_cap lowered). */
+ * (launches whose grid smh_set_grid_cap lowered), "pool_free_waited" (device blocks given back behind a wait for the whole
+ * device). */
 void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);

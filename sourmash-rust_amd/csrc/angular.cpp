@@ -2,7 +2,6 @@
 // norms of a resident index, the prune pass through ResidentIndex::compare_block, the read-back of the block kernel.
 #include <algorithm>
 #include <cstring>
-#include <memory>
 #include <string>
 
 #include "index.hpp"
@@ -35,15 +34,16 @@ struct Operand {
   const uint64_t* hashes = nullptr;
   const uint32_t* abunds = nullptr;
   uint32_t n = 0;
-  std::unique_ptr<PoolBlock> store, small;   // small: offsets (2 x u64), norm2 (u64), error word (u32)
   std::vector<uint32_t> staged;
   uint64_t off[2] = {0, 0}, norm2 = 0;   // norm2, err: read back by prepare, valid once the stream was waited for
   uint32_t err = kAngularNoError;
   const char* what = "";
-  uint64_t* offsets_dev() const { return small->as<uint64_t>(); }
-  uint64_t* norm2_dev() const { return small->as<uint64_t>() + 2; }
-  uint32_t* err_dev() const { return reinterpret_cast<uint32_t*>(small->as<uint64_t>() + 3); }
-  void done() { if (store) store->synced = true; if (small) small->synced = true; }
+  Workspace ws;                // `small` and the store (behind what the uploads and read-backs touch: it waits for them first)
+  uint64_t* small = nullptr;   // offsets (2 x u64), norm2 (u64), error word (u32)
+  explicit Operand(hipStream_t s) : ws(s) {}
+  uint64_t* offsets_dev() const { return small; }
+  uint64_t* norm2_dev() const { return small + 2; }
+  uint32_t* err_dev() const { return reinterpret_cast<uint32_t*>(small + 3); }
   AngularSet set() const { return {hashes, abunds, offsets_dev(), norm2_dev(), 1}; }
 };
 
@@ -51,7 +51,7 @@ struct Operand {
 void prepare(Operand& op, const KmerMinHash& mh, const char* what, hipStream_t s) {
   mh.flush_pending();
   op.what = what;
-  op.small = std::make_unique<PoolBlock>(32);
+  op.small = op.ws.take<uint64_t>(4);
   HIP_CHECK(hipMemsetAsync(op.err_dev(), 0xff, 4, s));
   uint64_t n = 0;
   if (mh.dev) {
@@ -59,11 +59,11 @@ void prepare(Operand& op, const KmerMinHash& mh, const char* what, hipStream_t s
     n = S.n;
     if (n >= 0xffffffffull) throw_internal("angular: a sketch of 2^32 - 1 or more hashes");
     if (n && !S.has_counts && !S.has_runs) throw_internal("angular: the sketch's device state carries no abundances");
-    op.store = std::make_unique<PoolBlock>(n * 4);
+    uint32_t* narrow = op.ws.take<uint32_t>(n);
     op.hashes = S.uniq.as<uint64_t>();
-    op.abunds = op.store->as<uint32_t>();
+    op.abunds = narrow;
     launch_angular_narrow(S.has_counts ? S.counts.as<uint64_t>() : nullptr, S.has_counts ? nullptr : S.starts.as<uint32_t>(),
-                          (uint32_t)S.total, (uint32_t)n, op.store->as<uint32_t>(), op.err_dev(), 0, s);
+                          (uint32_t)S.total, (uint32_t)n, narrow, op.err_dev(), 0, s);
   } else {
     n = mh.mins.size();
     check_host_state(mh, what);   // (nothing is pending any more)
@@ -73,13 +73,13 @@ void prepare(Operand& op, const KmerMinHash& mh, const char* what, hipStream_t s
       if (mh.abunds[i] >> 32) throw_norm(what);
       op.staged[i] = (uint32_t)mh.abunds[i];
     }
-    op.store = std::make_unique<PoolBlock>(n * 12);
+    uint64_t* store = reinterpret_cast<uint64_t*>(op.ws.take<uint8_t>(n * 12));   // n hashes, then n u32 abundances
     if (n) {
-      HIP_CHECK(hipMemcpyAsync(op.store->ptr, mh.mins.data(), n * 8, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(op.store->as<uint64_t>() + n, op.staged.data(), n * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(store, mh.mins.data(), n * 8, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(store + n, op.staged.data(), n * 4, hipMemcpyHostToDevice, s));
     }
-    op.hashes = op.store->as<uint64_t>();
-    op.abunds = reinterpret_cast<const uint32_t*>(op.store->as<uint64_t>() + n);
+    op.hashes = store;
+    op.abunds = reinterpret_cast<const uint32_t*>(store + n);
   }
   op.n = (uint32_t)n;
   op.off[1] = n;
@@ -93,23 +93,26 @@ void prepare(Operand& op, const KmerMinHash& mh, const char* what, hipStream_t s
 void settle(std::initializer_list<Operand*> ops, hipStream_t s) {
   HIP_CHECK(hipStreamSynchronize(s));
   for (Operand* bad : ops)
-    if (bad->err != kAngularNoError) { for (Operand* op : ops) op->done(); throw_norm(bad->what); }
+    if (bad->err != kAngularNoError) throw_norm(bad->what);
 }
 
 // runs the block kernel into pool memory and brings the wanted outputs and the two counters back; the stream is idle after
 void run_host(const AngularSet& R, const AngularSet& C, const uint64_t* prune_dev, bool symmetric, uint64_t* dot, double* cosine,
               double* angular, Device& dev, hipStream_t s) {
   const size_t np = (size_t)R.n * C.n;
-  PoolBlock d_dot(dot ? np * 8 : 0), d_cos(cosine ? np * 8 : 0), d_ang(angular ? np * 8 : 0), d_cnt(16);
-  const AngularOut o{dot ? d_dot.as<uint64_t>() : nullptr, cosine ? d_cos.as<double>() : nullptr, angular ? d_ang.as<double>() : nullptr};
-  launch_angular_block(R, C, prune_dev, symmetric, o, d_cnt.as<unsigned long long>(), dev, s);
   uint64_t cnt[2] = {0, 0};
-  if (dot) HIP_CHECK(hipMemcpyAsync(dot, d_dot.ptr, np * 8, hipMemcpyDeviceToHost, s));
-  if (cosine) HIP_CHECK(hipMemcpyAsync(cosine, d_cos.ptr, np * 8, hipMemcpyDeviceToHost, s));
-  if (angular) HIP_CHECK(hipMemcpyAsync(angular, d_ang.ptr, np * 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.ptr, 16, hipMemcpyDeviceToHost, s));
+  Workspace ws(s);
+  uint64_t* d_dot = ws.take<uint64_t>(dot ? np : 0);   // (an output nobody wants still takes its smallest block)
+  double* d_cos = ws.take<double>(cosine ? np : 0);
+  double* d_ang = ws.take<double>(angular ? np : 0);
+  unsigned long long* d_cnt = ws.take<unsigned long long>(2);
+  const AngularOut o{dot ? d_dot : nullptr, cosine ? d_cos : nullptr, angular ? d_ang : nullptr};
+  launch_angular_block(R, C, prune_dev, symmetric, o, d_cnt, dev, s);
+  if (dot) HIP_CHECK(hipMemcpyAsync(dot, d_dot, np * 8, hipMemcpyDeviceToHost, s));
+  if (cosine) HIP_CHECK(hipMemcpyAsync(cosine, d_cos, np * 8, hipMemcpyDeviceToHost, s));
+  if (angular) HIP_CHECK(hipMemcpyAsync(angular, d_ang, np * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(cnt, d_cnt, 16, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  d_dot.synced = d_cos.synced = d_ang.synced = d_cnt.synced = true;
   g_angular_walked = cnt[0]; g_angular_skipped = cnt[1];
 }
 }  // namespace
@@ -122,15 +125,15 @@ void ResidentIndex::angular_ensure(const char* what, hipStream_t s) {
     h_norm2.assign(n, 0);
     uint32_t err = kAngularNoError;
     if (n) {
-      PoolBlock e(4);
-      HIP_CHECK(hipMemsetAsync(e.ptr, 0xff, 4, s));
+      Workspace ws(s);
+      uint32_t* e = ws.take<uint32_t>(1);
+      HIP_CHECK(hipMemsetAsync(e, 0xff, 4, s));
       if (!abunds_resident && !h_abunds.empty())
         HIP_CHECK(hipMemcpyAsync(abunds_dev.ptr, h_abunds.data(), h_abunds.size() * 4, hipMemcpyHostToDevice, s));
-      launch_angular_norms(abunds_dev.as<uint32_t>(), offsets.as<uint64_t>(), n, norm2_dev.as<uint64_t>(), e.as<uint32_t>(), s);
+      launch_angular_norms(abunds_dev.as<uint32_t>(), offsets.as<uint64_t>(), n, norm2_dev.as<uint64_t>(), e, s);
       HIP_CHECK(hipMemcpyAsync(h_norm2.data(), norm2_dev.ptr, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(&err, e.ptr, 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(&err, e, 4, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
-      e.synced = true;
     }
     bad_node = std::min(wide_node, err);
     std::vector<uint32_t>().swap(h_abunds);   // they live in HBM now
@@ -162,13 +165,13 @@ void ResidentIndex::angular(ResidentIndex& cols, uint64_t* dot, double* cosine, 
   angular_ensure(self ? "node" : "row node", s);
   if (!self) cols.angular_ensure("column node", s);
   if (np == 0) return;
-  std::unique_ptr<PoolBlock> cc;
+  Workspace ws(s);
+  uint64_t* cc = nullptr;
   if (np >= g_angular_prune_min_pairs) {
-    cc = std::make_unique<PoolBlock>(np * 8);
-    compare_block(*this, cols, CompareOut{nullptr, nullptr, nullptr, cc->as<uint64_t>(), nullptr}, dev, s);
+    cc = ws.take<uint64_t>(np);
+    compare_block(*this, cols, CompareOut{nullptr, nullptr, nullptr, cc, nullptr}, dev, s);
   }
-  run_host(angular_set(), cols.angular_set(), cc ? cc->as<uint64_t>() : nullptr, self, dot, cosine, angular, dev, s);
-  if (cc) cc->synced = true;
+  run_host(angular_set(), cols.angular_set(), cc, self, dot, cosine, angular, dev, s);
 }
 
 void ResidentIndex::angular_query(const KmerMinHash& query, uint64_t* dot, uint64_t* query_norm2, double* cosine, double* angular) {
@@ -181,12 +184,11 @@ void ResidentIndex::angular_query(const KmerMinHash& query, uint64_t* dot, uint6
   hipStream_t s = dev.stream();
   g_angular_walked = g_angular_skipped = 0;
   angular_ensure("node", s);
-  Operand q;
+  Operand q(s);
   prepare(q, query, "the query", s);
   settle({&q}, s);
   if (query_norm2) std::fill(query_norm2, query_norm2 + n, q.norm2);
   if (n) run_host(q.set(), angular_set(), nullptr, false, dot, cosine, angular, dev, s);
-  q.done();
 }
 
 void angular_similarity(const KmerMinHash& a, const KmerMinHash& b, double* angular, double* cosine, uint64_t* dot, uint64_t* norm2_a,
@@ -200,14 +202,13 @@ void angular_similarity(const KmerMinHash& a, const KmerMinHash& b, double* angu
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
   hipStream_t s = dev.stream();
   g_angular_walked = g_angular_skipped = 0;
-  Operand A, B;
+  Operand A(s), B(s);
   prepare(A, a, "the first sketch", s);
   prepare(B, b, "the second sketch", s);
   settle({&A, &B}, s);
   uint64_t d = 0;
   double c = 0.0, an = 0.0;
   run_host(A.set(), B.set(), nullptr, false, &d, &c, &an, dev, s);
-  A.done(); B.done();
   if (angular) *angular = an;
   if (cosine) *cosine = c;
   if (dot) *dot = d;
@@ -234,14 +235,15 @@ void angular_block_dev(AngularSet R, const uint64_t* row_offsets, AngularSet C, 
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
   hipStream_t s = dev.user_stream(stream);
   g_angular_walked = g_angular_skipped = 0;
-  PoolBlock offs(((size_t)n_rows + n_cols + 2) * 8), norms(((size_t)n_rows + n_cols) * 8), small(32);
-  uint64_t* d_ro = offs.as<uint64_t>();
+  Workspace ws(s);
+  uint64_t* d_ro = ws.take<uint64_t>((size_t)n_rows + n_cols + 2);
+  uint64_t* norms = ws.take<uint64_t>((size_t)n_rows + n_cols);
   uint64_t* d_co = d_ro + n_rows + 1;
-  uint64_t* d_rn = row_norm2_dev ? row_norm2_dev : norms.as<uint64_t>();
-  uint64_t* d_cn = col_norm2_dev ? col_norm2_dev : norms.as<uint64_t>() + n_rows;
+  uint64_t* d_rn = row_norm2_dev ? row_norm2_dev : norms;
+  uint64_t* d_cn = col_norm2_dev ? col_norm2_dev : norms + n_rows;
   R.offsets = d_ro; R.norm2 = d_rn;
   C.offsets = d_co; C.norm2 = d_cn;
-  unsigned long long* d_cnt = small.as<unsigned long long>();
+  unsigned long long* d_cnt = ws.take<unsigned long long>(4);
   uint32_t* d_err = reinterpret_cast<uint32_t*>(d_cnt + 2);
   HIP_CHECK(hipMemcpyAsync(d_ro, row_offsets, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_co, col_offsets, ((size_t)n_cols + 1) * 8, hipMemcpyHostToDevice, s));
@@ -251,16 +253,12 @@ void angular_block_dev(AngularSet R, const uint64_t* row_offsets, AngularSet C, 
   uint32_t err[2] = {kAngularNoError, kAngularNoError};
   HIP_CHECK(hipMemcpyAsync(err, d_err, 8, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  if (err[0] != kAngularNoError || err[1] != kAngularNoError) {
-    offs.synced = norms.synced = small.synced = true;
-    if (err[0] != kAngularNoError) throw_norm("row sketch " + std::to_string(err[0]));
-    throw_norm("column sketch " + std::to_string(err[1]));
-  }
+  if (err[0] != kAngularNoError) throw_norm("row sketch " + std::to_string(err[0]));
+  if (err[1] != kAngularNoError) throw_norm("column sketch " + std::to_string(err[1]));
   launch_angular_block(R, C, count_common_dev, symmetric, out, d_cnt, dev, s);
   uint64_t cnt[2] = {0, 0};
   HIP_CHECK(hipMemcpyAsync(cnt, d_cnt, 16, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));   // the offsets and the counters live in blocks that go back to the pool now
-  offs.synced = norms.synced = small.synced = true;
+  HIP_CHECK(hipStreamSynchronize(s));
   g_angular_walked = cnt[0]; g_angular_skipped = cnt[1];
 }
 

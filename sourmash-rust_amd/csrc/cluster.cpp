@@ -4,7 +4,6 @@
 // per node does.
 #include <algorithm>
 #include <cmath>
-#include <memory>
 #include <numeric>
 #include <string>
 
@@ -62,22 +61,25 @@ void ResidentIndex::cluster(uint32_t metric, double threshold, uint32_t threshol
     max_q = std::max(max_q, b - a);
   }
   const size_t out_words = (size_t)n * (greedy ? 3 : 2) + 1;
-  std::vector<uint32_t> host_out(out_words);
-  PoolBlock d_rel(rel.size() * 4), d_c((size_t)max_q * n * 4), d_out(out_words * 4);
-  PoolBlock d_scores(scores && !greedy ? (size_t)n * 4 : 1);   // (greedy ranks the nodes on the host)
-  HIP_CHECK(hipMemcpyAsync(d_rel.ptr, rel.data(), rel.size() * 4, hipMemcpyHostToDevice, s));
-  if (scores && !greedy) HIP_CHECK(hipMemcpyAsync(d_scores.ptr, scores, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  std::vector<uint32_t> host_out(out_words), order, rank;   // (what copies on the stream touch is declared ahead of the workspace, which waits)
+  // the blocks of the whole call: they go back when it ends, on every way out, behind a wait for the stream
+  Workspace ws(s);
+  uint32_t* d_rel = ws.take<uint32_t>(rel.size());
+  uint32_t* d_c = ws.take<uint32_t>((size_t)max_q * n);
+  uint32_t* d_out = ws.take<uint32_t>(out_words);
+  uint32_t* d_scores = reinterpret_cast<uint32_t*>(ws.take<uint8_t>(scores && !greedy ? (size_t)n * 4 : 1));   // (greedy ranks the nodes on the host)
+  HIP_CHECK(hipMemcpyAsync(d_rel, rel.data(), rel.size() * 4, hipMemcpyHostToDevice, s));
+  if (scores && !greedy) HIP_CHECK(hipMemcpyAsync(d_scores, scores, (size_t)n * 4, hipMemcpyHostToDevice, s));
   auto chunk_of = [&](const Chunk& c) {
     SearchChunk ck = search_chunk(hashes.as<uint64_t>(), qoff, c.a, c.b, metric, threshold, threshold_common,
                                   greedy ? kSearchNoDiagonal : kSearchUpperOnly);
-    ck.qoff = d_rel.as<uint32_t>() + c.rel_at;
-    ck.c = d_c.as<uint32_t>();
+    ck.qoff = d_rel + c.rel_at;
+    ck.c = d_c;
     return ck;
   };
   auto fetch = [&] {
-    HIP_CHECK(hipMemcpyAsync(host_out.data(), d_out.ptr, out_words * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(host_out.data(), d_out, out_words * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    d_rel.synced = d_c.synced = d_scores.synced = d_out.synced = true;
     std::copy_n(host_out.begin(), n, cluster_out);
     std::copy_n(host_out.begin() + n, n, representative);
     if (rep_common) std::copy_n(host_out.begin() + 2 * (size_t)n, n, rep_common);
@@ -85,92 +87,84 @@ void ResidentIndex::cluster(uint32_t metric, double threshold, uint32_t threshol
   };
 
   if (!greedy) {
-    PoolBlock d_parent((size_t)n * 4), d_work(((size_t)n * 4 + 2) * 4);
-    launch_cluster_iota(d_parent.as<uint32_t>(), n, s);
+    uint32_t* d_parent = ws.take<uint32_t>(n);
+    uint32_t* d_work = ws.take<uint32_t>((size_t)n * 4 + 2);
+    launch_cluster_iota(d_parent, n, s);
     for (const Chunk& c : chunks) {
       dev.count("cluster_chunk");
       const SearchChunk ck = chunk_of(c);
       if (ck.T == 0) continue;
       HIP_CHECK(hipMemsetAsync(ck.c, 0, (size_t)ck.nq * n * 4, s));
       launch_cluster_probe(dir, ck, dev, s);
-      launch_cluster_link(ck, d_parent.as<uint32_t>(), dev, s);
+      launch_cluster_link(ck, d_parent, dev, s);
     }
-    launch_cluster_finish_components(d_parent.as<uint32_t>(), scores ? d_scores.as<uint32_t>() : nullptr, offsets.as<uint64_t>(), n,
-                                     d_work.as<uint32_t>(), d_out.as<uint32_t>(), dev, s);
+    launch_cluster_finish_components(d_parent, scores ? d_scores : nullptr, offsets.as<uint64_t>(), n, d_work, d_out, dev, s);
     fetch();
-    d_parent.synced = d_work.synced = true;
     return;
   }
 
   // greedy: the rows of the search kernels stay in HBM, chunk by chunk, until their total is known
-  struct Held { std::unique_ptr<PoolBlock> rows, qrows; uint32_t R; };
+  struct Held { SearchRow* rows = nullptr; uint32_t* qrows = nullptr; uint32_t R = 0; };
   std::vector<Held> held(chunks.size());
-  PoolBlock d_tiles(((size_t)max_q * tiles + 1) * 4), d_start(((size_t)n + 1) * 4);
+  uint32_t* d_tiles = ws.take<uint32_t>((size_t)max_q * tiles + 1);
+  uint32_t* d_start = ws.take<uint32_t>((size_t)n + 1);
   uint64_t total = 0;
-  try {
-    for (size_t k = 0; k < chunks.size(); k++) {
-      dev.count("cluster_chunk");
-      SearchChunk ck = chunk_of(chunks[k]);
-      held[k].R = 0;
-      if (ck.T == 0) continue;
-      ck.tile_rows = d_tiles.as<uint32_t>();
-      const uint32_t R = search_chunk_rows(dir, ck, dev, s);
-      total += R;
-      if (total > g_cluster_pair_budget)
-        throw Error(kMsg, "cluster: the greedy linkage holds the directed adjacency in device memory; it has reached " + std::to_string(total) +
-                          " entries, the pair budget is " + std::to_string(g_cluster_pair_budget) +
-                          " (smh_cluster_set_pair_budget; a higher threshold gives fewer)");
-      if (R == 0) continue;
-      held[k].R = R;
-      held[k].rows = std::make_unique<PoolBlock>((size_t)R * sizeof(SearchRow));
-      held[k].qrows = std::make_unique<PoolBlock>((size_t)ck.nq * 4);
-      launch_search_many_emit(ck, held[k].rows->as<SearchRow>(), held[k].qrows->as<uint32_t>(), dev, s);
-    }
-  } catch (...) {
-    (void)hipStreamSynchronize(s);   // nothing of this call is in flight when its blocks go back
-    throw;
+  for (size_t k = 0; k < chunks.size(); k++) {
+    dev.count("cluster_chunk");
+    SearchChunk ck = chunk_of(chunks[k]);
+    if (ck.T == 0) continue;
+    ck.tile_rows = d_tiles;
+    const uint32_t R = search_chunk_rows(dir, ck, dev, s);
+    total += R;
+    if (total > g_cluster_pair_budget)
+      throw Error(kMsg, "cluster: the greedy linkage holds the directed adjacency in device memory; it has reached " + std::to_string(total) +
+                        " entries, the pair budget is " + std::to_string(g_cluster_pair_budget) +
+                        " (smh_cluster_set_pair_budget; a higher threshold gives fewer)");
+    if (R == 0) continue;
+    held[k].R = R;
+    held[k].rows = ws.take<SearchRow>(R);
+    held[k].qrows = ws.take<uint32_t>(ck.nq);
+    launch_search_many_emit(ck, held[k].rows, held[k].qrows, dev, s);
   }
-  PoolBlock d_adj(std::max<uint64_t>(total, 1) * sizeof(ClusterAdj)), d_rank((size_t)n * 4), d_st((size_t)n * 8), d_und(8),
-      d_work(((size_t)n * 2 + 1) * 4);
+  ClusterAdj* d_adj = ws.take<ClusterAdj>(std::max<uint64_t>(total, 1));
+  uint32_t* d_rank = ws.take<uint32_t>(n);
+  uint32_t* d_st = ws.take<uint32_t>((size_t)n * 2);
+  unsigned long long* d_und = ws.take<unsigned long long>(1);
+  uint32_t* d_work = ws.take<uint32_t>((size_t)n * 2 + 1);
   uint32_t base = 0;
   for (size_t k = 0; k < chunks.size(); k++) {
     const Held& h = held[k];
-    launch_cluster_pack(h.R ? h.rows->as<SearchRow>() : nullptr, h.R, h.R ? h.qrows->as<uint32_t>() : nullptr, chunks[k].b - chunks[k].a, base,
-                        d_adj.as<ClusterAdj>(), d_start.as<uint32_t>() + chunks[k].a, s);
+    launch_cluster_pack(h.rows, h.R, h.qrows, chunks[k].b - chunks[k].a, base, d_adj, d_start + chunks[k].a, s);
     base += h.R;
   }
-  launch_cluster_pack(nullptr, 0, nullptr, 1, base, d_adj.as<ClusterAdj>(), d_start.as<uint32_t>() + n, s);   // start[n] = the entries
+  launch_cluster_pack(nullptr, 0, nullptr, 1, base, d_adj, d_start + n, s);   // start[n] = the entries
 
   // rank[v] = v's position in priority order: score descending, ties to the lower node
-  std::vector<uint32_t> order(n), rank(n);
+  order.resize(n); rank.resize(n);
   std::iota(order.begin(), order.end(), 0u);
   auto score_of = [&](uint32_t v) { return scores ? scores[v] : (uint32_t)(qoff[v + 1] - qoff[v]); };
   std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return score_of(x) > score_of(y); });
   for (uint32_t p = 0; p < n; p++) rank[order[p]] = p;
-  HIP_CHECK(hipMemcpyAsync(d_rank.ptr, rank.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_rank, rank.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
 
-  uint32_t* st[2] = {d_st.as<uint32_t>(), d_st.as<uint32_t>() + n};
+  uint32_t* st[2] = {d_st, d_st + n};
   HIP_CHECK(hipMemsetAsync(st[0], 0, (size_t)n * 4, s));   // kClusterUndecided
   int cur = 0;
   const uint32_t period = g_cluster_rounds;
   for (unsigned long long undecided = n; undecided != 0;) {
-    HIP_CHECK(hipMemsetAsync(d_und.ptr, 0, 8, s));
+    HIP_CHECK(hipMemsetAsync(d_und, 0, 8, s));
     const bool timed = dev.profiling();   // the timer's entries count the rounds then; else the event counter does
     for (uint32_t r = 0; r < period; r++) {
       if (timed) dev.prof_begin(s); else dev.count("cluster_round");
-      launch_cluster_round(d_start.as<uint32_t>(), d_adj.as<ClusterAdj>(), d_rank.as<uint32_t>(), st[cur], st[cur ^ 1], n,
-                           r + 1 == period ? d_und.as<unsigned long long>() : nullptr, dev, s);
+      launch_cluster_round(d_start, d_adj, d_rank, st[cur], st[cur ^ 1], n, r + 1 == period ? d_und : nullptr, dev, s);
       if (timed) dev.prof_end("cluster_round", s);
       cur ^= 1;
     }
-    HIP_CHECK(hipMemcpyAsync(&undecided, d_und.ptr, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&undecided, d_und, 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   }
-  for (Held& h : held) { if (h.rows) h.rows->synced = true; if (h.qrows) h.qrows->synced = true; }
-  launch_cluster_assign(d_start.as<uint32_t>(), d_adj.as<ClusterAdj>(), d_rank.as<uint32_t>(), st[cur], metric, offsets.as<uint64_t>(), n,
-                        d_work.as<uint32_t>(), d_out.as<uint32_t>(), dev, s);
+  launch_cluster_assign(d_start, d_adj, d_rank, st[cur], metric, offsets.as<uint64_t>(), n, d_work, d_out, dev, s);
   fetch();
-  d_tiles.synced = d_start.synced = d_adj.synced = d_rank.synced = d_st.synced = d_und.synced = d_work.synced = true;
 }
 
 }  // namespace smh

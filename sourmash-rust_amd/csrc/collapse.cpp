@@ -6,7 +6,6 @@
 // the error word under SUM).
 #include <algorithm>
 #include <cmath>
-#include <memory>
 #include <string>
 
 #include "index.hpp"
@@ -81,21 +80,19 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const uint32_t* group, uint32_t G
         }
       }
       const uint32_t nh = dir.n_hashes;
-      PoolBlock d_group((size_t)P.n * 4), d_need((size_t)G * 4), d_start(((size_t)G + 1) * 4), d_cnt(((size_t)nh + 1) * 4),
-          d_wave(((size_t)dir.n_pairs / (kCollapseLaneMax + 1) + 1) * 4), d_long(((size_t)dir.n_pairs / (kCollapseWaveMax + 1) + 1) * 4), d_small(16);
-      std::unique_ptr<PoolBlock> k0, k1, v0, v1;
-      auto idle = [&] {
-        d_group.synced = d_need.synced = d_start.synced = d_cnt.synced = d_wave.synced = d_long.synced = d_small.synced = true;
-        for (auto* b : {&k0, &k1, &v0, &v1}) if (*b) (*b)->synced = true;
-      };
-      HIP_CHECK(hipMemcpyAsync(d_group.ptr, group, (size_t)P.n * 4, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(d_need.ptr, need.data(), (size_t)G * 4, hipMemcpyHostToDevice, s));
+      Workspace ws(s);
+      uint32_t* d_group = ws.take<uint32_t>(P.n);
+      uint32_t* d_need = ws.take<uint32_t>(G);
+      uint32_t* d_start = ws.take<uint32_t>((size_t)G + 1);
       CollapseFold f;
       f.d = dir;
-      f.group = d_group.as<uint32_t>(); f.need = d_need.as<uint32_t>(); f.n_groups = G;
-      f.cnt = d_cnt.as<uint32_t>();
-      f.wave_list = d_wave.as<uint32_t>(); f.long_list = d_long.as<uint32_t>();
-      f.list_count = d_small.as<uint32_t>(); f.err = d_small.as<uint32_t>() + 2;
+      f.group = d_group; f.need = d_need; f.n_groups = G;
+      f.cnt = ws.take<uint32_t>((size_t)nh + 1);
+      f.wave_list = ws.take<uint32_t>((size_t)dir.n_pairs / (kCollapseLaneMax + 1) + 1);
+      f.long_list = ws.take<uint32_t>((size_t)dir.n_pairs / (kCollapseWaveMax + 1) + 1);
+      f.list_count = ws.take<uint32_t>(4); f.err = f.list_count + 2;
+      HIP_CHECK(hipMemcpyAsync(d_group, group, (size_t)P.n * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_need, need.data(), (size_t)G * 4, hipMemcpyHostToDevice, s));
       f.abund = abund;
       launch_collapse_count(f, dev, s);
       exclusive_scan_u32_dev(f.cnt, nh, f.cnt + nh, dev.scratch, s);
@@ -105,11 +102,11 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const uint32_t* group, uint32_t G
       S = total;
       if (S) {
         const bool vals = abund != kCollapseFlat;
-        k0 = std::make_unique<PoolBlock>(S * 8);
-        k1 = std::make_unique<PoolBlock>(S * 8);
-        if (vals) { v0 = std::make_unique<PoolBlock>(S * 4); v1 = std::make_unique<PoolBlock>(S * 4); }
-        f.key = k0->as<uint64_t>();
-        f.val = vals ? v0->as<uint32_t>() : nullptr;
+        uint64_t* k[2] = {ws.take<uint64_t>(S), ws.take<uint64_t>(S)};
+        uint32_t* v[2] = {nullptr, nullptr};
+        if (vals) { v[0] = ws.take<uint32_t>(S); v[1] = ws.take<uint32_t>(S); }
+        f.key = k[0];
+        f.val = v[0];
         if (abund == kCollapseSum) {
           f.hashes = P.hashes.as<uint64_t>(); f.offsets = P.offsets.as<uint64_t>(); f.abunds = P.abunds_dev.as<uint32_t>();
           HIP_CHECK(hipMemsetAsync(f.err, 0xff, 4, s));
@@ -119,11 +116,9 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const uint32_t* group, uint32_t G
           uint32_t err = kCollapseNoError;
           HIP_CHECK(hipMemcpyAsync(&err, f.err, 4, hipMemcpyDeviceToHost, s));
           HIP_CHECK(hipStreamSynchronize(s));
-          if (err != kCollapseNoError) {
-            idle();
+          if (err != kCollapseNoError)
             refuse("group " + std::to_string(err) + " holds a hash whose abundances add up to 2^32 or more; a sketch of an index keeps 32 bits "
                    "per abundance");
-          }
         }
         // survivors lie rank-major, so a stable sort by the group's bytes alone leaves every group ascending by rank
         int cur = 0;
@@ -131,24 +126,21 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const uint32_t* group, uint32_t G
         if (G > 1) {
           uint32_t mask = 0;
           for (int p = 0; p < 4; p++) if (((uint64_t)(G - 1) >> (8 * p)) != 0) mask |= 1u << (4 + p);
-          cur = vals ? radix_sort_u64_v32(k0->as<uint64_t>(), k1->as<uint64_t>(), v0->as<uint32_t>(), v1->as<uint32_t>(), S, dev.scratch, s, mask)
-                     : radix_sort_u64_keys(k0->as<uint64_t>(), k1->as<uint64_t>(), S, dev.scratch, s, mask);
+          cur = vals ? radix_sort_u64_v32(k[0], k[1], v[0], v[1], S, dev.scratch, s, mask) : radix_sort_u64_keys(k[0], k[1], S, dev.scratch, s, mask);
         }
         // where every group starts among the partitioned keys: the child's offsets
         std::vector<uint32_t> start((size_t)G + 1);
-        launch_collapse_bounds((cur ? k1 : k0)->as<uint64_t>(), (uint32_t)S, G, d_start.as<uint32_t>(), dev, s);
+        launch_collapse_bounds(k[cur], (uint32_t)S, G, d_start, dev, s);
         dev.prof_end("collapse_partition", s);
         hashes.ensure(S * 8 + 8);   // (the padding of pack_sketches: the compare kernels read a little past the end)
         if (vals) { abunds_dev.ensure(S * 4 + 4); abunds_resident = true; }
-        launch_collapse_finish(dir.U, (cur ? k1 : k0)->as<uint64_t>(), vals ? (cur ? v1 : v0)->as<uint32_t>() : nullptr, (uint32_t)S,
-                               hashes.as<uint64_t>(), vals ? abunds_dev.as<uint32_t>() : nullptr, dev, s);
-        HIP_CHECK(hipMemcpyAsync(start.data(), d_start.ptr, ((size_t)G + 1) * 4, hipMemcpyDeviceToHost, s));
+        launch_collapse_finish(dir.U, k[cur], v[cur], (uint32_t)S, hashes.as<uint64_t>(), vals ? abunds_dev.as<uint32_t>() : nullptr, dev, s);
+        HIP_CHECK(hipMemcpyAsync(start.data(), d_start, ((size_t)G + 1) * 4, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        if (start[0] != 0 || start[G] != S) { idle(); throw_internal("collapse: the group bounds do not span the survivors"); }
+        if (start[0] != 0 || start[G] != S) throw_internal("collapse: the group bounds do not span the survivors");
         for (uint32_t g = 0; g < G; g++) { h_offsets[g + 1] = start[g + 1]; max_len = std::max(max_len, start[g + 1] - start[g]); }
       }
       HIP_CHECK(hipStreamSynchronize(s));
-      idle();
     }
     hashes.ensure(S * 8 + 8);
     if (has_abunds && !abunds_resident) { abunds_dev.ensure(S * 4 + 4); abunds_resident = true; }

@@ -20,11 +20,11 @@ void throw_hip(hipError_t e, const char* what, const char* file, int line) {
 //    bench.py / distributed.py): memory parked here is memory torch cannot use.  It is therefore
 //    capped -- 1 GiB by default, SOURMASH_AMD_POOL_MB=<MiB> (0 = no pooling) or smh_pool_set_limit()
 //    change it -- and smh_release_workspace() hands everything back.
-//  * A block freed with sync=false may be handed out again at once.  That is safe for the one caller
-//    that does it (DeviceMirror) because every entry point that reads a mirror returns with its device
-//    work complete (include/sourmash_amd.h; the two entry points that leave work open -- a single owner's
-//    collection dictionary, Device::leave_open -- read no mirror): no kernel of a finished call can still
-//    be reading it.
+//  * A block freed with sync=false may be handed out again at once, to work on any stream.  Two callers do it.  A Workspace
+//    (device.hpp) has just waited for the stream its blocks were used on.  DeviceMirror relies on every entry point that
+//    reads a mirror returning with its device work complete (include/sourmash_amd.h; the two entry points that leave work
+//    open -- a single owner's collection dictionary, Device::leave_open -- read no mirror and take no pool block): no
+//    kernel of a finished call can still be reading it.  Every free with sync=true is counted as "pool_free_waited".
 namespace {
 std::mutex g_pool_mu;
 std::map<std::pair<int, size_t>, std::vector<void*>> g_pool;
@@ -90,7 +90,10 @@ void device_pool_free(void* ptr, size_t cap, bool sync) {
   if (!ptr) return;
   // hipFree waits for the device; a block that goes back to the pool instead may be handed to work on
   // another stream at once, so the callers whose block may still be in use keep that wait
-  if (sync) (void)hipDeviceSynchronize();
+  if (sync) {
+    (void)hipDeviceSynchronize();
+    try { Device::get().count("pool_free_waited"); } catch (...) {}   // (a destructor's call: nothing may leave it)
+  }
   if (cap >= 4096 && size_class(cap) == cap) {
     // a block that is parked is filled as well (behind the wait above): a pointer somebody kept into it reads the pattern,
     // not the old -- and right -- data.  A failed fill must not throw out of a destructor: the block is freed instead.
@@ -106,6 +109,20 @@ void device_pool_free(void* ptr, size_t cap, bool sync) {
     }
   }
   (void)hipFree(ptr);
+}
+
+void* Workspace::take_bytes(size_t bytes) {
+  blocks_.push_back({nullptr, 0});   // (first: a block is never without its entry)
+  Block& b = blocks_.back();
+  b.ptr = device_pool_alloc(bytes ? bytes : 1, &b.cap);
+  return b.ptr;
+}
+
+void Workspace::release() {
+  if (blocks_.empty()) return;
+  const bool failed = hipStreamSynchronize(stream_) != hipSuccess;
+  for (auto b = blocks_.rbegin(); b != blocks_.rend(); ++b) device_pool_free(b->ptr, b->cap, failed);
+  blocks_.clear();
 }
 
 void device_pool_trim() {

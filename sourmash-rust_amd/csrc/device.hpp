@@ -9,6 +9,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "common.hpp"
@@ -38,15 +39,43 @@ size_t device_pool_bytes();
 // than test this word.
 extern int32_t g_pool_fill;
 
-// a block of the device pool for the length of one call
+// A block of the device pool owned by a long-lived object (Records' sequence and names) or by a call that keeps no account of
+// its stream (records.cpp): work in flight may still be using it, so it waits for the device when it goes back.
 struct PoolBlock {
   void* ptr = nullptr;
   size_t cap = 0;
-  bool synced = false;   // the stream was waited for: nothing can still be using the block (else the free waits for the device)
   explicit PoolBlock(size_t bytes) { ptr = device_pool_alloc(bytes ? bytes : 1, &cap); }
   PoolBlock(const PoolBlock&) = delete; PoolBlock& operator=(const PoolBlock&) = delete;
-  ~PoolBlock() { device_pool_free(ptr, cap, !synced); }
+  ~PoolBlock() { device_pool_free(ptr, cap, true); }
   template <class T> T* as() const { return reinterpret_cast<T*>(ptr); }
+};
+
+// The device blocks of one call -- or of one chunk, fold or operand of it -- on one stream.  take() borrows a block from the
+// pool; every block lives until the workspace dies.  The destructor waits for the stream and then gives the blocks back, last
+// taken first, without the device-wide wait: whatever was queued on the stream behind the last wait the caller made -- on a
+// success path nothing (the call has just read its results back, and the wait is a query), on an error path the kernels of
+// the statement that threw -- is over before a block can reach another stream.  There is no state to keep in step with the
+// stream and so none to get wrong; lifetimes are scopes.  If the wait itself reports an error the blocks go back behind the
+// device-wide wait instead.  Only for work the call completes: the two entry points that leave work open on purpose
+// (Device::leave_open) use no pool blocks and must not start to.
+class Workspace {
+ public:
+  explicit Workspace(hipStream_t s) : stream_(s) {}
+  Workspace(Workspace&& o) noexcept : stream_(o.stream_), blocks_(std::move(o.blocks_)) { o.blocks_.clear(); }
+  Workspace& operator=(Workspace&& o) noexcept {
+    if (this != &o) { release(); stream_ = o.stream_; blocks_ = std::move(o.blocks_); o.blocks_.clear(); }
+    return *this;
+  }
+  ~Workspace() { release(); }
+  // `count` elements of T in a block of their own (one device_pool_alloc; a count of 0 still yields a valid pointer)
+  template <class T> T* take(size_t count) { return static_cast<T*>(take_bytes(count * sizeof(T))); }
+
+ private:
+  struct Block { void* ptr; size_t cap; };
+  void* take_bytes(size_t bytes);
+  void release();
+  hipStream_t stream_;
+  std::vector<Block> blocks_;
 };
 
 // grow-only device allocation (never shrinks; released with the context or explicitly)

@@ -47,12 +47,12 @@ void downsample_max_hash(const KmerMinHash& src, uint64_t mx, KmerMinHash& out) 
   const DeviceSketch& S = *src.dev;
   const bool counts = src.has_abunds && S.has_counts, runs = src.has_abunds && !S.has_counts;
   if (runs && !S.has_runs && S.n) throw_internal("downsample: the sketch's device state carries no abundances");
-  PoolBlock small(16);
   uint64_t res[2] = {0, 0};   // the cut and the total its run starts end at
-  launch_downsample_cut(S.uniq.as<uint64_t>(), S.n, runs ? S.starts.as<uint32_t>() : nullptr, S.total, mx, small.as<uint64_t>(), s);
-  HIP_CHECK(hipMemcpyAsync(res, small.ptr, 16, hipMemcpyDeviceToHost, s));
+  Workspace ws(s);
+  uint64_t* small = ws.take<uint64_t>(2);
+  launch_downsample_cut(S.uniq.as<uint64_t>(), S.n, runs ? S.starts.as<uint32_t>() : nullptr, S.total, mx, small, s);
+  HIP_CHECK(hipMemcpyAsync(res, small, 16, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  small.synced = true;
   const uint64_t cut = res[0];
   if (cut == 0) return;   // (an empty sketch has no device state)
   auto ds = std::make_shared<DeviceSketch>();
@@ -87,12 +87,12 @@ uint32_t downsample_bounds_host(const uint64_t* hashes_dev, const uint64_t* offs
                                 std::vector<uint64_t>* new_off, Device& dev, hipStream_t s) {
   new_off->assign((size_t)n + 1, 0);
   if (n == 0) return 0;
-  PoolBlock kept((size_t)n * 4);
   std::vector<uint32_t> h_kept(n);
-  launch_downsample_bounds(hashes_dev, offsets_dev, n, mx, kept.as<uint32_t>(), dev, s);
-  HIP_CHECK(hipMemcpyAsync(h_kept.data(), kept.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  Workspace ws(s);
+  uint32_t* kept = ws.take<uint32_t>(n);
+  launch_downsample_bounds(hashes_dev, offsets_dev, n, mx, kept, dev, s);
+  HIP_CHECK(hipMemcpyAsync(h_kept.data(), kept, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  kept.synced = true;
   uint32_t max_len = 0;
   for (uint32_t i = 0; i < n; i++) {
     (*new_off)[i + 1] = (*new_off)[i] + h_kept[i];
@@ -114,24 +114,21 @@ void downsample_block_dev(const uint64_t* hashes_dev, const uint32_t* abunds_dev
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
   hipStream_t s = dev.user_stream(stream);
   std::vector<uint64_t> new_off;
-  PoolBlock offs(((size_t)n + 1) * 16);
-  uint64_t* d_src = offs.as<uint64_t>();
+  Workspace ws(s);
+  uint64_t* d_src = ws.take<uint64_t>(((size_t)n + 1) * 2);
   uint64_t* d_new = d_src + n + 1;
   HIP_CHECK(hipMemcpyAsync(d_src, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
   downsample_bounds_host(hashes_dev, d_src, n, mx, &new_off, dev, s);
   const uint64_t total = new_off[n];
-  if (total > capacity) {
-    offs.synced = true;
+  if (total > capacity)
     refuse("the kept hashes (" + std::to_string(total) + ") exceed the capacity of the output (" + std::to_string(capacity) + ")");
-  }
   if (total) {
     require(out_hashes_dev, "out_hashes_dev");
     if (abunds_dev) require(out_abunds_dev, "out_abunds_dev");
     HIP_CHECK(hipMemcpyAsync(d_new, new_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
     launch_downsample_copy(hashes_dev, abunds_dev, d_src, d_new, n, total, out_hashes_dev, out_abunds_dev, dev, s);
   }
-  HIP_CHECK(hipStreamSynchronize(s));   // the offsets live in a block that goes back to the pool now
-  offs.synced = true;
+  HIP_CHECK(hipStreamSynchronize(s));   // (`new_off` is read by the upload)
   std::copy(new_off.begin(), new_off.end(), out_offsets);
 }
 

@@ -5,7 +5,6 @@
 // -- and 4 more under OPERAND with an operand that lives in HBM, the error word of its narrowed abundances.  select() copies
 // whole nodes with downsample_copy, whose contract takes any array of source starts.
 #include <algorithm>
-#include <memory>
 #include <string>
 
 #include "index.hpp"
@@ -72,9 +71,8 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const KmerMinHash* operand, const
     FilterPass f;
     f.rule = rule;
     // the operand where it lives: a state in HBM is read there, a host state goes up in one upload
-    std::unique_ptr<PoolBlock> up, narrow, err;
     std::vector<uint64_t> stage;
-    auto idle = [&] { for (auto* b : {&up, &narrow, &err}) if (*b) (*b)->synced = true; };
+    Workspace ws(s);
     if (oper) {
       operand->flush_pending();
       const uint64_t lq = operand->dev ? operand->dev->n : operand->mins.size();
@@ -85,16 +83,16 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const KmerMinHash* operand, const
         f.operand = S.uniq.as<uint64_t>();
         if (inflate && lq) {
           if (!S.has_counts && !S.has_runs) throw_internal("filter: the operand's device state carries no abundances");
-          narrow = std::make_unique<PoolBlock>(lq * 4);
-          err = std::make_unique<PoolBlock>(4);
+          uint32_t* narrow = ws.take<uint32_t>(lq);
+          uint32_t* err = ws.take<uint32_t>(1);
           uint32_t wide = kAngularNoError;
-          HIP_CHECK(hipMemsetAsync(err->ptr, 0xff, 4, s));
+          HIP_CHECK(hipMemsetAsync(err, 0xff, 4, s));
           launch_angular_narrow(S.has_counts ? S.counts.as<uint64_t>() : nullptr, S.has_counts ? nullptr : S.starts.as<uint32_t>(),
-                                (uint32_t)S.total, (uint32_t)lq, narrow->as<uint32_t>(), err->as<uint32_t>(), 0, s);
-          HIP_CHECK(hipMemcpyAsync(&wide, err->ptr, 4, hipMemcpyDeviceToHost, s));
+                                (uint32_t)S.total, (uint32_t)lq, narrow, err, 0, s);
+          HIP_CHECK(hipMemcpyAsync(&wide, err, 4, hipMemcpyDeviceToHost, s));
           HIP_CHECK(hipStreamSynchronize(s));
-          if (wide != kAngularNoError) { idle(); refuse("the operand holds an abundance of 2^32 or more"); }
-          f.operand_abunds = narrow->as<uint32_t>();
+          if (wide != kAngularNoError) refuse("the operand holds an abundance of 2^32 or more");
+          f.operand_abunds = narrow;
         }
       } else {
         if (inflate && operand->abunds.size() != lq) refuse("the operand's abundance vector does not match its hashes (quirks Q5/Q6)");
@@ -103,7 +101,7 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const KmerMinHash* operand, const
             if (a >> 32) refuse("the operand holds an abundance of 2^32 or more");
         if (lq) {
           const size_t words = lq + (inflate ? (lq + 1) / 2 : 0);   // [hashes | u32 abundances]
-          up = std::make_unique<PoolBlock>(words * 8);
+          uint64_t* up = ws.take<uint64_t>(words);
           const uint64_t* src = operand->mins.data();
           if (inflate) {
             stage.assign(words, 0);
@@ -112,9 +110,9 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const KmerMinHash* operand, const
             for (uint64_t k = 0; k < lq; k++) a32[k] = (uint32_t)operand->abunds[k];
             src = stage.data();
           }
-          HIP_CHECK(hipMemcpyAsync(up->ptr, src, words * 8, hipMemcpyHostToDevice, s));
-          f.operand = up->as<uint64_t>();
-          if (inflate) f.operand_abunds = reinterpret_cast<const uint32_t*>(up->as<uint64_t>() + lq);
+          HIP_CHECK(hipMemcpyAsync(up, src, words * 8, hipMemcpyHostToDevice, s));
+          f.operand = up;
+          if (inflate) f.operand_abunds = reinterpret_cast<const uint32_t*>(up + lq);
         }
       }
     }
@@ -126,20 +124,19 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const KmerMinHash* operand, const
       f.hashes = P.hashes.as<uint64_t>() + base;
       f.total = total;
       // the parent's abundances: read in place when they live in HBM, else uploaded for the call
-      std::unique_ptr<PoolBlock> ab;
+      Workspace pass(s);
       if (need_abunds) {
         if (P.angular_ready || P.abunds_resident) {
           f.abunds = P.abunds_dev.as<uint32_t>() + base;
         } else {
-          ab = std::make_unique<PoolBlock>(total * 4);
-          HIP_CHECK(hipMemcpyAsync(ab->ptr, P.h_abunds.data(), total * 4, hipMemcpyHostToDevice, s));
-          f.abunds = ab->as<uint32_t>();
+          uint32_t* ab = pass.take<uint32_t>(total);
+          HIP_CHECK(hipMemcpyAsync(ab, P.h_abunds.data(), total * 4, hipMemcpyHostToDevice, s));
+          f.abunds = ab;
         }
       }
       const uint64_t tiles = filter_tiles(total);
-      PoolBlock mask(tiles * kFilterWords * 8), tile_at((tiles + 1) * 8);
-      f.mask = mask.as<uint64_t>();
-      f.tile_at = tile_at.as<uint64_t>();
+      f.mask = pass.take<uint64_t>(tiles * kFilterWords);
+      f.tile_at = pass.take<uint64_t>(tiles + 1);
       launch_filter_flag(f, dev, s);
       launch_filter_scan(f.tile_at, tiles, s);
       launch_filter_offsets(f, P.offsets.as<uint64_t>(), n, offsets.as<uint64_t>(), dev, s);
@@ -153,8 +150,6 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const KmerMinHash* operand, const
         launch_filter_emit(f, hashes.as<uint64_t>(), has_abunds ? abunds_dev.as<uint32_t>() : nullptr, dev, s);
         HIP_CHECK(hipStreamSynchronize(s));
       }
-      mask.synced = tile_at.synced = true;   // the stream is idle
-      if (ab) ab->synced = true;
     } else {
       HIP_CHECK(hipMemsetAsync(offsets.ptr, 0, h_offsets.size() * 8, s));
       hashes.ensure(8);
@@ -165,7 +160,6 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const KmerMinHash* operand, const
     nums.ensure((size_t)n * 4 + 4);
     HIP_CHECK(hipMemsetAsync(nums.ptr, 0, (size_t)n * 4 + 4, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    idle();
     dev.count("index_filtered");
   }
   enroll();
@@ -226,14 +220,14 @@ ResidentIndex::ResidentIndex(ResidentIndex& P, const uint32_t* ids, uint32_t n_i
     offsets.ensure(h_offsets.size() * 8);
     nums.ensure((size_t)n * 4 + 4);
     if (on_device) { abunds_dev.ensure(total * 4 + 4); abunds_resident = true; }
-    PoolBlock d_src(src.size() * 8);
-    HIP_CHECK(hipMemcpyAsync(d_src.ptr, src.data(), src.size() * 8, hipMemcpyHostToDevice, s));
+    Workspace ws(s);
+    uint64_t* d_src = ws.take<uint64_t>(src.size());
+    HIP_CHECK(hipMemcpyAsync(d_src, src.data(), src.size() * 8, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(offsets.ptr, h_offsets.data(), h_offsets.size() * 8, hipMemcpyHostToDevice, s));
     if (n) HIP_CHECK(hipMemcpyAsync(nums.ptr, h_nums.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    launch_downsample_copy(P.hashes.as<uint64_t>(), on_device ? P.abunds_dev.as<uint32_t>() : nullptr, d_src.as<uint64_t>(),
+    launch_downsample_copy(P.hashes.as<uint64_t>(), on_device ? P.abunds_dev.as<uint32_t>() : nullptr, d_src,
                            offsets.as<uint64_t>(), n, total, hashes.as<uint64_t>(), on_device ? abunds_dev.as<uint32_t>() : nullptr, dev, s);
     HIP_CHECK(hipStreamSynchronize(s));
-    d_src.synced = true;
     dev.count("index_selected");
   }
   enroll();

@@ -205,21 +205,22 @@ uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q
   while ((((uint64_t)lq + (1ull << shift) - 1) >> shift) > kGatherSamples) shift++;
   const uint32_t m = (uint32_t)(((uint64_t)lq + (1ull << shift) - 1) >> shift);
 
-  PoolBlock hits(n_elems * 4), counters((size_t)n * 8), perq(((size_t)lq + 1) * 4 + (size_t)lq * 8), rows((size_t)std::max(cap, 1u) * sizeof(GatherRow)),
-      state(sizeof(GatherState));
-  uint32_t* d_c0 = counters.as<uint32_t>();
+  Workspace ws(s);
+  uint32_t* hits = ws.take<uint32_t>(n_elems);
+  uint32_t* d_c0 = ws.take<uint32_t>((size_t)n * 2);
   uint32_t* d_c = d_c0 + n;
-  uint32_t* d_invoff = perq.as<uint32_t>();          // lq + 1: degrees, then their exclusive scan
+  uint32_t* d_invoff = ws.take<uint32_t>((size_t)lq * 3 + 1);   // lq + 1: degrees, then their exclusive scan
   uint32_t* d_cursor = d_invoff + lq + 1;            // lq
   uint32_t* d_assigned = d_cursor + lq;              // lq
-  GatherState* d_st = state.as<GatherState>();
+  GatherRow* rows = ws.take<GatherRow>(std::max(cap, 1u));
+  GatherState* d_st = ws.take<GatherState>(1);
   HIP_CHECK(hipMemsetAsync(d_invoff, 0, ((size_t)lq + 1) * 4 + (size_t)lq * 4, s));
   HIP_CHECK(hipMemsetAsync(d_assigned, 0xff, (size_t)lq * 4, s));
   HIP_CHECK(hipMemsetAsync(d_st, 0, sizeof(GatherState), s));
 
   const uint32_t grid = grid_for(n, 4, dev.grid_limit(), dev);
   dev.prof_begin(s);
-  hipLaunchKernelGGL(k_gather_hits, dim3(grid), dim3(256), 0, s, idx, q.hashes, lq, shift, m, hits.as<uint32_t>(), d_c0, d_c, d_invoff, d_st);
+  hipLaunchKernelGGL(k_gather_hits, dim3(grid), dim3(256), 0, s, idx, q.hashes, lq, shift, m, hits, d_c0, d_c, d_invoff, d_st);
   HIP_CHECK(hipGetLastError());
   dev.prof_end("gather_hits", s);
   GatherState h_st;
@@ -229,11 +230,11 @@ uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q
   const uint32_t total_hits = (uint32_t)h_st.total_hits;
 
   uint32_t rounds = 0;
-  PoolBlock inv((size_t)std::max(total_hits, 1u) * 4);
+  uint32_t* inv = ws.take<uint32_t>(std::max(total_hits, 1u));
   if (total_hits != 0 && cap != 0) {
     dev.prof_begin(s);
     exclusive_scan_u32_dev(d_invoff, (size_t)lq + 1, nullptr, dev.scratch, s);
-    hipLaunchKernelGGL(k_gather_invert, dim3(grid), dim3(256), 0, s, idx, hits.as<uint32_t>(), d_c0, d_invoff, d_cursor, inv.as<uint32_t>());
+    hipLaunchKernelGGL(k_gather_invert, dim3(grid), dim3(256), 0, s, idx, hits, d_c0, d_invoff, d_cursor, inv);
     HIP_CHECK(hipGetLastError());
     dev.prof_end("gather_invert", s);
     const GatherWeights wt{q.counts, q.starts, q.total};
@@ -241,9 +242,9 @@ uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q
     for (;;) {
       dev.prof_begin(s);
       for (uint32_t k = 0; k < kGatherRoundsPerSync; k++) {
-        hipLaunchKernelGGL(k_gather_pick, dim3(1), dim3(1024), 0, s, d_c, n, d_c0, idx.offsets, threshold, cap, rows.as<GatherRow>(), d_st);
-        hipLaunchKernelGGL(k_gather_subtract, dim3(sub_grid), dim3(256), 0, s, idx.offsets, hits.as<uint32_t>(), d_c0, d_invoff,
-                           inv.as<uint32_t>(), lq, wt, d_c, d_assigned, rows.as<GatherRow>(), d_st);
+        hipLaunchKernelGGL(k_gather_pick, dim3(1), dim3(1024), 0, s, d_c, n, d_c0, idx.offsets, threshold, cap, rows, d_st);
+        hipLaunchKernelGGL(k_gather_subtract, dim3(sub_grid), dim3(256), 0, s, idx.offsets, hits, d_c0, d_invoff,
+                           inv, lq, wt, d_c, d_assigned, rows, d_st);
       }
       HIP_CHECK(hipGetLastError());
       dev.prof_end("gather_rounds", s);
@@ -253,10 +254,9 @@ uint32_t gather_run(const SketchSet& idx, uint32_t max_len, const GatherQuery& q
     }
     rounds = h_st.rounds;
   }
-  if (rounds) HIP_CHECK(hipMemcpyAsync(rows_host, rows.ptr, (size_t)rounds * sizeof(GatherRow), hipMemcpyDeviceToHost, s));
+  if (rounds) HIP_CHECK(hipMemcpyAsync(rows_host, rows, (size_t)rounds * sizeof(GatherRow), hipMemcpyDeviceToHost, s));
   if (assigned_host && lq) HIP_CHECK(hipMemcpyAsync(assigned_host, d_assigned, (size_t)lq * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  hits.synced = counters.synced = perq.synced = rows.synced = state.synced = inv.synced = true;
   return rounds;
 }
 

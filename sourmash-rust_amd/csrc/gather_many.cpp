@@ -57,34 +57,34 @@ void ResidentIndex::gather_many_dev(const uint64_t* qh, const uint64_t* qab, con
       for (uint32_t q = a; q < b; q++) roff[q + 1] = roff[q];
       if (T == 0) { dev.count("gather_many_chunk"); break; }
       const size_t pairs = (size_t)Qc * n;
-      PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_pos(T * 8), d_cnt(pairs * 12 + 4), d_qcnt((size_t)Qc * 4), d_qs((size_t)Qc * sizeof(GatherManyQuery)),
-          d_st(sizeof(GatherManyState)), d_rowoff((size_t)Qc * 8);
+      Workspace ws(s);
       GatherManyChunk ck;
       ck.hashes = qh + qoff[a];
       ck.counts = qab ? qab + qoff[a] : nullptr;
-      ck.qoff = d_qoff.as<uint32_t>();
+      uint32_t* d_qoff = ws.take<uint32_t>((size_t)Qc + 1);
+      ck.qoff = d_qoff;
       ck.nq = Qc; ck.T = (uint32_t)T; ck.n = n;
-      ck.rank = d_pos.as<uint32_t>();
+      ck.rank = ws.take<uint32_t>(T * 2);
       ck.assigned = ck.rank + T;
-      ck.c0 = d_cnt.as<uint32_t>();
+      ck.c0 = ws.take<uint32_t>(pairs * 3 + 1);
       ck.c = ck.c0 + pairs;
       ck.loff = ck.c + pairs;
-      ck.rowoff = d_rowoff.as<uint64_t>();
-      ck.qs = d_qs.as<GatherManyQuery>();
-      ck.st = d_st.as<GatherManyState>();
-      upload_chunk_offsets(qoff, a, b, &rel, d_qoff.as<uint32_t>(), s);   // (the stream is waited for below, on every way on)
+      uint32_t* d_qcnt = ws.take<uint32_t>(Qc);
+      ck.qs = ws.take<GatherManyQuery>(Qc);
+      ck.st = ws.take<GatherManyState>(1);
+      uint64_t* d_rowoff = ws.take<uint64_t>(Qc);
+      ck.rowoff = d_rowoff;
+      upload_chunk_offsets(qoff, a, b, &rel, d_qoff, s);   // (the stream is waited for below, on every way on)
       HIP_CHECK(hipMemsetAsync(ck.c0, 0, pairs * 8, s));   // c0 and c
       HIP_CHECK(hipMemsetAsync(ck.assigned, 0xff, T * 4, s));
       HIP_CHECK(hipMemsetAsync(ck.st, 0, sizeof(GatherManyState), s));
-      launch_gather_many_probe(dir, ck, threshold, d_qcnt.as<uint32_t>(), dev, s);
+      launch_gather_many_probe(dir, ck, threshold, d_qcnt, dev, s);
       qcnt.resize(Qc);
       GatherManyState h_st;
-      HIP_CHECK(hipMemcpyAsync(qcnt.data(), d_qcnt.ptr, (size_t)Qc * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(qcnt.data(), d_qcnt, (size_t)Qc * 4, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipMemcpyAsync(&h_st, ck.st, sizeof h_st, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
-      auto idle = [&] { d_qoff.synced = d_pos.synced = d_cnt.synced = d_qcnt.synced = d_qs.synced = d_st.synced = d_rowoff.synced = true; };
       if (h_st.hits >= (1ull << 32)) {
-        idle();
         if (Qc == 1) throw_internal("gather_many: 2^32 or more (sketch, query hash) matches of one query");
         b = a + Qc / 2;
         continue;
@@ -102,14 +102,13 @@ void ResidentIndex::gather_many_dev(const uint64_t* qh, const uint64_t* qab, con
         max_cap = std::max(max_cap, qs[k].cap);
         max_lq = std::max(max_lq, rel[k + 1] - rel[k]);
       }
-      if (h_st.hits == 0 || R == 0) { blank(qoff[a] - base0, T); idle(); break; }
+      if (h_st.hits == 0 || R == 0) { blank(qoff[a] - base0, T); break; }
       const uint32_t hits = (uint32_t)h_st.hits;
-      PoolBlock d_lists((size_t)hits * 4), d_rows(R * sizeof(GatherRow));
-      ck.lists = d_lists.as<uint32_t>();
-      ck.rows = d_rows.as<GatherRow>();
+      ck.lists = ws.take<uint32_t>(hits);
+      ck.rows = ws.take<GatherRow>(R);
       h_st.live = Qc; h_st.max_rounds = 0;
-      HIP_CHECK(hipMemcpyAsync(d_rowoff.ptr, rowoff.data(), (size_t)Qc * 8, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(d_qs.ptr, qs.data(), (size_t)Qc * sizeof(GatherManyQuery), hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_rowoff, rowoff.data(), (size_t)Qc * 8, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(ck.qs, qs.data(), (size_t)Qc * sizeof(GatherManyQuery), hipMemcpyHostToDevice, s));
       HIP_CHECK(hipMemcpyAsync(ck.st, &h_st, 8, hipMemcpyHostToDevice, s));
       launch_gather_many_fill(dir, ck, dev, s);
       // every query is done after its cap + 1 picks at the latest
@@ -123,12 +122,10 @@ void ResidentIndex::gather_many_dev(const uint64_t* qh, const uint64_t* qab, con
         if (queued > max_cap) throw_internal("gather_many: queries still live after every round they can take");
       }
       crow.resize(R);
-      HIP_CHECK(hipMemcpyAsync(crow.data(), d_rows.ptr, R * sizeof(GatherRow), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(qs.data(), d_qs.ptr, (size_t)Qc * sizeof(GatherManyQuery), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(crow.data(), ck.rows, R * sizeof(GatherRow), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(qs.data(), ck.qs, (size_t)Qc * sizeof(GatherManyQuery), hipMemcpyDeviceToHost, s));
       if (assigned) HIP_CHECK(hipMemcpyAsync(assigned + (qoff[a] - base0), ck.assigned, T * 4, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
-      idle();
-      d_lists.synced = d_rows.synced = true;
       for (uint32_t k = 0; k < Qc; k++) {
         out.insert(out.end(), crow.begin() + rowoff[k], crow.begin() + rowoff[k] + qs[k].rounds);
         roff[a + k + 1] = roff[a + k] + qs[k].rounds;

@@ -152,24 +152,27 @@ MatchDirectory ResidentIndex::ensure_directory(const char* who, Device& dev, hip
   auto d = std::make_unique<MatchDir>();
   d->n_pairs = (uint32_t)total;
   if (total == 0) { match_dir = d.release(); return match_dir->view(); }
-  PoolBlock k0(total * 8), k1(total * 8), v0(total * 4), v1(total * 4), uq(total * 8), st(total * 4 + 4), cnt(4);
-  HIP_CHECK(hipMemcpyAsync(k0.ptr, hashes.as<uint64_t>() + h_offsets.front(), total * 8, hipMemcpyDeviceToDevice, s));
-  launch_match_owner_ids(offsets.as<uint64_t>(), n, total, v0.as<uint32_t>(), dev, s);
-  const int cur = radix_sort_u64_v32(k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(), total, dev.scratch, s);
-  run_length_encode_u64_async((cur ? k1 : k0).as<uint64_t>(), total, uq.as<uint64_t>(), st.as<uint32_t>(), dev.scratch, s, nullptr, nullptr,
-                              cnt.as<uint32_t>(), nullptr);
+  Workspace ws(s);
+  uint64_t* k[2] = {ws.take<uint64_t>(total), ws.take<uint64_t>(total)};
+  uint32_t* v[2] = {ws.take<uint32_t>(total), ws.take<uint32_t>(total)};
+  uint64_t* uq = ws.take<uint64_t>(total);
+  uint32_t* st = ws.take<uint32_t>(total + 1);
+  uint32_t* cnt = ws.take<uint32_t>(1);
+  HIP_CHECK(hipMemcpyAsync(k[0], hashes.as<uint64_t>() + h_offsets.front(), total * 8, hipMemcpyDeviceToDevice, s));
+  launch_match_owner_ids(offsets.as<uint64_t>(), n, total, v[0], dev, s);
+  const int cur = radix_sort_u64_v32(k[0], k[1], v[0], v[1], total, dev.scratch, s);
+  run_length_encode_u64_async(k[cur], total, uq, st, dev.scratch, s, nullptr, nullptr, cnt, nullptr);
   uint32_t nu = 0;
-  HIP_CHECK(hipMemcpyAsync(&nu, cnt.ptr, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(&nu, cnt, 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   d->n_hashes = nu;
   d->U.ensure((size_t)nu * 8);
   d->starts.ensure((size_t)nu * 4);
   d->owners.ensure(total * 4);
-  HIP_CHECK(hipMemcpyAsync(d->U.ptr, uq.ptr, (size_t)nu * 8, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(d->starts.ptr, st.ptr, (size_t)nu * 4, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(d->owners.ptr, (cur ? v1 : v0).ptr, total * 4, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d->U.ptr, uq, (size_t)nu * 8, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d->starts.ptr, st, (size_t)nu * 4, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d->owners.ptr, v[cur], total * 4, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  k0.synced = k1.synced = v0.synced = v1.synced = uq.synced = st.synced = cnt.synced = true;
   dev.count("match_directory_built");
   match_dir = d.release();
   return match_dir->view();
@@ -282,7 +285,7 @@ uint32_t ResidentIndex::gather(const KmerMinHash& query, uint32_t threshold_comm
   query.flush_pending();
   // the query where it lives: a state in HBM is read there (uniq + counts or run starts), a host state is uploaded once
   GatherQuery q;
-  std::unique_ptr<PoolBlock> up;
+  Workspace ws(s);
   uint64_t lq = 0;
   if (query.dev) {
     const DeviceSketch& S = *query.dev;
@@ -298,12 +301,12 @@ uint32_t ResidentIndex::gather(const KmerMinHash& query, uint32_t threshold_comm
     if (query.has_abunds && query.abunds.size() != lq)
       throw_internal("gather: the query's abundance vector does not match its hashes (quirks Q5/Q6)");
     if (lq) {
-      up = std::make_unique<PoolBlock>(lq * 8 * (query.has_abunds ? 2 : 1));
-      HIP_CHECK(hipMemcpyAsync(up->ptr, query.mins.data(), lq * 8, hipMemcpyHostToDevice, s));
-      q.hashes = up->as<uint64_t>();
+      uint64_t* up = ws.take<uint64_t>(lq * (query.has_abunds ? 2 : 1));
+      HIP_CHECK(hipMemcpyAsync(up, query.mins.data(), lq * 8, hipMemcpyHostToDevice, s));
+      q.hashes = up;
       if (query.has_abunds) {
-        HIP_CHECK(hipMemcpyAsync(up->as<uint64_t>() + lq, query.abunds.data(), lq * 8, hipMemcpyHostToDevice, s));
-        q.counts = up->as<uint64_t>() + lq;
+        HIP_CHECK(hipMemcpyAsync(up + lq, query.abunds.data(), lq * 8, hipMemcpyHostToDevice, s));
+        q.counts = up + lq;
       }
     }
   }
@@ -311,9 +314,7 @@ uint32_t ResidentIndex::gather(const KmerMinHash& query, uint32_t threshold_comm
   q.n = (uint32_t)lq;
   if (assigned && lq && n == 0) std::fill(assigned, assigned + lq, 0xffffffffu);
   if (n == 0 || lq == 0) return 0;
-  const uint32_t n_rows = gather_run(set(), max_len, q, threshold_common, rows, rows_capacity, assigned, dev, s);
-  if (up) up->synced = true;   // gather_run returns with the stream idle
-  return n_rows;
+  return gather_run(set(), max_len, q, threshold_common, rows, rows_capacity, assigned, dev, s);
 }
 
 }  // namespace smh

@@ -13,6 +13,8 @@
 
 namespace smh {
 
+struct SearchRowsOut;
+
 struct ResidentIndex {
   DeviceBuffer hashes, offsets, nums;
   std::vector<uint64_t> h_offsets;
@@ -158,6 +160,16 @@ struct ResidentIndex {
                              uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s);
   // the index against itself: the queries are read from the resident CSR in place
   SearchRow* search_self(uint32_t metric, double threshold, uint32_t threshold_common, bool upper_only, uint64_t* row_offsets, Device& dev);
+  // What search_many_dev and nearest_dev are made of: the checks (`who` begins their messages), the early returns, the directory,
+  // the chunks under search_many's budget (each counted as `chunk_counter`) and the rows' accounting.  Per chunk with a hash the
+  // three blocks every search kernel reads (ck.qoff, uploaded; ck.c; ck.tile_rows) come from the chunk's workspace, then
+  // tail(dir, ck, ws, out, starts) runs the kernels: it takes its further blocks from ws, makes room in `out` for the chunk's R
+  // rows, brings them there, writes starts[1 .. ck.nq) -- where each later query's rows begin among them -- and returns R
+  // with the stream waited for.
+  using SearchChunkTail = std::function<uint32_t(const MatchDirectory&, const SearchChunk&, Workspace&, SearchRowsOut&, uint32_t*)>;
+  SearchRow* search_chunks(const char* who, const char* chunk_counter, const uint64_t* q_hashes_dev, const uint64_t* q_offsets,
+                           uint32_t n_queries, uint32_t metric, double threshold, uint32_t threshold_common, uint32_t self,
+                           uint64_t* row_offsets, Device& dev, hipStream_t s, const SearchChunkTail& tail);
   // (nearest.cpp) Of those pairs, per query the best k by (value descending, node ascending) (the rules:
   // include/sourmash_amd.h, smh_index_nearest_many).  The three forms, the returned rows and row_offsets are search_many's,
   // but for the order of a query's rows; nearest_self leaves the diagonal out and nothing else.
@@ -247,11 +259,12 @@ extern uint64_t g_lca_budget;
 constexpr uint64_t kQueryLimit32 = 0xffffffffull, kQueryLimit31 = 1ull << 31;
 struct QueryBatch {
   QueryBatch(const KmerMinHash* const* queries, uint32_t n_queries, const char* who, uint64_t limit, bool want_abunds, Device& dev);
-  const uint64_t* hashes() const { return csr->as<uint64_t>(); }
-  const uint64_t* abunds() const { return with_abunds ? csr->as<uint64_t>() + qoff.back() : nullptr; }   // null: every hash weighs 1
+  const uint64_t* hashes() const { return csr; }
+  const uint64_t* abunds() const { return with_abunds ? csr + qoff.back() : nullptr; }   // null: every hash weighs 1
   const uint64_t* offsets() const { return qoff.data(); }   // n_queries + 1, from 0
  private:
-  std::unique_ptr<PoolBlock> csr, up;   // [hashes | abundances]; the host states on their way there when a query lives in HBM
+  Workspace ws;    // [hashes | abundances], and the host states on their way there when a query lives in HBM
+  uint64_t* csr = nullptr;
   std::vector<uint64_t> qoff;
   bool with_abunds = false;
 };

@@ -6,7 +6,6 @@
 // runs of several folds are merged by one more sort and the same kernels with the counts as weights.  Per fold the candidate
 // count and the run count come to the host, per call the offsets; no hash does.
 #include <algorithm>
-#include <memory>
 #include <string>
 #include <vector>
 
@@ -25,61 +24,57 @@ constexpr uint64_t kMaxPairs = (1ull << 31) - 1;   // what the directory and the
 
 // the runs of one fold, or of all of them merged: ascending by (group, hash)
 struct Runs {
-  std::unique_ptr<PoolBlock> hash, pack;   // n u64 each; pack: (group << kBuildCountBits) | count
+  Workspace ws;   // the two blocks: they move with the runs and go back where the runs die
+  uint64_t* hash = nullptr;
+  uint64_t* pack = nullptr;   // n u64 each; pack: (group << kBuildCountBits) | count
   uint64_t n = 0;
+  explicit Runs(hipStream_t s) : ws(s) {}
 };
 
 // n elements sorted by (tag >> shift, hash) -> their runs.  The stream is idle when it returns.
 Runs runs_of(const uint64_t* hash, const uint64_t* tag, uint64_t n, int shift, uint32_t* err, Device& dev, hipStream_t s) {
-  Runs out;
+  Runs out(s);
   const uint32_t tiles = index_build_tiles(n);
-  PoolBlock d_tiles(((size_t)tiles + 1) * 4);
-  launch_index_build_heads(hash, tag, n, shift, d_tiles.as<uint32_t>(), dev, s);
-  exclusive_scan_u32_dev(d_tiles.as<uint32_t>(), tiles, d_tiles.as<uint32_t>() + tiles, dev.scratch, s);
+  Workspace ws(s);
+  uint32_t* d_tiles = ws.take<uint32_t>((size_t)tiles + 1);
+  launch_index_build_heads(hash, tag, n, shift, d_tiles, dev, s);
+  exclusive_scan_u32_dev(d_tiles, tiles, d_tiles + tiles, dev.scratch, s);
   uint32_t nruns = 0;
-  HIP_CHECK(hipMemcpyAsync(&nruns, d_tiles.as<uint32_t>() + tiles, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(&nruns, d_tiles + tiles, 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   out.n = nruns;
-  out.hash = std::make_unique<PoolBlock>((size_t)nruns * 8);
-  out.pack = std::make_unique<PoolBlock>((size_t)nruns * 8);
-  PoolBlock d_start((size_t)nruns * 4);
-  launch_index_build_emit(hash, tag, n, shift, d_tiles.as<uint32_t>(), out.hash->as<uint64_t>(), d_start.as<uint32_t>(), dev, s);
-  launch_index_build_counts(tag, n, shift, d_start.as<uint32_t>(), nruns, out.pack->as<uint64_t>(), err, dev, s);
+  out.hash = out.ws.take<uint64_t>(nruns);
+  out.pack = out.ws.take<uint64_t>(nruns);
+  uint32_t* d_start = ws.take<uint32_t>(nruns);
+  launch_index_build_emit(hash, tag, n, shift, d_tiles, out.hash, d_start, dev, s);
+  launch_index_build_counts(tag, n, shift, d_start, nruns, out.pack, err, dev, s);
   HIP_CHECK(hipStreamSynchronize(s));
-  d_tiles.synced = d_start.synced = true;
   return out;
-}
-
-void mark_synced(std::vector<Runs>& v) {
-  for (Runs& r : v) r.hash->synced = r.pack->synced = true;
 }
 
 // the runs of several folds -> one: a hash of one group that shows up in several folds is one hash with the counts added
 Runs merge_runs(std::vector<Runs>& folds, uint32_t* err, Device& dev, hipStream_t s) {
   uint64_t N = 0;
   for (const Runs& r : folds) N += r.n;
-  PoolBlock k0(N * 8), k1(N * 8), v0(N * 8), v1(N * 8);
+  Workspace ws(s);
+  uint64_t* k[2] = {ws.take<uint64_t>(N), ws.take<uint64_t>(N)};
+  uint64_t* v[2] = {ws.take<uint64_t>(N), ws.take<uint64_t>(N)};
   uint64_t at = 0;
   for (const Runs& r : folds) {
     if (r.n == 0) continue;
-    HIP_CHECK(hipMemcpyAsync(k0.as<uint64_t>() + at, r.hash->ptr, r.n * 8, hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(v0.as<uint64_t>() + at, r.pack->ptr, r.n * 8, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(k[0] + at, r.hash, r.n * 8, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(v[0] + at, r.pack, r.n * 8, hipMemcpyDeviceToDevice, s));
     at += r.n;
   }
   HIP_CHECK(hipStreamSynchronize(s));
-  mark_synced(folds);
   folds.clear();
-  uint64_t* k[2] = {k0.as<uint64_t>(), k1.as<uint64_t>()};
-  uint64_t* v[2] = {v0.as<uint64_t>(), v1.as<uint64_t>()};
   // by hash, then stably by the group's bytes above the count: (group, hash) order
   dev.prof_begin(s);
   const int c1 = radix_sort_u64(k[0], k[1], v[0], v[1], N, dev.scratch, s);
   const int c2 = radix_sort_u64(v[c1], v[c1 ^ 1], k[c1], k[c1 ^ 1], N, dev.scratch, s, kBuildCountBits / 8, 8);
   dev.prof_end("index_build_merge", s);
   const int cur = c1 ^ c2;
-  Runs out = runs_of(k[cur], v[cur], N, kBuildCountBits, err, dev, s);
-  k0.synced = k1.synced = v0.synced = v1.synced = true;
-  return out;
+  return runs_of(k[cur], v[cur], N, kBuildCountBits, err, dev, s);
 }
 
 }  // namespace
@@ -129,7 +124,7 @@ ResidentIndex::ResidentIndex(const KmerMinHash& like, int input, const uint8_t* 
   auto& dev = Device::get();
   Engine& E = Engine::get();
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-  Runs result;
+  Runs result(s);
   if (any_long && G) {
     // the sources are exercised on batches of two records and more: a single record gets an empty one behind it
     std::vector<uint64_t> off1;
@@ -144,16 +139,17 @@ ResidentIndex::ResidentIndex(const KmerMinHash& like, int input, const uint8_t* 
     E.offbuf.ensure(((size_t)nrec + 1) * 8);
     E.grpbuf.ensure((size_t)nrec * per * 4);
     HIP_CHECK(hipMemcpyAsync(E.offbuf.ptr, off, ((size_t)nrec + 1) * 8, hipMemcpyHostToDevice, s));
-    PoolBlock d_groups(groups && per > 1 ? (size_t)nrec * 4 : 4), d_err(4);
+    Workspace ws(s);
+    uint32_t* d_groups = ws.take<uint32_t>(groups && per > 1 ? nrec : 1);
+    uint32_t* d_err = ws.take<uint32_t>(1);
     if (groups && per == 1) {
       HIP_CHECK(hipMemcpyAsync(E.grpbuf.ptr, groups, (size_t)nrec * 4, hipMemcpyHostToDevice, s));
     } else {
-      if (groups) HIP_CHECK(hipMemcpyAsync(d_groups.ptr, groups, (size_t)nrec * 4, hipMemcpyHostToDevice, s));
-      launch_index_build_groups(groups ? d_groups.as<uint32_t>() : nullptr, (uint64_t)nrec * per, per, E.grpbuf.as<uint32_t>(), s);
+      if (groups) HIP_CHECK(hipMemcpyAsync(d_groups, groups, (size_t)nrec * 4, hipMemcpyHostToDevice, s));
+      launch_index_build_groups(groups ? d_groups : nullptr, (uint64_t)nrec * per, per, E.grpbuf.as<uint32_t>(), s);
     }
-    HIP_CHECK(hipMemsetAsync(d_err.ptr, 0xff, 4, s));
+    HIP_CHECK(hipMemsetAsync(d_err, 0xff, 4, s));
     HIP_CHECK(hipStreamSynchronize(s));   // (the caller's arrays, or the vectors above, were read by the uploads)
-    d_groups.synced = true;
     SeqBatch b;
     b.seq = seq_dev; b.len = total_len; b.starts = E.offbuf.as<uint64_t>(); b.nrec = nrec; b.vend0 = total_len;
     BatchSource src(kind, like, b, off, s);
@@ -166,47 +162,39 @@ ResidentIndex::ResidentIndex(const KmerMinHash& like, int input, const uint8_t* 
     const uint64_t CH = want > 4.0e12L ? (uint64_t)4e12 : std::max<uint64_t>((uint64_t)want, 1);
     std::vector<Runs> folds;
     uint64_t held = 0;
-    try {
-      for (uint64_t lo = 0; lo < P; lo += CH) {
-        const uint64_t hi = std::min(P, lo + CH);
-        const uint64_t nc = E.run_chunk(src.ref(), lo, hi, like.max_hash, true, s);
-        if (nc == 0) continue;
-        dev.count("index_build_fold");
-        // (hash, position) -> (hash, group); sort by hash, then stably by group: (group, hash) order
-        launch_pos_to_group(E.cand_pos[0].as<uint64_t>(), nc, src.pos_table, src.pos_entries, E.grpbuf.as<uint32_t>(), s, 0);
-        const int c1 = radix_sort_u64(E.cand_hash[0].as<uint64_t>(), E.cand_hash[1].as<uint64_t>(), E.cand_pos[0].as<uint64_t>(),
-                                      E.cand_pos[1].as<uint64_t>(), nc, dev.scratch, s);
-        const int c2 = radix_sort_u64(E.cand_pos[c1].as<uint64_t>(), E.cand_pos[c1 ^ 1].as<uint64_t>(), E.cand_hash[c1].as<uint64_t>(),
-                                      E.cand_hash[c1 ^ 1].as<uint64_t>(), nc, dev.scratch, s, 0, 8);
-        const int cur = c1 ^ c2;
-        Runs f = runs_of(E.cand_hash[cur].as<uint64_t>(), E.cand_pos[cur].as<uint64_t>(), nc, 0, d_err.as<uint32_t>(), dev, s);
-        held += f.n;
-        folds.push_back(std::move(f));
-        if (held > kMaxPairs) {   // merged early: what is held stays below 2^32 elements, and the refusal is exact
-          Runs m = merge_runs(folds, d_err.as<uint32_t>(), dev, s);
-          if (m.n > kMaxPairs)
-            refuse("the result would hold more than 2^31 - 1 (group, hash) pairs (" + std::to_string(m.n) + " so far); build it in pieces");
-          held = m.n;
-          folds.push_back(std::move(m));
-        }
+    for (uint64_t lo = 0; lo < P; lo += CH) {
+      const uint64_t hi = std::min(P, lo + CH);
+      const uint64_t nc = E.run_chunk(src.ref(), lo, hi, like.max_hash, true, s);
+      if (nc == 0) continue;
+      dev.count("index_build_fold");
+      // (hash, position) -> (hash, group); sort by hash, then stably by group: (group, hash) order
+      launch_pos_to_group(E.cand_pos[0].as<uint64_t>(), nc, src.pos_table, src.pos_entries, E.grpbuf.as<uint32_t>(), s, 0);
+      const int c1 = radix_sort_u64(E.cand_hash[0].as<uint64_t>(), E.cand_hash[1].as<uint64_t>(), E.cand_pos[0].as<uint64_t>(),
+                                    E.cand_pos[1].as<uint64_t>(), nc, dev.scratch, s);
+      const int c2 = radix_sort_u64(E.cand_pos[c1].as<uint64_t>(), E.cand_pos[c1 ^ 1].as<uint64_t>(), E.cand_hash[c1].as<uint64_t>(),
+                                    E.cand_hash[c1 ^ 1].as<uint64_t>(), nc, dev.scratch, s, 0, 8);
+      const int cur = c1 ^ c2;
+      Runs f = runs_of(E.cand_hash[cur].as<uint64_t>(), E.cand_pos[cur].as<uint64_t>(), nc, 0, d_err, dev, s);
+      held += f.n;
+      folds.push_back(std::move(f));
+      if (held > kMaxPairs) {   // merged early: what is held stays below 2^32 elements, and the refusal is exact
+        Runs m = merge_runs(folds, d_err, dev, s);
+        if (m.n > kMaxPairs)
+          refuse("the result would hold more than 2^31 - 1 (group, hash) pairs (" + std::to_string(m.n) + " so far); build it in pieces");
+        held = m.n;
+        folds.push_back(std::move(m));
       }
-      if (src.have_error) throw src.err;   // the translated arm's UTF-8 panic
-      const bool merged = folds.size() > 1;
-      if (merged) { Runs m = merge_runs(folds, d_err.as<uint32_t>(), dev, s); folds.push_back(std::move(m)); }
-      uint32_t err = kBuildNoError;
-      HIP_CHECK(hipMemcpyAsync(&err, d_err.ptr, 4, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      d_err.synced = true;
-      if (err != kBuildNoError && has_abunds)
-        refuse("group " + std::to_string(err) + " holds a hash seen in 2^32 or more windows; a sketch of an index keeps 32 bits per abundance");
-      if (!folds.empty()) result = std::move(folds.back());
-      folds.clear();
-    } catch (...) {
-      (void)hipStreamSynchronize(s);
-      mark_synced(folds);
-      d_err.synced = true;
-      throw;
     }
+    if (src.have_error) throw src.err;   // the translated arm's UTF-8 panic
+    const bool merged = folds.size() > 1;
+    if (merged) { Runs m = merge_runs(folds, d_err, dev, s); folds.push_back(std::move(m)); }
+    uint32_t err = kBuildNoError;
+    HIP_CHECK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (err != kBuildNoError && has_abunds)
+      refuse("group " + std::to_string(err) + " holds a hash seen in 2^32 or more windows; a sketch of an index keeps 32 bits per abundance");
+    if (!folds.empty()) result = std::move(folds.back());
+    folds.clear();
   }
 
   const uint64_t S = result.n;
@@ -216,15 +204,14 @@ ResidentIndex::ResidentIndex(const KmerMinHash& like, int input, const uint8_t* 
   nums.ensure((size_t)n * 4 + 4);
   HIP_CHECK(hipMemsetAsync(nums.ptr, 0, (size_t)n * 4 + 4, s));
   if (S) {
-    HIP_CHECK(hipMemcpyAsync(hashes.ptr, result.hash->ptr, S * 8, hipMemcpyDeviceToDevice, s));
-    launch_index_build_finish(result.pack->as<uint64_t>(), (uint32_t)S, G, offsets.as<uint64_t>(), has_abunds ? abunds_dev.as<uint32_t>() : nullptr,
+    HIP_CHECK(hipMemcpyAsync(hashes.ptr, result.hash, S * 8, hipMemcpyDeviceToDevice, s));
+    launch_index_build_finish(result.pack, (uint32_t)S, G, offsets.as<uint64_t>(), has_abunds ? abunds_dev.as<uint32_t>() : nullptr,
                               dev, s);
     HIP_CHECK(hipMemcpyAsync(h_offsets.data(), offsets.ptr, h_offsets.size() * 8, hipMemcpyDeviceToHost, s));
   } else {
     HIP_CHECK(hipMemsetAsync(offsets.ptr, 0, h_offsets.size() * 8, s));
   }
   HIP_CHECK(hipStreamSynchronize(s));
-  if (S) result.hash->synced = result.pack->synced = true;
   if (h_offsets.front() != 0 || h_offsets.back() != S) throw_internal("index build: the group bounds do not span the runs");
   for (uint32_t g = 0; g < n; g++) max_len = std::max<uint32_t>(max_len, (uint32_t)(h_offsets[g + 1] - h_offsets[g]));
   dev.count("index_built");

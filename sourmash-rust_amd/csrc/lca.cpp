@@ -61,10 +61,10 @@ ResidentIndex::LcaView ResidentIndex::ensure_lca(const MatchDirectory& dir, Devi
     if (n) HIP_CHECK(hipMemcpyAsync(L->node_taxon.ptr, node_taxon.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     const LcaTaxonomy T{L->tax.as<uint64_t>(), L->node_taxon.as<uint32_t>()};
     const size_t longs = (size_t)dir.n_pairs / (kLcaOwnerLaneMax + 1) + 1;
-    PoolBlock d_long((longs + 1) * 4);
-    launch_lca_table(dir, T, L->hash_taxon.as<uint32_t>(), d_long.as<uint32_t>(), d_long.as<uint32_t>() + longs, dev, s);
+    Workspace ws(s);
+    uint32_t* d_long = ws.take<uint32_t>(longs + 1);
+    launch_lca_table(dir, T, L->hash_taxon.as<uint32_t>(), d_long, d_long + longs, dev, s);
     HIP_CHECK(hipStreamSynchronize(s));   // (`packed` is read by the upload)
-    d_long.synced = true;
     dev.count("lca_table_built");
     lca_dev = L.release();
   }
@@ -111,32 +111,33 @@ void ResidentIndex::lca_many_dev(const uint64_t* qh, const uint64_t* qoff, uint3
     dev.count("lca_chunk");
     for (uint32_t q = a; q < b; q++) coff[q + 1] = coff[q];
     if (T == 0) continue;
-    PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_tax((size_t)T * 4), d_key((size_t)T * 8), d_flag(((size_t)T + 1) * 4);
-    upload_chunk_offsets(qoff, a, b, &rel, d_qoff.as<uint32_t>(), s);
-    launch_lca_probe(dir, L.hash_taxon, qh + qoff[a], d_qoff.as<uint32_t>(), Qc, T, d_tax.as<uint32_t>(), d_key.as<uint64_t>(),
-                     d_flag.as<uint32_t>(), dev, s);
-    if (hash_taxon) HIP_CHECK(hipMemcpyAsync(hash_taxon + (qoff[a] - base0), d_tax.ptr, (size_t)T * 4, hipMemcpyDeviceToHost, s));
-    uint32_t* total_dev = d_flag.as<uint32_t>() + T;
+    Workspace ws(s);
+    uint32_t* d_qoff = ws.take<uint32_t>((size_t)Qc + 1);
+    uint32_t* d_tax = ws.take<uint32_t>(T);
+    uint64_t* d_key = ws.take<uint64_t>(T);
+    uint32_t* d_flag = ws.take<uint32_t>((size_t)T + 1);
+    upload_chunk_offsets(qoff, a, b, &rel, d_qoff, s);
+    launch_lca_probe(dir, L.hash_taxon, qh + qoff[a], d_qoff, Qc, T, d_tax, d_key, d_flag, dev, s);
+    if (hash_taxon) HIP_CHECK(hipMemcpyAsync(hash_taxon + (qoff[a] - base0), d_tax, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+    uint32_t* total_dev = d_flag + T;
     uint32_t nkeys = 0;
-    exclusive_scan_u32_dev(d_flag.as<uint32_t>(), T, total_dev, dev.scratch, s);
+    exclusive_scan_u32_dev(d_flag, T, total_dev, dev.scratch, s);
     HIP_CHECK(hipMemcpyAsync(&nkeys, total_dev, 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));   // (`rel` is read by the upload)
-    auto idle = [&] { d_qoff.synced = d_tax.synced = d_key.synced = d_flag.synced = true; };
-    if (nkeys == 0) { idle(); continue; }
+    if (nkeys == 0) continue;
     // the assigned keys compacted, sorted, run-length encoded: the runs are (query, taxon) ascending with their counts
-    PoolBlock k0((size_t)nkeys * 8), k1((size_t)nkeys * 8), d_uniq((size_t)nkeys * 8), d_starts(((size_t)nkeys + 1) * 4);
-    launch_lca_keys(d_key.as<uint64_t>(), d_flag.as<uint32_t>(), T, k0.as<uint64_t>(), dev, s);
-    const int cur = radix_sort_u64_keys(k0.as<uint64_t>(), k1.as<uint64_t>(), nkeys, dev.scratch, s, 0);
-    const uint32_t nruns = run_length_encode_u64((cur ? k1 : k0).as<uint64_t>(), nkeys, d_uniq.as<uint64_t>(), d_starts.as<uint32_t>(),
-                                                 dev.scratch, s);
-    uint64_t* d_cnt = (cur ? k0 : k1).as<uint64_t>();   // (the sort's other half is free now: nruns <= nkeys)
-    starts_to_counts(d_starts.as<uint32_t>(), nruns, nkeys, d_cnt, s);
+    uint64_t* k[2] = {ws.take<uint64_t>(nkeys), ws.take<uint64_t>(nkeys)};
+    uint64_t* d_uniq = ws.take<uint64_t>(nkeys);
+    uint32_t* d_starts = ws.take<uint32_t>((size_t)nkeys + 1);
+    launch_lca_keys(d_key, d_flag, T, k[0], dev, s);
+    const int cur = radix_sort_u64_keys(k[0], k[1], nkeys, dev.scratch, s, 0);
+    const uint32_t nruns = run_length_encode_u64(k[cur], nkeys, d_uniq, d_starts, dev.scratch, s);
+    uint64_t* d_cnt = k[cur ^ 1];   // (the sort's other half is free now: nruns <= nkeys)
+    starts_to_counts(d_starts, nruns, nkeys, d_cnt, s);
     h_keys.resize(nruns); h_cnt.resize(nruns);
-    HIP_CHECK(hipMemcpyAsync(h_keys.data(), d_uniq.ptr, (size_t)nruns * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(h_keys.data(), d_uniq, (size_t)nruns * 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)nruns * 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    idle();
-    k0.synced = k1.synced = d_uniq.synced = d_starts.synced = true;
     per.assign(Qc, 0);
     for (uint32_t r = 0; r < nruns; r++) {
       taxa.push_back((uint32_t)h_keys[r]);
@@ -166,11 +167,11 @@ void ResidentIndex::lca_records(const uint8_t* seq_dev, uint64_t total_len, cons
   auto tail = [&](const MatchDirectory& dir, const MatchFold& f) {
     Device& dev = Device::get();
     const LcaView L = ensure_lca(dir, dev, s);
-    PoolBlock d_out((size_t)f.nf * sizeof(LcaRow)), d_big((size_t)f.nf * 4 + 4);
-    launch_lca_records(L.tax, L.hash_taxon, f.rank, f.rows, f.rec_first, f.nf, d_out.as<LcaRow>(), d_big.as<uint32_t>(),
-                       d_big.as<uint32_t>() + f.nf, dev, s);
-    fetch_rows(d_out.ptr, rows + f.f0, f.nf, Engine::get(), s);
-    d_out.synced = d_big.synced = true;   // (fetch_rows has waited for the stream)
+    Workspace ws(s);
+    LcaRow* d_out = ws.take<LcaRow>(f.nf);
+    uint32_t* d_big = ws.take<uint32_t>((size_t)f.nf + 1);
+    launch_lca_records(L.tax, L.hash_taxon, f.rank, f.rows, f.rec_first, f.nf, d_out, d_big, d_big + f.nf, dev, s);
+    fetch_rows(d_out, rows + f.f0, f.nf, Engine::get(), s);
   };
   match_folds(seq_dev, total_len, off, nrec, false, s, blank, tail);
 }

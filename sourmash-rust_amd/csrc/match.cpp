@@ -5,7 +5,6 @@
 // match_folds, which lca.cpp's records route runs too; what follows the probe is the caller's `tail`.
 #include <algorithm>
 #include <cstring>
-#include <memory>
 #include <numeric>
 #include <string>
 
@@ -126,22 +125,23 @@ void ResidentIndex::match_folds(const uint8_t* seq_dev, uint64_t total_len, cons
                                                  dev.scratch, s, nullptr, nullptr, E.cand_pos[cur].as<uint64_t>(), E.uniq2.as<uint64_t>(), 0);
     if (nruns == 0) { blank(f0, r1); continue; }
 
-    PoolBlock d_rows((size_t)nf * sizeof(MatchRow)), d_first((size_t)nf * 4), d_pairs((size_t)nf * 8), d_rank((size_t)nruns * 4),
-        d_flag(want_hits ? ((size_t)nruns + 1) * 4 : 4);
-    HIP_CHECK(hipMemsetAsync(d_rows.ptr, 0, (size_t)nf * sizeof(MatchRow), s));
-    HIP_CHECK(hipMemsetAsync(d_first.ptr, 0xff, (size_t)nf * 4, s));
-    HIP_CHECK(hipMemsetAsync(d_pairs.ptr, 0, (size_t)nf * 8, s));
-    launch_match_probe(dir, E.uniq.as<uint64_t>(), E.uniq2.as<uint64_t>(), E.starts.as<uint32_t>(), nruns, (uint32_t)nc, f0,
-                       d_rows.as<MatchRow>(), d_first.as<uint32_t>(), d_pairs.as<unsigned long long>(), d_rank.as<uint32_t>(),
-                       want_hits ? d_flag.as<uint32_t>() : nullptr, dev, s);
+    Workspace ws(s);
     MatchFold f;
     f.f0 = f0; f.nf = nf; f.nruns = nruns;
     f.run_hash = E.uniq.as<uint64_t>();
-    f.rows = d_rows.as<MatchRow>(); f.rec_first = d_first.as<uint32_t>(); f.rec_pairs = d_pairs.as<unsigned long long>();
-    f.rank = d_rank.as<uint32_t>(); f.hit_flag = want_hits ? d_flag.as<uint32_t>() : nullptr;
+    f.rows = ws.take<MatchRow>(nf);
+    f.rec_first = ws.take<uint32_t>(nf);
+    f.rec_pairs = ws.take<unsigned long long>(nf);
+    f.rank = ws.take<uint32_t>(nruns);
+    uint32_t* d_flag = ws.take<uint32_t>(want_hits ? (size_t)nruns + 1 : 1);
+    f.hit_flag = want_hits ? d_flag : nullptr;
+    HIP_CHECK(hipMemsetAsync(f.rows, 0, (size_t)nf * sizeof(MatchRow), s));
+    HIP_CHECK(hipMemsetAsync(f.rec_first, 0xff, (size_t)nf * 4, s));
+    HIP_CHECK(hipMemsetAsync(f.rec_pairs, 0, (size_t)nf * 8, s));
+    launch_match_probe(dir, E.uniq.as<uint64_t>(), E.uniq2.as<uint64_t>(), E.starts.as<uint32_t>(), nruns, (uint32_t)nc, f0, f.rows, f.rec_first,
+                       f.rec_pairs, f.rank, f.hit_flag, dev, s);
     tail(dir, f);
     HIP_CHECK(hipStreamSynchronize(s));
-    d_rows.synced = d_first.synced = d_pairs.synced = d_rank.synced = d_flag.synced = true;
   }
 }
 
@@ -158,32 +158,31 @@ void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint
     Device& dev = Device::get();
     Engine& E = Engine::get();
     const uint32_t nf = f.nf;
-    PoolBlock d_big((size_t)nf * 4 + 4);
-    uint32_t* big_count = d_big.as<uint32_t>() + nf;
+    Workspace ws(s);
+    uint32_t* d_big = ws.take<uint32_t>((size_t)nf + 1);
+    uint32_t* big_count = d_big + nf;
     HIP_CHECK(hipMemsetAsync(big_count, 0, 4, s));
-    launch_match_tally(dir, f.rank, f.rows, f.rec_first, f.rec_pairs, nf, d_big.as<uint32_t>(), big_count, dev, s);
+    launch_match_tally(dir, f.rank, f.rows, f.rec_first, f.rec_pairs, nf, d_big, big_count, dev, s);
     uint32_t nbig = 0;
     HIP_CHECK(hipMemcpyAsync(&nbig, big_count, 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     if (nbig) {
       // the dense regime, in rounds of as many records as the budget holds counters for (n per record; one at least)
       std::vector<uint32_t> big(nbig);
-      HIP_CHECK(hipMemcpyAsync(big.data(), d_big.ptr, (size_t)nbig * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(big.data(), d_big, (size_t)nbig * 4, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       std::sort(big.begin(), big.end());   // (the kernel appended them in any order)
-      HIP_CHECK(hipMemcpyAsync(d_big.ptr, big.data(), (size_t)nbig * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_big, big.data(), (size_t)nbig * 4, hipMemcpyHostToDevice, s));
       const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g_match_pair_budget / n, 1), std::min<uint32_t>(nbig, 1u << 16));
-      PoolBlock slab((size_t)per * n * 4);
+      Workspace dense(s);
+      uint32_t* slab = dense.take<uint32_t>((size_t)per * n);
       for (uint32_t at = 0; at < nbig; at += per) {
-        launch_match_dense(dir, f.rank, f.rows, f.rec_first, d_big.as<uint32_t>() + at, std::min(per, nbig - at), n, slab.as<uint32_t>(),
-                           dev, s);
+        launch_match_dense(dir, f.rank, f.rows, f.rec_first, d_big + at, std::min(per, nbig - at), n, slab, dev, s);
         dev.count("match_dense_round");
       }
       HIP_CHECK(hipStreamSynchronize(s));   // (big is read by the upload above)
-      slab.synced = true;
     }
     fetch_rows(f.rows, rows + f.f0, nf, E, s);
-    d_big.synced = true;   // (fetch_rows has waited for the stream behind the last kernel that reads the list)
     if (want_hits) {
       uint32_t* total_dev = f.hit_flag + f.nruns;
       uint32_t nhit = 0;
@@ -191,13 +190,13 @@ void ResidentIndex::match(const uint8_t* seq_dev, uint64_t total_len, const uint
       HIP_CHECK(hipMemcpyAsync(&nhit, total_dev, 4, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       if (nhit) {
-        PoolBlock d_hits((size_t)nhit * 8);
-        launch_match_hit_scatter(f.run_hash, f.rank, f.hit_flag, f.nruns, d_hits.as<uint64_t>(), dev, s);
+        Workspace hits(s);
+        uint64_t* d_hits = hits.take<uint64_t>(nhit);
+        launch_match_hit_scatter(f.run_hash, f.rank, f.hit_flag, f.nruns, d_hits, dev, s);
         const size_t have = hit_hashes->size();
         hit_hashes->resize(have + nhit);
-        HIP_CHECK(hipMemcpyAsync(hit_hashes->data() + have, d_hits.ptr, (size_t)nhit * 8, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(hit_hashes->data() + have, d_hits, (size_t)nhit * 8, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        d_hits.synced = true;
       }
     }
   };

@@ -1079,6 +1079,7 @@ void KmerMinHash::add_proteins_host(const uint8_t* h_seq, uint64_t total, const 
   flush_pending();                  // (the queue's own flush uploads through seqbuf too: drain it before the buffer is reused)
   E.seqbuf.ensure(total + 64);
   HIP_CHECK(hipMemcpyAsync(E.seqbuf.ptr, h_seq, total, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemsetAsync(E.seqbuf.as<uint8_t>() + total, 0, 64, s));   // (see add_sequences_host)
   add_proteins_device(E.seqbuf.as<uint8_t>(), total, h_offsets, nrec, s);
 }
 
@@ -1093,6 +1094,9 @@ void KmerMinHash::add_sequences_host(const uint8_t* h_seq, uint64_t total, const
   if (!(num == 0 && max_hash > 0)) materialize();
   E.seqbuf.ensure(total + 64);
   uint8_t* d_seq = E.seqbuf.as<uint8_t>();
+  // The kernels load whole 16-byte granules, so they see what lies behind the batch.  A recycled block holds anything there, and a
+  // byte >= 0x80 sends the one-pass protein kernel to its two-pass path (same sketch, another route): the pad reads as zeros.
+  HIP_CHECK(hipMemsetAsync(d_seq + total, 0, 64, s));
 
   constexpr uint64_t kChunk = 128ull << 20;
   bool pipelined = force && !is_protein && ksize >= 1 && total >= 2 * kChunk && mode_of(*this) == kScaled;
@@ -1475,6 +1479,7 @@ void KmerMinHash::flush_pending() const {
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
   E.seqbuf.ensure(seqs.size() + 64);
   HIP_CHECK(hipMemcpyAsync(E.seqbuf.ptr, seqs.data(), seqs.size(), hipMemcpyHostToDevice, dev.stream()));
+  HIP_CHECK(hipMemsetAsync(E.seqbuf.as<uint8_t>() + seqs.size(), 0, 64, dev.stream()));   // (see add_sequences_host)
   // queued DNA records were cut at their first invalid byte when force was false, so force=true
   // reproduces both settings; protein ignores force (reference src/lib.rs:275-302)
   const_cast<KmerMinHash*>(this)->add_sequences_device(E.seqbuf.as<uint8_t>(), seqs.size(), offs.data(),

@@ -16,48 +16,16 @@ void check_nearest_k(uint32_t k) {
 
 SearchRow* ResidentIndex::nearest_dev(const uint64_t* qh, const uint64_t* qoff, uint32_t nq, uint32_t k, uint32_t metric, double threshold,
                                       uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s) {
-  check_search(metric, threshold);
+  check_search(metric, threshold);   // (search_chunks' first check again: the refusal of k comes behind it)
   check_nearest_k(k);
-  if (any_num) throw Error(kMsg, "nearest_many: the index holds a num sketch; only scaled sketches (num == 0) can be searched");
-  if (threshold_common == 0) threshold_common = 1;
-  check_query_offsets("nearest_many", qoff, nq, kQueryLimit32);
-  check_directory_size("nearest_many");
-  if (n > 0xffffffffu - 2 * kSearchTile) throw_internal("nearest_many: too many nodes");
-  const uint64_t total = nq ? qoff[nq] - qoff[0] : 0;
-  std::vector<uint64_t> roff((size_t)nq + 1, 0);
-  SearchRowsOut out("nearest_many");
-  auto finish = [&] {
-    SearchRow* r = out.release();   // (may refuse: nothing has been written then)
-    std::copy(roff.begin(), roff.end(), row_offsets);
-    return r;
-  };
-  if (n == 0 || total == 0) return finish();
-
-  std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-  const MatchDirectory dir = ensure_directory("nearest_many", dev, s);
-  if (dir.n_hashes == 0) return finish();
-  std::vector<uint32_t> rel, qrows;
-  const uint32_t tiles = (n + kSearchTile - 1) / kSearchTile;
-
-  for (uint32_t a = 0, b = 0; a < nq; a = b) {
-    b = search_many_chunk_end(qoff, a, nq, n, g_search_many_budget);
-    const uint32_t Qc = b - a;
-    const uint64_t T = qoff[b] - qoff[a];
-    const uint64_t base = roff[a];
-    for (uint32_t q = a; q < b; q++) roff[q + 1] = base;
-    dev.count("nearest_chunk");
-    if (T == 0) continue;
-    const size_t cells = (size_t)Qc * tiles;
-    PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_c((size_t)Qc * n * 4), d_tiles((cells + 1) * 4), d_at((cells + 1 + Qc + 1) * 4);
-    SearchChunk ck = search_chunk(qh, qoff, a, b, metric, threshold, threshold_common, self);
-    ck.qoff = d_qoff.as<uint32_t>();
-    ck.c = d_c.as<uint32_t>();
-    ck.tile_rows = d_tiles.as<uint32_t>();
+  std::vector<uint32_t> row_at;
+  auto tail = [&](const MatchDirectory& dir, const SearchChunk& ck, Workspace& ws, SearchRowsOut& out, uint32_t* starts) -> uint32_t {
+    const uint32_t Qc = ck.nq;
+    const size_t cells = (size_t)Qc * ck.tiles;
     NearestChunk nc;
     nc.k = k;
-    nc.cand_at = d_at.as<uint32_t>();
+    nc.cand_at = ws.take<uint32_t>(cells + 1 + Qc + 1);
     nc.row_at = nc.cand_at + cells + 1;
-    upload_chunk_offsets(qoff, a, b, &rel, d_qoff.as<uint32_t>(), s);
     HIP_CHECK(hipMemsetAsync(ck.c, 0, (size_t)Qc * n * 4, s));
     launch_search_many_probe(dir, ck, dev, s);
     launch_search_many_select(ck, dev, s);
@@ -66,24 +34,22 @@ SearchRow* ResidentIndex::nearest_dev(const uint64_t* qh, const uint64_t* qoff, 
     HIP_CHECK(hipMemcpyAsync(&sized[0], nc.cand_at + cells, 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&sized[1], nc.row_at + Qc, 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    d_qoff.synced = d_c.synced = d_tiles.synced = d_at.synced = true;
     const uint32_t C = sized[0], R = sized[1] - sized[0];
-    if (R == 0) continue;
+    if (R == 0) return 0;
     SearchRow* dst = out.room(R);   // (before the device rows: a refusal leaves only blocks that go back by themselves)
-    PoolBlock d_cand((size_t)C * 12), d_rows((size_t)R * sizeof(SearchRow));
-    nc.cand_v = d_cand.as<uint64_t>();
+    nc.cand_v = reinterpret_cast<uint64_t*>(ws.take<uint8_t>((size_t)C * 12));   // C u64 values, then C u32 nodes
     nc.cand_n = reinterpret_cast<uint32_t*>(nc.cand_v + C);
+    SearchRow* d_rows = ws.take<SearchRow>(R);
     launch_nearest_tile(ck, nc, dev, s);
-    launch_nearest_merge(ck, nc, d_rows.as<SearchRow>(), dev, s);
-    qrows.resize((size_t)Qc + 1);
-    HIP_CHECK(hipMemcpyAsync(dst, d_rows.ptr, (size_t)R * sizeof(SearchRow), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(qrows.data(), nc.row_at, ((size_t)Qc + 1) * 4, hipMemcpyDeviceToHost, s));
+    launch_nearest_merge(ck, nc, d_rows, dev, s);
+    row_at.resize((size_t)Qc + 1);
+    HIP_CHECK(hipMemcpyAsync(dst, d_rows, (size_t)R * sizeof(SearchRow), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(row_at.data(), nc.row_at, ((size_t)Qc + 1) * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    d_cand.synced = d_rows.synced = true;
-    out.len += R;
-    for (uint32_t j = 1; j <= Qc; j++) roff[a + j] = base + (qrows[j] - qrows[0]);
-  }
-  return finish();
+    for (uint32_t j = 1; j < Qc; j++) starts[j] = row_at[j] - row_at[0];
+    return R;
+  };
+  return search_chunks("nearest_many", "nearest_chunk", qh, qoff, nq, metric, threshold, threshold_common, self, row_offsets, dev, s, tail);
 }
 
 SearchRow* ResidentIndex::nearest_many(const KmerMinHash* const* queries, uint32_t nq, uint32_t k, uint32_t metric, double threshold,

@@ -35,7 +35,7 @@ void check_query_offsets(const char* who, const uint64_t* qoff, uint32_t nq, uin
 }
 
 QueryBatch::QueryBatch(const KmerMinHash* const* queries, uint32_t nq, const char* who, uint64_t limit, bool want_abunds, Device& dev)
-    : qoff((size_t)nq + 1, 0) {
+    : ws(dev.stream()), qoff((size_t)nq + 1, 0) {
   hipStream_t s = dev.stream();
   bool any_dev = false;
   uint64_t host_total = 0;
@@ -55,8 +55,8 @@ QueryBatch::QueryBatch(const KmerMinHash* const* queries, uint32_t nq, const cha
   }
   const uint64_t total = qoff[nq];
   const size_t words = with_abunds ? 2 : 1;
-  csr = std::make_unique<PoolBlock>(total * 8 * words);
-  uint64_t* d_h = csr->as<uint64_t>();
+  csr = ws.take<uint64_t>(total * words);
+  uint64_t* d_h = csr;
   uint64_t* d_a = d_h + total;   // (read only when with_abunds)
   // the host states, one layout for both routes: [the hashes of each | the abundances of each], one query after another
   std::vector<uint64_t> stage(host_total * words);
@@ -72,9 +72,8 @@ QueryBatch::QueryBatch(const KmerMinHash* const* queries, uint32_t nq, const cha
   if (!any_dev) {   // straight into place: the host states are the CSR
     if (!stage.empty()) HIP_CHECK(hipMemcpyAsync(d_h, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
   } else {
-    up = std::make_unique<PoolBlock>(stage.size() * 8);
-    if (!stage.empty()) HIP_CHECK(hipMemcpyAsync(up->ptr, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
-    const uint64_t* u_h = up->as<uint64_t>();
+    uint64_t* u_h = ws.take<uint64_t>(stage.size());
+    if (!stage.empty()) HIP_CHECK(hipMemcpyAsync(u_h, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, s));
     at = 0;
     for (uint32_t q = 0; q < nq; q++) {
       const KmerMinHash& Q = *queries[q];
@@ -94,8 +93,6 @@ QueryBatch::QueryBatch(const KmerMinHash* const* queries, uint32_t nq, const cha
     }
   }
   HIP_CHECK(hipStreamSynchronize(s));   // (`stage` is read by the upload)
-  csr->synced = true;
-  if (up) up->synced = true;
 }
 
 size_t append_chunk_offsets(const uint64_t* qoff, uint32_t a, uint32_t b, std::vector<uint32_t>* rel) {

@@ -1,5 +1,6 @@
 // records.cpp -- the records of one FASTA / FASTQ text parsed on the device: the host side of
-// parse_kernels.hip.  Its transient blocks never set `synced`: they wait for the device when they go back to the pool.
+// parse_kernels.hip.  Its transient blocks are PoolBlocks, not a Workspace's: they wait for the device when they go back to the
+// pool, as the blocks a Records object keeps do.
 #include <string>
 #include <vector>
 

@@ -33,17 +33,19 @@ SearchRow* SearchRowsOut::room(size_t more) {
   return p + len;
 }
 
-SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qoff, uint32_t nq, uint32_t metric, double threshold,
-                                          uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s) {
+SearchRow* ResidentIndex::search_chunks(const char* who, const char* chunk_counter, const uint64_t* qh, const uint64_t* qoff, uint32_t nq,
+                                        uint32_t metric, double threshold, uint32_t threshold_common, uint32_t self, uint64_t* row_offsets,
+                                        Device& dev, hipStream_t s, const SearchChunkTail& tail) {
+  const std::string name(who);
   check_search(metric, threshold);
-  if (any_num) throw Error(kMsg, "search_many: the index holds a num sketch; only scaled sketches (num == 0) can be searched");
+  if (any_num) throw Error(kMsg, name + ": the index holds a num sketch; only scaled sketches (num == 0) can be searched");
   if (threshold_common == 0) threshold_common = 1;
-  check_query_offsets("search_many", qoff, nq, kQueryLimit32);
-  check_directory_size("search_many");
-  if (n > 0xffffffffu - 2 * kSearchTile) throw_internal("search_many: too many nodes");
+  check_query_offsets(who, qoff, nq, kQueryLimit32);
+  check_directory_size(who);
+  if (n > 0xffffffffu - 2 * kSearchTile) throw_internal(name + ": too many nodes");
   const uint64_t total = nq ? qoff[nq] - qoff[0] : 0;
   std::vector<uint64_t> roff((size_t)nq + 1, 0);
-  SearchRowsOut out("search_many");
+  SearchRowsOut out(who);
   auto finish = [&] {
     SearchRow* r = out.release();   // (may refuse: nothing has been written then)
     std::copy(roff.begin(), roff.end(), row_offsets);
@@ -52,9 +54,9 @@ SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qo
   if (n == 0 || total == 0) return finish();
 
   std::lock_guard<std::recursive_mutex> lock(dev.mutex());
-  const MatchDirectory dir = ensure_directory("search_many", dev, s);
+  const MatchDirectory dir = ensure_directory(who, dev, s);
   if (dir.n_hashes == 0) return finish();
-  std::vector<uint32_t> rel, qrows;
+  std::vector<uint32_t> rel, starts;
   const uint32_t tiles = (n + kSearchTile - 1) / kSearchTile;
 
   for (uint32_t a = 0, b = 0; a < nq; a = b) {
@@ -63,30 +65,39 @@ SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qo
     const uint64_t T = qoff[b] - qoff[a];
     const uint64_t base = roff[a];
     for (uint32_t q = a; q < b; q++) roff[q + 1] = base;
-    dev.count("search_many_chunk");
+    dev.count(chunk_counter);
     if (T == 0) continue;
-    PoolBlock d_qoff(((size_t)Qc + 1) * 4), d_c((size_t)Qc * n * 4), d_tiles(((size_t)Qc * tiles + 1) * 4), d_qrows((size_t)Qc * 4);
+    Workspace ws(s);
     SearchChunk ck = search_chunk(qh, qoff, a, b, metric, threshold, threshold_common, self);
-    ck.qoff = d_qoff.as<uint32_t>();
-    ck.c = d_c.as<uint32_t>();
-    ck.tile_rows = d_tiles.as<uint32_t>();
-    upload_chunk_offsets(qoff, a, b, &rel, d_qoff.as<uint32_t>(), s);
-    const uint32_t R = search_chunk_rows(dir, ck, dev, s);
-    d_qoff.synced = d_c.synced = d_tiles.synced = d_qrows.synced = true;
-    if (R == 0) continue;
-    SearchRow* dst = out.room(R);   // (before the device rows: a refusal leaves only blocks that go back by themselves)
-    PoolBlock d_rows((size_t)R * sizeof(SearchRow));
-    launch_search_many_emit(ck, d_rows.as<SearchRow>(), d_qrows.as<uint32_t>(), dev, s);
-    qrows.resize(Qc);
-    HIP_CHECK(hipMemcpyAsync(dst, d_rows.ptr, (size_t)R * sizeof(SearchRow), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(qrows.data(), d_qrows.ptr, (size_t)Qc * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    d_rows.synced = true;
+    uint32_t* d_qoff = ws.take<uint32_t>((size_t)Qc + 1);
+    ck.qoff = d_qoff;
+    ck.c = ws.take<uint32_t>((size_t)Qc * n);
+    ck.tile_rows = ws.take<uint32_t>((size_t)Qc * tiles + 1);
+    upload_chunk_offsets(qoff, a, b, &rel, d_qoff, s);
+    starts.assign(Qc, 0);
+    const uint32_t R = tail(dir, ck, ws, out, starts.data());
     out.len += R;
-    for (uint32_t k = 1; k < Qc; k++) roff[a + k] = base + qrows[k];
+    for (uint32_t k = 1; k < Qc; k++) roff[a + k] = base + starts[k];
     roff[b] = base + R;
   }
   return finish();
+}
+
+SearchRow* ResidentIndex::search_many_dev(const uint64_t* qh, const uint64_t* qoff, uint32_t nq, uint32_t metric, double threshold,
+                                          uint32_t threshold_common, uint32_t self, uint64_t* row_offsets, Device& dev, hipStream_t s) {
+  auto tail = [&](const MatchDirectory& dir, const SearchChunk& ck, Workspace& ws, SearchRowsOut& out, uint32_t* starts) -> uint32_t {
+    uint32_t* d_qrows = ws.take<uint32_t>(ck.nq);
+    const uint32_t R = search_chunk_rows(dir, ck, dev, s);
+    if (R == 0) return 0;
+    SearchRow* dst = out.room(R);   // (before the device rows: a refusal leaves only blocks that go back by themselves)
+    SearchRow* d_rows = ws.take<SearchRow>(R);
+    launch_search_many_emit(ck, d_rows, d_qrows, dev, s);
+    HIP_CHECK(hipMemcpyAsync(dst, d_rows, (size_t)R * sizeof(SearchRow), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(starts, d_qrows, (size_t)ck.nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return R;
+  };
+  return search_chunks("search_many", "search_many_chunk", qh, qoff, nq, metric, threshold, threshold_common, self, row_offsets, dev, s, tail);
 }
 
 SearchRow* ResidentIndex::search_many(const KmerMinHash* const* queries, uint32_t nq, uint32_t metric, double threshold,
