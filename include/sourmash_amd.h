@@ -7,11 +7,15 @@
  * a reference symbol.  Plain pointers and sizes only; `stream` is a hipStream_t passed as
  * void*.  NULL = the library's own stream, which is first ordered after everything already queued
  * on the legacy default stream (where a caller without streams of its own produced the inputs);
- * every entry point returns with its device work complete -- with two stated exceptions,
+ * every entry point returns with its device work complete -- with three stated exceptions.  Two are
  * smh_collection_begin with world == 1 and smh_collection_finish without a gathered buffer (a single
  * owner's dictionary, which only later calls of this library use): their work is left queued, and
  * EVERY later entry point, on whatever stream it is given, is first ordered behind it (an event
  * recorded behind the open work; the library's shared scratch buffers are never rewritten under it).
+ * The third is smh_synth_dna_dev with a caller's stream: its one kernel is left queued on that stream
+ * and touches nothing but the caller's buffer, so work the caller queues behind it on the SAME stream
+ * (a sketching call given that stream) reads the finished bytes; anything else waits for the stream
+ * first.  With NULL it waits like every other call.
  * "dev" pointers are HIP device pointers.
  *
  * Error convention: same thread-local slot as sourmash.h; functions returning int return 0 on
@@ -937,7 +941,9 @@ uint64_t smh_lca_budget(void);
 void smh_set_grid_cap(uint32_t workgroups);
 uint32_t smh_grid_cap(void);
 
-/* deterministic synthetic DNA of SURVEY.md 8d written to device memory (benchmark input) */
+/* deterministic synthetic DNA of SURVEY.md 8d written to device memory (benchmark input).  With a caller's stream the kernel
+ * is left queued on it (the third exception of this header's opening contract: the benchmark queues it in front of
+ * smh_add_sequences_dev on the same stream); with NULL the buffer is complete on return. */
 int smh_synth_dna_dev(void *out_dev, uint64_t start, uint64_t len, uint64_t seed, uint64_t n_every,
                       void *stream);
 

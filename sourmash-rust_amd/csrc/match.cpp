@@ -120,7 +120,7 @@ void ResidentIndex::match_folds(const uint8_t* seq_dev, uint64_t total_len, cons
     const int c2 = radix_sort_u64(E.cand_pos[c1].as<uint64_t>(), E.cand_pos[c1 ^ 1].as<uint64_t>(), E.cand_hash[c1].as<uint64_t>(),
                                   E.cand_hash[c1 ^ 1].as<uint64_t>(), nc, dev.scratch, s, 0, 8);
     const int cur = c1 ^ c2;
-    E.uniq.ensure(nc * 8); E.uniq2.ensure(nc * 8); E.starts.ensure((nc + 1) * 4);
+    E.ensure_runs(nc); E.uniq2.ensure(nc * 8);
     const uint32_t nruns = run_length_encode_u64(E.cand_hash[cur].as<uint64_t>(), nc, E.uniq.as<uint64_t>(), E.starts.as<uint32_t>(),
                                                  dev.scratch, s, nullptr, nullptr, E.cand_pos[cur].as<uint64_t>(), E.uniq2.as<uint64_t>(), 0);
     if (nruns == 0) { blank(f0, r1); continue; }

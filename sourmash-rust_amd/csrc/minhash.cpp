@@ -424,6 +424,12 @@ uint64_t Engine::run_dna_chunk(const SeqBatch& b, uint32_t ksize, uint64_t seed,
   return run_chunk(&src, lo, hi, thr, true, s);
 }
 
+void Engine::ensure_runs(size_t n) {
+  const size_t m = std::max<size_t>(n, kSmallFoldMax);
+  uniq.ensure(m * 8);
+  starts.ensure((m + 1) * 4);
+}
+
 bool Engine::run_chunk_small(HashSourceRef src_, uint64_t lo, uint64_t hi, uint64_t thr, uint32_t expected, hipStream_t s,
                              DeviceSketch* out, uint64_t* n_out, uint64_t* cap_out) {
   HashSource& src = *static_cast<HashSource*>(src_);
@@ -433,8 +439,7 @@ bool Engine::run_chunk_small(HashSourceRef src_, uint64_t lo, uint64_t hi, uint6
   cand_hash[1].ensure(cap * 8);
   counter.ensure(8);
   misc.ensure(16);
-  uniq.ensure((size_t)kSmallFoldMax * 8);
-  starts.ensure(((size_t)kSmallFoldMax + 1) * 4);
+  ensure_runs(kSmallFoldMax);
   HIP_CHECK(hipMemsetAsync(counter.ptr, 0, 8, s));
   CandSink sink;
   sink.hash = cand_hash[0].as<uint64_t>();
@@ -482,8 +487,7 @@ void Engine::reduce_chunk(uint64_t n, uint32_t keep, bool have_pos, bool want_mi
                            have_pos ? cand_pos[0].as<uint64_t>() : nullptr,
                            have_pos ? cand_pos[1].as<uint64_t>() : nullptr, n, dev.scratch, s, 0, 8, pass_mask);
   out->sorted_buf = cur;
-  uniq.ensure(n * 8);
-  starts.ensure((n + 1) * 4);
+  ensure_runs(n);
   uint32_t nruns = run_length_encode_u64(cand_hash[cur].as<uint64_t>(), n, uniq.as<uint64_t>(),
                                          starts.as<uint32_t>(), dev.scratch, s);
   const uint32_t kept = (keep != 0 && nruns > keep) ? keep : nruns;
@@ -796,8 +800,7 @@ bool KmerMinHash::merge_on_device(const KmerMinHash& other) {
   int cur = radix_sort_u64(E.cand_hash[0].as<uint64_t>(), E.cand_hash[1].as<uint64_t>(),
                            both_tracked ? E.cand_pos[0].as<uint64_t>() : nullptr,
                            both_tracked ? E.cand_pos[1].as<uint64_t>() : nullptr, n, dev.scratch, s);
-  E.uniq.ensure(n * 8);
-  E.starts.ensure((n + 1) * 4);
+  E.ensure_runs(n);
   const uint32_t nruns = run_length_encode_u64(E.cand_hash[cur].as<uint64_t>(), n, E.uniq.as<uint64_t>(),
                                                E.starts.as<uint32_t>(), dev.scratch, s);
   std::vector<uint64_t> nm(nruns), na_sum;
@@ -1293,7 +1296,7 @@ void add_sequences_grouped(KmerMinHash* const* mhs, uint32_t n_mh, const uint8_t
                                   keep_pos ? kPosBits / 8 : 0, 8);
     const int cur = c1 ^ c2;
     fold_cur = cur;
-    E.uniq.ensure(n * 8); E.uniq2.ensure(n * 8); E.starts.ensure((n + 1) * 4);
+    E.ensure_runs(n); E.uniq2.ensure(n * 8);
     const uint32_t nruns = run_length_encode_u64(E.cand_hash[cur].as<uint64_t>(), n, E.uniq.as<uint64_t>(),
                                                  E.starts.as<uint32_t>(), dev.scratch, s, nullptr, nullptr,
                                                  E.cand_pos[cur].as<uint64_t>(), E.uniq2.as<uint64_t>(), keep_pos ? kPosBits : 0);

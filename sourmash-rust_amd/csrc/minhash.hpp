@@ -214,6 +214,12 @@ class Engine {
   void pack_sketches(const std::vector<const KmerMinHash*>& v, DeviceBuffer& data, DeviceBuffer& offs, SketchSet* out,
                      uint32_t* maxlen, std::vector<uint64_t>* h_off, hipStream_t s);
 
+  // uniq and starts sized for n runs -- and never for fewer than the small fold takes (kSmallFoldMax).  The folds hand these two
+  // blocks over to the sketch they leave in HBM (run_chunk_small, reduce_chunk) and take the sketch's in exchange, for a fresh
+  // sketch none at all; if the next caller sized them for its own few runs (a match of a handful of records), the small fold
+  // after it had to grow them, and a regrowth gives the old block back behind the device-wide wait: one such wait per
+  // alternation of the two calls, whichever threads they came from.
+  void ensure_runs(size_t n);
   DeviceBuffer cand_hash[2], cand_pos[2], counter, uniq, uniq2, starts, red_b, misc, seqbuf, offbuf, vendbuf, vendbuf2, grpbuf, union_tmp;
   PinnedBuffer pin_a, pin_b, pin_pair;
   DeviceBuffer pair_out;
