@@ -97,6 +97,64 @@ int smh_add_records(KmerMinHash *ptr, const SmhRecords *r, bool force);
 int smh_add_records_grouped(KmerMinHash *const *sketches, uint32_t n_sketches, const SmhRecords *r, const uint32_t *groups,
                             bool force);
 
+/* Blocked gzip (BGZF, what bgzip / htslib write) inflated ON THE DEVICE, in front of the parser.  The file
+ * is a chain of independent gzip members (RFC 1952), each at most 64 KiB compressed and at most 64 KiB inflated; a member's
+ * compressed size is in its header (extra subfield 'B' 'C', SLEN 2: BSIZE = member size - 1), its CRC-32 and inflated size
+ * (ISIZE) in its trailer.  The host finds every member by hopping headers; the device inflates all members at once, each
+ * into its own slice of the text.  Plain single-stream gzip has no such structure and stays with the caller.
+ *   smh_gzip_scan   walks the headers of data[0, len) and needs no device.  Per member: magic 1f 8b, CM 8; FEXTRA with any
+ *              subfields in front of and behind BC (the first BC counts); FNAME and FCOMMENT up to their NUL; FHCRC.  It
+ *              records the payload's offset and length, ISIZE, the CRC-32 and the running output offset (64 bits).  An empty
+ *              input is zero members; a member with ISIZE 0 (the BGZF end marker, anywhere in the chain) is a member like
+ *              any other and is decoded and checked.  Refusals are code 3 and name the member's index and byte offset as
+ *              "(member I at byte B)":  "the bytes are not gzip" (member 0 without the magic or with another CM);  "not
+ *              blocked gzip" (a member without BC: the caller may fall back to a host gzip);  "BSIZE runs past the end";
+ *              "header is cut short" (the fixed header, XLEN, a subfield, a name without NUL, or a header and trailer
+ *              that BSIZE has no room for);  "ISIZE above 65536";  "bytes trail after the last member" (anything behind a
+ *              member that does not begin another).
+ *   smh_gzip_member   payload offset and length, ISIZE and CRC-32 of member i (any pointer may be NULL).
+ *   smh_gzip_inflate_dev   data_dev: the len scanned bytes in HBM at any alignment; out_dev receives the text, out_cap
+ *              must be at least smh_gzip_inflated_len.  It follows the stream contract at the top of this file: the work is
+ *              ordered on `stream` (NULL: the library's own, behind the legacy default stream) and is complete on return.
+ *              verify_crc = 0 skips the CRC-32; ISIZE is always checked.  status_out (host, one byte per member, or NULL)
+ *              receives every member's status, also when the call fails.  A member stops at the FIRST rule it breaks, so
+ *              its status is deterministic:
+ *                 0  ok
+ *                 1  reserved block type (3)
+ *                 2  stored block whose LEN is not the complement of NLEN
+ *                 3  more than 286 literal/length codes or more than 30 distance codes announced
+ *                 4  code-length repeat 16 with nothing to repeat, or a repeat running past the announced lengths
+ *                 5  over-subscribed code set (code-length, literal/length or distance)
+ *                 6  incomplete code set; a literal/length or distance set of ONE code of length 1, and a distance set
+ *                    without any code, are legal; an incomplete code-length set never is
+ *                 7  no end-of-block code (symbol 256 has length 0)
+ *                 8  invalid symbol: literal/length 286 or 287, distance 30 or 31, or bits that no code of the set has
+ *                 9  distance reaching in front of the member's own output
+ *                10  input exhausted (a symbol is read a bit at a time: the payload ends before a code is complete)
+ *                11  output would pass ISIZE
+ *                12  stream ends with output below ISIZE
+ *                13  payload bytes left over after the final block (bits of its last byte are not bytes)
+ *                14  CRC-32 mismatch
+ *              Checks happen in stream order; in a dynamic header: the counts, the code-length set, the lengths and their
+ *              repeats, the end-of-block code, the literal/length set, the distance set.  A failing call returns code 3 and
+ *              names the LOWEST bad member, its byte offset and the reason.  On failure the contents of out_dev are
+ *              unspecified, but on ANY input no byte outside out[0, inflated_len) is written and no byte outside
+ *              data[0, len) is read.  len must be the length that was scanned.
+ *   smh_gzip_inflate   the same from host bytes: scans, uploads the compressed bytes once, inflates. */
+typedef struct SmhGzip SmhGzip;
+enum { SMH_INFLATE_OK = 0, SMH_INFLATE_BLOCK_TYPE = 1, SMH_INFLATE_STORED_LEN = 2, SMH_INFLATE_HEADER_COUNTS = 3, SMH_INFLATE_REPEAT = 4,
+       SMH_INFLATE_OVER_SUBSCRIBED = 5, SMH_INFLATE_INCOMPLETE = 6, SMH_INFLATE_NO_END_OF_BLOCK = 7, SMH_INFLATE_BAD_SYMBOL = 8,
+       SMH_INFLATE_DISTANCE = 9, SMH_INFLATE_INPUT = 10, SMH_INFLATE_OUTPUT_OVER = 11, SMH_INFLATE_OUTPUT_UNDER = 12,
+       SMH_INFLATE_LEFTOVER = 13, SMH_INFLATE_CRC = 14 };
+SmhGzip *smh_gzip_scan(const void *data, uint64_t len);
+void smh_gzip_free(SmhGzip *g);
+uint64_t smh_gzip_members(const SmhGzip *g);
+uint64_t smh_gzip_inflated_len(const SmhGzip *g);
+int smh_gzip_member(const SmhGzip *g, uint64_t i, uint64_t *payload_off, uint32_t *payload_len, uint32_t *isize, uint32_t *crc);
+int smh_gzip_inflate_dev(const SmhGzip *g, const void *data_dev, uint64_t len, void *out_dev, uint64_t out_cap, int verify_crc,
+                         uint8_t *status_out /* host, one per member, or NULL */, void *stream);
+int smh_gzip_inflate(const void *data, uint64_t len, void *out_dev, uint64_t out_cap, int verify_crc, uint8_t *status_out);
+
 /* Alphabets and amino-acid input.  The reference revision sketches protein only out of translated DNA
  * and in the 20-letter alphabet only; this library fixes the rest:
  *   Molecule   a sketch has one of DNA, protein, dayhoff, hp.  kmerminhash_new(prot = false / true) gives DNA / protein;

@@ -132,6 +132,13 @@ _SIGS = {
     "smh_records_offsets": (u64p, [C.c_void_p]),
     "smh_records_names": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_uint32)]),
     "smh_records_tile_bytes": (C.c_uint32, []),
+    "smh_gzip_scan": (C.c_void_p, [C.c_char_p, C.c_uint64]),
+    "smh_gzip_free": (None, [C.c_void_p]),
+    "smh_gzip_members": (C.c_uint64, [C.c_void_p]),
+    "smh_gzip_inflated_len": (C.c_uint64, [C.c_void_p]),
+    "smh_gzip_member": (C.c_int, [C.c_void_p, C.c_uint64, u64p, u32p, u32p, u32p]),
+    "smh_gzip_inflate_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint8), C.c_void_p]),
+    "smh_gzip_inflate": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint8)]),
     "smh_kmerminhash_new_molecule": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_bool]),
     "smh_kmerminhash_molecule": (C.c_int, [C.c_void_p]),
     "smh_add_protein": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64]),

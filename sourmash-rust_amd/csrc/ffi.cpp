@@ -551,6 +551,50 @@ int smh_records_names(const SmhRecords* r, uint64_t* start_out, uint32_t* len_ou
   });
 }
 
+// ------------------------------------------------------------------ blocked gzip (inflate.cpp)
+
+struct SmhGzip : smh::Gzip {};
+
+SmhGzip* smh_gzip_scan(const void* data, uint64_t len) {
+  return pad<SmhGzip*>([&] {
+    if (len) require(data, "data");
+    auto g = std::make_unique<SmhGzip>();
+    smh::gzip_scan(g.get(), static_cast<const uint8_t*>(data), len);
+    return g.release();
+  });
+}
+void smh_gzip_free(SmhGzip* g) { delete g; }
+uint64_t smh_gzip_members(const SmhGzip* g) { return g ? g->members.size() : 0; }
+uint64_t smh_gzip_inflated_len(const SmhGzip* g) { return g ? g->inflated : 0; }
+int smh_gzip_member(const SmhGzip* g, uint64_t i, uint64_t* payload_off, uint32_t* payload_len, uint32_t* isize, uint32_t* crc) {
+  return pad_code([&] {
+    require(g, "g");
+    if (i >= g->members.size()) throw Error(smh::kMsg, "gzip: member " + std::to_string(i) + " of " + std::to_string(g->members.size()));
+    const smh::InflateMember& m = g->members[i];
+    if (payload_off) *payload_off = m.payload_off;
+    if (payload_len) *payload_len = m.payload_len;
+    if (isize) *isize = m.isize;
+    if (crc) *crc = m.crc;
+  });
+}
+int smh_gzip_inflate_dev(const SmhGzip* g, const void* data_dev, uint64_t len, void* out_dev, uint64_t out_cap, int verify_crc,
+                         uint8_t* status_out, void* stream) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    require(g, "g");
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    smh::gzip_inflate_dev(*g, static_cast<const uint8_t*>(data_dev), len, static_cast<uint8_t*>(out_dev), out_cap, verify_crc != 0, status_out,
+                          dev.user_stream(stream), dev);
+  });
+}
+int smh_gzip_inflate(const void* data, uint64_t len, void* out_dev, uint64_t out_cap, int verify_crc, uint8_t* status_out) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    if (len) require(data, "data");
+    smh::gzip_inflate_host(static_cast<const uint8_t*>(data), len, static_cast<uint8_t*>(out_dev), out_cap, verify_crc != 0, status_out, dev);
+  });
+}
+
 int smh_add_records(KmerMinHash* ptr, const SmhRecords* r, bool force) {
   return pad_code([&] {
     require(ptr, "ptr"); require(r, "r");

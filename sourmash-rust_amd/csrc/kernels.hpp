@@ -1,7 +1,7 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
 // gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip, collapse_kernels.hip,
-// index_build_kernels.hip, filter_kernels.hip, nearest_kernels.hip).
+// index_build_kernels.hip, filter_kernels.hip, nearest_kernels.hip, inflate_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <memory>
+#include <vector>
 
 #include "device.hpp"
 
@@ -151,6 +152,32 @@ struct Records {
 };
 // fills a new *rec from a text in device memory (on the caller's `stream`) or in host memory (uploaded first, own stream)
 void parse_records(Records* rec, const void* text, bool text_on_host, uint64_t len, int format, void* stream, Device& dev);
+
+// --- inflate_kernels.hip, inflate.cpp --------------------------------------------------
+// Blocked gzip (BGZF) inflated on the device (the rules are in include/sourmash_amd.h, "Blocked gzip").
+constexpr uint32_t kInflateThreads = 256;    // four waves per workgroup, one member per wave and trip
+struct InflateMember {                       // one gzip member of the chain, as the host scan found it
+  uint64_t payload_off;                      // the DEFLATE stream: data[payload_off, payload_off + payload_len)
+  uint64_t out_off;                          // its text: out[out_off, out_off + isize)
+  uint32_t payload_len, isize, crc, pad;
+};
+// status[m] = the inflate::Reason of member m; *err (caller: all ones) is lowered to (m << 8 | reason) by every bad member.
+// Profile name inflate.
+void launch_inflate(const uint8_t* data, const InflateMember* members, uint64_t n_members, uint8_t* out, bool verify_crc, uint8_t* status,
+                    unsigned long long* err, Device& dev, hipStream_t s);
+// The member table of one chain (host only: no device is touched).
+struct Gzip {
+  std::vector<InflateMember> members;
+  std::vector<uint64_t> header_off;          // where each member starts in the file (error messages)
+  uint64_t len = 0, inflated = 0;            // bytes scanned; sum of the ISIZEs
+};
+void gzip_scan(Gzip* g, const uint8_t* data, uint64_t len);   // throws Error(kMsg)
+// data_dev: the len scanned bytes in device memory.  status_out: host, one byte per member, or null.  Returns with the work
+// complete; throws Error(kMsg) naming the lowest bad member (status_out is filled first).
+void gzip_inflate_dev(const Gzip& g, const uint8_t* data_dev, uint64_t len, uint8_t* out_dev, uint64_t out_cap, bool verify_crc,
+                      uint8_t* status_out, hipStream_t s, Device& dev);
+void gzip_inflate_host(const uint8_t* data, uint64_t len, uint8_t* out_dev, uint64_t out_cap, bool verify_crc, uint8_t* status_out,
+                       Device& dev);
 
 // --- sort.hip -----------------------------------------------------------------------
 // LSD radix sort, ping-pong between (k0,v0) and (k1,v1); returns which pair holds the result.
