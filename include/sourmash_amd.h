@@ -1166,6 +1166,93 @@ void smh_profile_enable(int on);
 void smh_profile_reset(void);
 int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);
 
+/* Signature JSON on the device.  A database arrives as `.sig` JSON, and nearly all of its bytes are decimal
+ * digits inside `mins` and `abundances`.  An SmhSignatures handle is made from such text in host or device memory: the DEVICE
+ * turns every number of every numeric array into u64 and keeps them in HBM in document order; the HOST receives the span table
+ * of those arrays and the text without them -- a skeleton of a few hundred bytes per signature -- which it parses with the
+ * JSON parser of the host loader, so keys, nulls, defaults, Q9, unknown fields and escapes mean what they mean there.  An index
+ * of chosen sketches is then built with device-to-device copies: nothing proportional to the hashes crosses to the host in
+ * either direction.  The rules (tests/sigscan_restatement.py states them as plain Python and is normative):
+ *   String state   a byte is inside a string if an odd number of unescaped '"' precede it; a '"' is escaped if it is directly
+ *              preceded by an odd-length run of '\'.
+ *   Span       every '[' outside a string opens a span: the maximal run of bytes from 0-9 ',' ' ' '\n' '\t' '\r' directly
+ *              behind it (it may be empty).  The k-th such '[' of the text owns span k.
+ *   Tokens     a token is a maximal digit run inside a span; its value is values[first_token[k] + i].  A token that breaks
+ *              a rule below has the value 0.
+ *   Status     of a span; the lowest rule broken decides and the offset of the offending byte is kept:
+ *              SMH_SIGSPAN_BAD_SYNTAX   a comma whose previous non-blank byte in the span is not a digit (the comma);  a token
+ *                                       whose previous non-blank byte in the span is a digit (its first digit);  a token of more
+ *                                       than one digit that starts with 0 (that 0);
+ *              SMH_SIGSPAN_OVERFLOW     a token above 2^64 - 1 (its first digit), which any token of more than 20 digits is: at
+ *                                       most 21 digits of a token are read, however long it is;
+ *              SMH_SIGSPAN_OPEN         the last non-blank byte is a comma;
+ *              SMH_SIGSPAN_CLOSED       otherwise.
+ *   Skeleton   the text with every span's bytes removed: behind every '[' stands its hole.
+ *   Host       the k-th '[' of the skeleton gets span k's tokens as its leading elements.  OPEN must be followed by a value;
+ *              CLOSED with tokens by ']'; CLOSED without tokens by either.  BAD_SYNTAX fails the document wherever the array
+ *              stands; OVERFLOW fails only an array read as u64 (`mins`, `abundances`: elsewhere such a number reads as a
+ *              float).  An array read as u64 must consist of its span alone.  A span that reaches its document's end fails
+ *              that document.
+ *   Deviation  a span that ends in a digit and is followed in the skeleton by '.', 'e' or 'E' is a float split in two.  The
+ *              call refuses the document with code 3, names the document and the byte offset and points to load_signatures.
+ *              No sourmash writer produces this.
+ * Documents: text[doc_offsets[d], doc_offsets[d + 1]) is document d, a JSON array of signatures as signatures_load_buffer takes
+ * one; doc_offsets == NULL: the whole text is one document (n_docs is not read).  The documents tile the text: doc_offsets
+ * ascend, doc_offsets[0] == 0 and doc_offsets[n_docs] == len, else code 3 (the scan enters byte 0 outside a string, so bytes
+ * that belong to no document would decide how the documents behind them are read).  A document is accepted exactly when
+ * signatures_load_buffer accepts it, apart from the deviation.  Where both refuse the code is 100004 (serde); the message begins
+ * "document D, byte B: " (B counts in the document's own text); the lowest failing document decides and no handle is returned.
+ * An accepted document's metadata equals the host loader's field for field (`num` follows Q9).
+ * Entries: one per sketch, in document order, then signature order, then sketch order -- the order signatures_load_buffer
+ * flattens them in.  smh_signatures_entry fills an SmhSigEntry; its strings are NUL-terminated, owned by the handle and valid
+ * while it lives; `md5sum` is the string as written (it is not verified).  smh_signatures_span gives one row of the span
+ * table (any pointer may be NULL); smh_signatures_values_dev the values in HBM, smh_signatures_tokens of them.
+ * smh_signatures_parse uploads host text once and parses it; *_parse_dev takes text already in HBM at any alignment, follows
+ * the stream contract at the top of this file and reads no byte outside [text, text + len).  Both return complete.
+ *   smh_signatures_index            node j = the `mins` of entry ids[j]: any order, repeats allowed, ids == NULL: every entry
+ *              (n_ids is not read).  The per-node parameters, whether the index has abundances (every node has them, as many as
+ *              hashes), their narrowing to 32 bits and the places of abundances of 2^32 or more are decided as smh_index_new
+ *              decides them, so the result answers every call as smh_index_new(signatures_load_buffer(...)) does.  One refusal
+ *              of its own, code 3: the hashes of every chosen sketch must be strictly ascending (the compare kernels assume
+ *              it); the message names the lowest node and position, and nothing is built.
+ *   smh_signatures_filter           the entries signatures_load_buffer's filter keeps (ksize 0: any; moltype NULL: any, else
+ *              "dna", "protein", "dayhoff" or "hp" in any case; any other string keeps none), ascending: returns how many and,
+ *              when ids_out is not NULL, writes them (room for smh_signatures_len entries always suffices).  Needs no device.
+ *   smh_signatures_index_filtered   smh_signatures_index of exactly those entries.
+ * Out of scope: zip containers, single-stream gzip on the device (BGZF goes through smh_gzip_inflate_dev in front of
+ * *_parse_dev), md5 verification, sorting unsorted `mins`, writing signatures.
+ * smh_sigscan_geometry: bytes per workgroup tile (cut on 16-byte boundaries of the address) and threads per workgroup (tests,
+ * tools).  Timers: "sigscan_summary", "sigscan_scan", "sigscan_compact", "sigscan_gather" (the checks of a gathered index; its
+ * copy is timed as "downsample_copy"); event counters: "signatures_parsed", "index_from_signatures". */
+typedef struct SmhSignatures SmhSignatures;
+enum { SMH_SIGSPAN_CLOSED = 0, SMH_SIGSPAN_OPEN = 1, SMH_SIGSPAN_OVERFLOW = 2, SMH_SIGSPAN_BAD_SYNTAX = 3 };
+typedef struct SmhSigEntry {
+  uint32_t document, signature, sketch;   /* where the sketch stands in the text */
+  uint32_t num, ksize;
+  uint64_t seed, max_hash;
+  int32_t molecule;                       /* SMH_MOLECULE_* */
+  uint8_t name_is_null, filename_is_null; /* the JSON null (or the key is missing): the string is then "" */
+  uint8_t has_abundances;                 /* `abundances` is present and not null */
+  uint8_t pad;
+  const char *name, *filename, *license, *sig_class, *md5sum;
+  uint64_t n_mins, n_abundances;          /* tokens of the two arrays */
+  uint64_t mins_span, abundances_span;    /* their rows in the span table (abundances_span: only with has_abundances) */
+} SmhSigEntry;
+SmhSignatures *smh_signatures_parse(const char *text, uint64_t len, const uint64_t *doc_offsets, uint32_t n_docs);
+SmhSignatures *smh_signatures_parse_dev(const void *text_dev, uint64_t len, const uint64_t *doc_offsets, uint32_t n_docs, void *stream);
+void smh_signatures_free(SmhSignatures *sigs);
+uint32_t smh_signatures_len(const SmhSignatures *sigs);      /* entries */
+uint64_t smh_signatures_spans(const SmhSignatures *sigs);
+uint64_t smh_signatures_tokens(const SmhSignatures *sigs);
+int smh_signatures_entry(const SmhSignatures *sigs, uint32_t i, SmhSigEntry *out);
+int smh_signatures_span(const SmhSignatures *sigs, uint64_t k, uint64_t *start, uint64_t *end, uint64_t *first_token, uint64_t *n_tokens,
+                        uint32_t *status, uint64_t *bad_offset /* all ones: none */);
+const uint64_t *smh_signatures_values_dev(const SmhSignatures *sigs);   /* device */
+SmhIndex *smh_signatures_index(const SmhSignatures *sigs, const uint32_t *ids, uint32_t n_ids);
+uint32_t smh_signatures_filter(const SmhSignatures *sigs, uint64_t ksize, const char *moltype, uint32_t *ids_out);
+SmhIndex *smh_signatures_index_filtered(const SmhSignatures *sigs, uint64_t ksize, const char *moltype);
+void smh_sigscan_geometry(uint32_t *tile_bytes, uint32_t *threads);
+
 #ifdef __cplusplus
 }
 #endif

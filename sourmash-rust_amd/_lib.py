@@ -50,6 +50,14 @@ class SmhLcaRow(C.Structure):
                 ("taxon", C.c_uint32), ("status", C.c_uint32)]
 
 
+class SmhSigEntry(C.Structure):
+    _fields_ = [("document", C.c_uint32), ("signature", C.c_uint32), ("sketch", C.c_uint32), ("num", C.c_uint32), ("ksize", C.c_uint32),
+                ("seed", C.c_uint64), ("max_hash", C.c_uint64), ("molecule", C.c_int32), ("name_is_null", C.c_uint8),
+                ("filename_is_null", C.c_uint8), ("has_abundances", C.c_uint8), ("pad", C.c_uint8), ("name", C.c_char_p),
+                ("filename", C.c_char_p), ("license", C.c_char_p), ("sig_class", C.c_char_p), ("md5sum", C.c_char_p),
+                ("n_mins", C.c_uint64), ("n_abundances", C.c_uint64), ("mins_span", C.c_uint64), ("abundances_span", C.c_uint64)]
+
+
 class SmhFilter(C.Structure):
     _fields_ = [("operand_mode", C.c_uint32), ("abund_out", C.c_uint32), ("min_abund", C.c_uint32), ("max_abund", C.c_uint32),
                 ("min_owners", C.c_uint32), ("max_owners", C.c_uint32)]
@@ -223,6 +231,19 @@ _SIGS = {
     "smh_index_filter": (C.c_void_p, [C.c_void_p, C.c_void_p, C.POINTER(SmhFilter)]),
     "smh_index_select": (C.c_void_p, [C.c_void_p, u32p, C.c_uint32]),
     "smh_filter_geometry": (None, [u32p, u32p, u32p]),
+    "smh_signatures_parse": (C.c_void_p, [C.c_char_p, C.c_uint64, u64p, C.c_uint32]),
+    "smh_signatures_parse_dev": (C.c_void_p, [C.c_void_p, C.c_uint64, u64p, C.c_uint32, C.c_void_p]),
+    "smh_signatures_free": (None, [C.c_void_p]),
+    "smh_signatures_len": (C.c_uint32, [C.c_void_p]),
+    "smh_signatures_spans": (C.c_uint64, [C.c_void_p]),
+    "smh_signatures_tokens": (C.c_uint64, [C.c_void_p]),
+    "smh_signatures_entry": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(SmhSigEntry)]),
+    "smh_signatures_span": (C.c_int, [C.c_void_p, C.c_uint64, u64p, u64p, u64p, u64p, u32p, u64p]),
+    "smh_signatures_values_dev": (C.c_void_p, [C.c_void_p]),
+    "smh_signatures_index": (C.c_void_p, [C.c_void_p, u32p, C.c_uint32]),
+    "smh_signatures_filter": (C.c_uint32, [C.c_void_p, C.c_uint64, C.c_char_p, u32p]),
+    "smh_signatures_index_filtered": (C.c_void_p, [C.c_void_p, C.c_uint64, C.c_char_p]),
+    "smh_sigscan_geometry": (None, [u32p, u32p]),
     "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
     "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
     "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),

@@ -12,6 +12,7 @@
 #include "index.hpp"
 #include "sbt.hpp"
 #include "signature.hpp"
+#include "sigscan.hpp"
 
 using smh::Error;
 using smh::require;
@@ -1059,6 +1060,91 @@ SmhIndex* smh_index_select(SmhIndex* index, const uint32_t* ids, uint32_t n_ids)
   });
 }
 void smh_filter_geometry(uint32_t* tile, uint32_t* operand_samples, uint32_t* threads) { smh::filter_geometry(tile, operand_samples, threads); }
+
+// ------------------------------------------------------------------ signature JSON on the device (sigscan.cpp)
+
+struct SmhSignatures : smh::Signatures {};
+static_assert(SMH_SIGSPAN_CLOSED == smh::sigscan::kClosed && SMH_SIGSPAN_OPEN == smh::sigscan::kOpen &&
+              SMH_SIGSPAN_OVERFLOW == smh::sigscan::kOverflow && SMH_SIGSPAN_BAD_SYNTAX == smh::sigscan::kBadSyntax,
+              "the statuses of the header are sigscan_core.hpp's");
+
+static SmhSignatures* signatures_parse(const void* text, const char* what, bool on_host, uint64_t len, const uint64_t* doc_offsets,
+                                       uint32_t n_docs, void* stream) {
+  return pad<SmhSignatures*>([&] {
+    auto& dev = smh::Device::get();
+    if (len) require(text, what);
+    auto sigs = std::make_unique<SmhSignatures>();
+    smh::parse_signatures(sigs.get(), text, on_host, len, doc_offsets, n_docs, stream, dev);
+    return sigs.release();
+  });
+}
+SmhSignatures* smh_signatures_parse(const char* text, uint64_t len, const uint64_t* doc_offsets, uint32_t n_docs) {
+  return signatures_parse(text, "text", true, len, doc_offsets, n_docs, nullptr);
+}
+SmhSignatures* smh_signatures_parse_dev(const void* text_dev, uint64_t len, const uint64_t* doc_offsets, uint32_t n_docs, void* stream) {
+  return signatures_parse(text_dev, "text_dev", false, len, doc_offsets, n_docs, stream);
+}
+void smh_signatures_free(SmhSignatures* sigs) { delete sigs; }
+uint32_t smh_signatures_len(const SmhSignatures* sigs) { return sigs ? (uint32_t)sigs->entries.size() : 0; }
+uint64_t smh_signatures_spans(const SmhSignatures* sigs) { return sigs ? sigs->spans.size() : 0; }
+uint64_t smh_signatures_tokens(const SmhSignatures* sigs) { return sigs ? sigs->n_tokens : 0; }
+const uint64_t* smh_signatures_values_dev(const SmhSignatures* sigs) { return sigs ? sigs->values_dev() : nullptr; }
+
+int smh_signatures_entry(const SmhSignatures* sigs, uint32_t i, SmhSigEntry* out) {
+  return pad_code([&] {
+    require(sigs, "sigs"); require(out, "out");
+    if (i >= sigs->entries.size()) throw Error(smh::kMsg, "signatures: entry " + std::to_string(i) + " of " + std::to_string(sigs->entries.size()));
+    const smh::SigEntry& e = sigs->entries[i];
+    memset(out, 0, sizeof *out);
+    out->document = e.document; out->signature = e.signature; out->sketch = e.sketch;
+    out->num = e.num; out->ksize = e.ksize; out->seed = e.seed; out->max_hash = e.max_hash; out->molecule = e.molecule;
+    out->name_is_null = !e.has_name; out->filename_is_null = !e.has_filename; out->has_abundances = e.has_abunds;
+    out->name = e.name.c_str(); out->filename = e.filename.c_str(); out->license = e.license.c_str();
+    out->sig_class = e.klass.c_str(); out->md5sum = e.md5sum.c_str();
+    out->n_mins = e.n_mins; out->n_abundances = e.n_abunds; out->mins_span = e.mins_span; out->abundances_span = e.abunds_span;
+  });
+}
+
+int smh_signatures_span(const SmhSignatures* sigs, uint64_t k, uint64_t* start, uint64_t* end, uint64_t* first_token, uint64_t* n_tokens,
+                        uint32_t* status, uint64_t* bad_offset) {
+  return pad_code([&] {
+    require(sigs, "sigs");
+    if (k >= sigs->spans.size()) throw Error(smh::kMsg, "signatures: span " + std::to_string(k) + " of " + std::to_string(sigs->spans.size()));
+    const smh::sigscan::SpanRow& r = sigs->spans[k];
+    if (start) *start = r.start;
+    if (end) *end = r.end;
+    if (first_token) *first_token = r.first_token;
+    if (n_tokens) *n_tokens = r.n_tokens;
+    if (status) *status = r.status;
+    if (bad_offset) *bad_offset = r.bad_off;
+  });
+}
+
+SmhIndex* smh_signatures_index(const SmhSignatures* sigs, const uint32_t* ids, uint32_t n_ids) {
+  return pad<SmhIndex*>([&] {
+    (void)smh::Device::get();
+    if (!sigs) throw Error(smh::kMsg, "index from signatures: sigs is NULL");
+    return new SmhIndex(*sigs, ids, n_ids);   // (ids == NULL: every entry, n_ids is not read)
+  });
+}
+uint32_t smh_signatures_filter(const SmhSignatures* sigs, uint64_t ksize, const char* moltype, uint32_t* ids_out) {
+  return pad<uint32_t>([&] {
+    require(sigs, "sigs");
+    const std::vector<uint32_t> ids = smh::signatures_filter(*sigs, (size_t)ksize, moltype);
+    if (ids_out) std::copy(ids.begin(), ids.end(), ids_out);
+    return (uint32_t)ids.size();
+  });
+}
+SmhIndex* smh_signatures_index_filtered(const SmhSignatures* sigs, uint64_t ksize, const char* moltype) {
+  return pad<SmhIndex*>([&] {
+    (void)smh::Device::get();
+    if (!sigs) throw Error(smh::kMsg, "index from signatures: sigs is NULL");
+    const std::vector<uint32_t> ids = smh::signatures_filter(*sigs, (size_t)ksize, moltype);
+    static const uint32_t none = 0;
+    return new SmhIndex(*sigs, ids.empty() ? &none : ids.data(), (uint32_t)ids.size());
+  });
+}
+void smh_sigscan_geometry(uint32_t* tile_bytes, uint32_t* threads) { smh::sigscan_geometry(tile_bytes, threads); }
 
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {

@@ -14,6 +14,7 @@
 namespace smh {
 
 struct SearchRowsOut;
+struct Signatures;   // sigscan.hpp
 
 struct ResidentIndex {
   DeviceBuffer hashes, offsets, nums;
@@ -75,6 +76,14 @@ struct ResidentIndex {
   // parameters and nums, the abundances wherever the parent has them (host or HBM), wide_pos / wide_node remapped and the
   // taxonomy with node_taxon permuted.  An id >= parent.n is refused (kMsg, the message names its position).
   ResidentIndex(ResidentIndex& parent, const uint32_t* ids, uint32_t n_ids);
+  // (sigscan.cpp) Node j holds the `mins` of sketch ids[j] of a signature text read on the device (the rules:
+  // include/sourmash_amd.h, "Signature JSON on the device"): any order, repeats allowed, ids null: every sketch in order.  The
+  // hashes are copied device to device out of the text's values (downsample_copy, starts permuted); the parameters, uniform,
+  // any_num, all_scaled, has_abunds, the narrowed abundances and wide_node / wide_pos are decided as the constructor from host
+  // nodes decides them, so the result answers every call as smh_index_new(load_signatures(...)) does.  The abundances stay in
+  // HBM (abunds_resident).  One refusal of its own (kMsg, nothing is built): a node whose hashes are not strictly ascending;
+  // the lowest node and position are named.
+  ResidentIndex(const Signatures& sigs, const uint32_t* ids, uint32_t n_ids);
   ~ResidentIndex();
   void enroll();   // into the registry of live indexes: the last step of every constructor
   // (collapse.cpp) the index as it is held: offsets (n + 1, from 0), hashes and abundances (offsets[n] each); any may be null.

@@ -179,6 +179,35 @@ void gzip_inflate_dev(const Gzip& g, const uint8_t* data_dev, uint64_t len, uint
 void gzip_inflate_host(const uint8_t* data, uint64_t len, uint8_t* out_dev, uint64_t out_cap, bool verify_crc, uint8_t* status_out,
                        Device& dev);
 
+// --- sigscan_kernels.hip ---------------------------------------------------------------
+// Signature JSON text in device memory -> the u64 values of its number arrays, one row per span, and the skeleton
+// (the rules are in include/sourmash_amd.h, "Signature JSON on the device", the automaton in sigscan_core.hpp).
+constexpr uint32_t kSigThreads = 256;
+constexpr uint32_t kSigTileBytes = 4096;   // tiles are cut on 16-byte boundaries of the address, as the parser's are
+struct SigTotals {
+  uint64_t skeleton, spans, tokens;        // bytes kept, spans opened, tokens started
+  uint32_t final_state, pad;               // the sigscan::State the text ends in
+};
+struct SigSpanDev {                        // one span as the compaction leaves it; the caller fills the rows with all ones first
+  uint64_t start, end, first_token, end_token;   // end stays all ones for a span that runs to the end of the text
+  uint64_t bad_syntax, overflow;                 // the lowest offending byte of either kind, all ones: none
+  uint32_t last_state, pad;
+};
+void sigscan_geometry(uint32_t* tile_bytes, uint32_t* threads);
+size_t sigscan_workspace_bytes(const void* text, uint64_t len);
+// passes 1 and 2 (profile names sigscan_summary, sigscan_scan): tile summaries and their scan into `workspace`; *totals_dev is written
+void launch_sigscan_scan(const uint8_t* text, uint64_t len, void* workspace, SigTotals* totals_dev, Device& dev, hipStream_t s);
+// pass 3 (sigscan_compact), with the totals read back: skeleton (totals.skeleton bytes), rows (totals.spans), values (totals.tokens)
+void launch_sigscan_compact(const uint8_t* text, uint64_t len, const void* workspace, const SigTotals& totals, uint8_t* skeleton,
+                            SigSpanDev* rows, uint64_t* values, Device& dev, hipStream_t s);
+// The checks of a CSR gathered from the values (hashes, offsets_dev: n + 1 from 0, total = offsets[n]): *err (caller: all ones) is
+// lowered to node << 32 | position by every hash not above its predecessor in the node.  out_abunds non-null: node v's abundances are
+// values[abund_src_dev[v] ..), narrowed to 32 bits (2^32 or more: all ones, counted in *n_wide, its place appended to wide_pos when
+// that is given and holds fewer than wide_cap).
+void launch_sigscan_gather_check(const uint64_t* hashes, const uint64_t* offsets_dev, uint32_t n, uint64_t total, const uint64_t* values,
+                                 const uint64_t* abund_src_dev, uint32_t* out_abunds, unsigned long long* err, unsigned long long* n_wide,
+                                 uint64_t* wide_pos, uint64_t wide_cap, Device& dev, hipStream_t s);
+
 // --- sort.hip -----------------------------------------------------------------------
 // LSD radix sort, ping-pong between (k0,v0) and (k1,v1); returns which pair holds the result.
 // Only the byte passes [first_pass, last_pass) are run (default: all eight): a stable sort by a bit

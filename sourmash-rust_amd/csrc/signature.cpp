@@ -4,6 +4,7 @@
 // the md5sum of ksize + decimal mins), 546-675 (Signature, load_signatures, PartialEq).  The
 // writer reproduces serde_json's compact output (field order of the Serialize impls, no spaces).
 #include "signature.hpp"
+#include "sigjson.hpp"
 
 #include <cctype>
 #include <cmath>
@@ -104,220 +105,33 @@ std::string sketch_md5(const KmerMinHash& mh) {
 }
 
 // ------------------------------------------------------------------------------------
-// minimal JSON document model + parser (what serde_json accepts for these types)
+// the JSON document model, its parser and the fields of a document: sigjson.hpp (shared with the device route, sigscan.cpp)
 namespace {
 
-struct JVal {
-  enum Kind { Null, Bool, UInt, NegInt, Float, Str, Arr, Obj } kind = Null;
-  bool b = false;
-  uint64_t u = 0;     // UInt: value; NegInt: magnitude
-  double f = 0.0;
-  std::string s;
-  std::vector<JVal> arr;
-  std::vector<std::pair<std::string, JVal>> obj;
-  const JVal* get(const char* key) const {
-    const JVal* found = nullptr;
-    for (auto& kv : obj) if (kv.first == key) found = &kv.second;  // serde: duplicate -> error; keep last
-    return found;
-  }
-};
+[[noreturn]] void rethrow(const JsonError& e) { throw Error(kSerdeError, e.message); }
 
-[[noreturn]] void serde_error(const std::string& m) { throw Error(kSerdeError, m); }
-
-struct JParser {
-  const char* p;
-  const char* end;
-  int depth = 0;
-  void ws() { while (p < end && (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r')) p++; }
-  [[noreturn]] void fail(const char* what) { serde_error(std::string("JSON error: ") + what); }
-
-  void parse_string(std::string& out) {
-    if (p >= end || *p != '"') fail("expected string");
-    p++;
-    while (true) {
-      if (p >= end) fail("EOF while parsing a string");
-      unsigned char c = (unsigned char)*p++;
-      if (c == '"') break;
-      if (c < 0x20) fail("control character in string");
-      if (c != '\\') { out.push_back((char)c); continue; }
-      if (p >= end) fail("EOF in escape");
-      char e = *p++;
-      switch (e) {
-        case '"': out.push_back('"'); break;
-        case '\\': out.push_back('\\'); break;
-        case '/': out.push_back('/'); break;
-        case 'b': out.push_back('\b'); break;
-        case 'f': out.push_back('\f'); break;
-        case 'n': out.push_back('\n'); break;
-        case 'r': out.push_back('\r'); break;
-        case 't': out.push_back('\t'); break;
-        case 'u': {
-          auto hex4 = [&]() {
-            if (end - p < 4) fail("EOF in \\u escape");
-            uint32_t v = 0;
-            for (int i = 0; i < 4; i++) {
-              char h = *p++;
-              v <<= 4;
-              if (h >= '0' && h <= '9') v |= h - '0';
-              else if (h >= 'a' && h <= 'f') v |= h - 'a' + 10;
-              else if (h >= 'A' && h <= 'F') v |= h - 'A' + 10;
-              else fail("invalid escape");
-            }
-            return v;
-          };
-          uint32_t cp = hex4();
-          if (cp >= 0xD800 && cp <= 0xDBFF) {
-            if (end - p < 2 || p[0] != '\\' || p[1] != 'u') fail("lone surrogate");
-            p += 2;
-            uint32_t lo = hex4();
-            if (lo < 0xDC00 || lo > 0xDFFF) fail("lone surrogate");
-            cp = 0x10000 + ((cp - 0xD800) << 10) + (lo - 0xDC00);
-          } else if (cp >= 0xDC00 && cp <= 0xDFFF) fail("lone surrogate");
-          if (cp < 0x80) out.push_back((char)cp);
-          else if (cp < 0x800) { out.push_back((char)(0xC0 | (cp >> 6))); out.push_back((char)(0x80 | (cp & 0x3F))); }
-          else if (cp < 0x10000) {
-            out.push_back((char)(0xE0 | (cp >> 12))); out.push_back((char)(0x80 | ((cp >> 6) & 0x3F)));
-            out.push_back((char)(0x80 | (cp & 0x3F)));
-          } else {
-            out.push_back((char)(0xF0 | (cp >> 18))); out.push_back((char)(0x80 | ((cp >> 12) & 0x3F)));
-            out.push_back((char)(0x80 | ((cp >> 6) & 0x3F))); out.push_back((char)(0x80 | (cp & 0x3F)));
-          }
-          break;
-        }
-        default: fail("invalid escape");
-      }
-    }
-  }
-
-  void parse_number(JVal& v) {
-    const char* s = p;
-    bool neg = false;
-    if (*p == '-') { neg = true; p++; }
-    if (p >= end || !isdigit((unsigned char)*p)) fail("invalid number");
-    bool is_float = false, overflow = false;
-    uint64_t acc = 0;
-    if (*p == '0') { p++; }
-    else while (p < end && isdigit((unsigned char)*p)) {
-      uint64_t d = (uint64_t)(*p - '0');
-      if (acc > (UINT64_MAX - d) / 10) overflow = true; else acc = acc * 10 + d;
-      p++;
-    }
-    if (p < end && *p == '.') { is_float = true; p++; if (p >= end || !isdigit((unsigned char)*p)) fail("invalid number"); while (p < end && isdigit((unsigned char)*p)) p++; }
-    if (p < end && (*p == 'e' || *p == 'E')) {
-      is_float = true; p++;
-      if (p < end && (*p == '+' || *p == '-')) p++;
-      if (p >= end || !isdigit((unsigned char)*p)) fail("invalid number");
-      while (p < end && isdigit((unsigned char)*p)) p++;
-    }
-    if (is_float || overflow) { v.kind = JVal::Float; v.f = strtod(std::string(s, p).c_str(), nullptr); }
-    else if (neg) { v.kind = JVal::NegInt; v.u = acc; v.f = -(double)acc; }
-    else { v.kind = JVal::UInt; v.u = acc; v.f = (double)acc; }
-  }
-
-  void parse_value(JVal& v) {
-    ws();
-    if (p >= end) fail("EOF while parsing a value");
-    if (++depth > 128) fail("recursion limit exceeded");
-    char c = *p;
-    if (c == '{') {
-      v.kind = JVal::Obj; p++; ws();
-      if (p < end && *p == '}') { p++; }
-      else while (true) {
-        ws();
-        std::string k; parse_string(k);
-        ws();
-        if (p >= end || *p != ':') fail("expected ':'");
-        p++;
-        v.obj.emplace_back(std::move(k), JVal());
-        parse_value(v.obj.back().second);
-        ws();
-        if (p < end && *p == ',') { p++; continue; }
-        if (p < end && *p == '}') { p++; break; }
-        fail("expected ',' or '}'");
-      }
-    } else if (c == '[') {
-      v.kind = JVal::Arr; p++; ws();
-      if (p < end && *p == ']') { p++; }
-      else while (true) {
-        v.arr.emplace_back();
-        parse_value(v.arr.back());
-        ws();
-        if (p < end && *p == ',') { p++; continue; }
-        if (p < end && *p == ']') { p++; break; }
-        fail("expected ',' or ']'");
-      }
-    } else if (c == '"') { v.kind = JVal::Str; parse_string(v.s); }
-    else if (c == 't' && end - p >= 4 && !memcmp(p, "true", 4)) { v.kind = JVal::Bool; v.b = true; p += 4; }
-    else if (c == 'f' && end - p >= 5 && !memcmp(p, "false", 5)) { v.kind = JVal::Bool; v.b = false; p += 5; }
-    else if (c == 'n' && end - p >= 4 && !memcmp(p, "null", 4)) { v.kind = JVal::Null; p += 4; }
-    else if (c == '-' || isdigit((unsigned char)c)) parse_number(v);
-    else fail("expected value");
-    depth--;
-  }
-};
-
-uint64_t want_uint(const JVal* v, const char* field, uint64_t maxv) {
-  if (!v) serde_error(std::string("missing field `") + field + "`");
-  if (v->kind != JVal::UInt || v->u > maxv) serde_error(std::string("invalid type for field `") + field + "`");
-  return v->u;
-}
-const std::string& want_str(const JVal* v, const char* field) {
-  if (!v) serde_error(std::string("missing field `") + field + "`");
-  if (v->kind != JVal::Str) serde_error(std::string("invalid type for field `") + field + "`: expected a string");
-  return v->s;
-}
-std::vector<uint64_t> want_u64_array(const JVal* v, const char* field) {
-  if (!v) serde_error(std::string("missing field `") + field + "`");
-  if (v->kind != JVal::Arr) serde_error(std::string("invalid type for field `") + field + "`: expected a sequence");
+std::vector<uint64_t> u64_elements(const JVal& v) {
   std::vector<uint64_t> out;
-  out.reserve(v->arr.size());
-  for (auto& e : v->arr) {
-    if (e.kind != JVal::UInt) serde_error(std::string("invalid type in `") + field + "`: expected u64");
-    out.push_back(e.u);
-  }
+  out.reserve(v.arr.size());
+  for (auto& e : v.arr) out.push_back(e.u);
   return out;
 }
 
 // reference src/lib.rs:104-139
-KmerMinHash sketch_from_json(const JVal& v) {
-  if (v.kind != JVal::Obj) serde_error("invalid type: expected struct TempSig");
+KmerMinHash sketch_from_fields(const SketchFields& f) {
+  static_assert(kMoleculeDNA == 0 && kMoleculeProtein == 1 && kMoleculeDayhoff == 2 && kMoleculeHp == 3, "sigjson.hpp's molecule numbers");
   KmerMinHash mh;
-  uint32_t num = (uint32_t)want_uint(v.get("num"), "num", UINT32_MAX);
-  mh.ksize = (uint32_t)want_uint(v.get("ksize"), "ksize", UINT32_MAX);
-  mh.seed = want_uint(v.get("seed"), "seed", UINT64_MAX);
-  mh.max_hash = want_uint(v.get("max_hash"), "max_hash", UINT64_MAX);
-  (void)want_str(v.get("md5sum"), "md5sum");
-  mh.mins = want_u64_array(v.get("mins"), "mins");
-  const JVal* ab = v.get("abundances");
-  if (ab && ab->kind != JVal::Null) { mh.has_abunds = true; mh.abunds = want_u64_array(ab, "abundances"); }
-  else { mh.has_abunds = false; mh.abunds.clear(); }
-  const std::string& mol = want_str(v.get("molecule"), "molecule");
-  // anything else reads as DNA (Q9); dayhoff / hp are this library's own (include/sourmash_amd.h "alphabets")
-  mh.molecule = mol == "protein" ? kMoleculeProtein : mol == "dayhoff" ? kMoleculeDayhoff : mol == "hp" ? kMoleculeHp : kMoleculeDNA;
+  mh.ksize = f.ksize;
+  mh.seed = f.seed;
+  mh.max_hash = f.max_hash;
+  mh.mins = u64_elements(*f.mins);
+  mh.has_abunds = f.has_abunds;
+  if (f.has_abunds) mh.abunds = u64_elements(*f.abunds);
+  else mh.abunds.clear();
+  mh.molecule = f.molecule;
   mh.is_protein = mh.molecule != kMoleculeDNA;
-  mh.num = mh.max_hash != 0 ? 0 : num;          // Q9
+  mh.num = f.num;
   return mh;
-}
-
-// reference src/lib.rs:546-577
-Signature signature_from_json(const JVal& v) {
-  if (v.kind != JVal::Obj) serde_error("invalid type: expected struct Signature");
-  Signature s;
-  if (const JVal* c = v.get("class")) s.klass = want_str(c, "class");
-  if (const JVal* e = v.get("email")) s.email = want_str(e, "email");
-  s.hash_function = want_str(v.get("hash_function"), "hash_function");
-  if (const JVal* f = v.get("filename")) { if (f->kind != JVal::Null) { s.has_filename = true; s.filename = want_str(f, "filename"); } }
-  if (const JVal* n = v.get("name")) { if (n->kind != JVal::Null) { s.has_name = true; s.name = want_str(n, "name"); } }
-  if (const JVal* l = v.get("license")) s.license = want_str(l, "license");
-  const JVal* sk = v.get("signatures");
-  if (!sk) serde_error("missing field `signatures`");
-  if (sk->kind != JVal::Arr) serde_error("invalid type for field `signatures`: expected a sequence");
-  for (auto& e : sk->arr) s.signatures.push_back(sketch_from_json(e));
-  if (const JVal* ver = v.get("version")) {
-    if (ver->kind == JVal::UInt || ver->kind == JVal::NegInt || ver->kind == JVal::Float) s.version = ver->f;
-    else serde_error("invalid type for field `version`: expected f64");
-  }
-  return s;
 }
 
 void json_escape(std::string& out, const std::string& s) {
@@ -415,16 +229,26 @@ std::string signatures_to_json(const std::vector<const Signature*>& v) {
 
 // reference src/lib.rs:585-591 from_reader: a JSON array of signatures
 std::vector<Signature> signatures_from_json(const char* data, size_t len) {
-  JParser ps{data, data + len};
-  JVal root;
-  ps.parse_value(root);
-  ps.ws();
-  if (ps.p != ps.end) serde_error("JSON error: trailing characters");
-  if (root.kind != JVal::Arr) serde_error("invalid type: expected a sequence");
-  std::vector<Signature> out;
-  out.reserve(root.arr.size());
-  for (auto& e : root.arr) out.push_back(signature_from_json(e));
-  return out;
+  try {
+    JVal root;
+    parse_document(data, len, nullptr, &root);
+    std::vector<Signature> out;
+    out.reserve(root.arr.size());
+    std::vector<KmerMinHash> sketches;
+    walk_document(root, nullptr,
+                  [&](size_t, size_t, const SketchFields& f) { sketches.push_back(sketch_from_fields(f)); },
+                  [&](size_t, const SignatureFields& f) {   // reference src/lib.rs:546-577
+                    Signature s;
+                    s.klass = f.klass; s.email = f.email; s.hash_function = f.hash_function;
+                    s.has_filename = f.has_filename; s.filename = f.filename;
+                    s.has_name = f.has_name; s.name = f.name;
+                    s.license = f.license; s.version = f.version;
+                    s.signatures = std::move(sketches);
+                    sketches.clear();
+                    out.push_back(std::move(s));
+                  });
+    return out;
+  } catch (const JsonError& e) { rethrow(e); }
 }
 
 // reference src/lib.rs:593-645 load_signatures: one Signature per sketch, filtered
@@ -457,49 +281,51 @@ bool signature_equal(const Signature& a, const Signature& b) {
 }
 
 SbtJson sbt_json_from(const char* data, size_t len) {
-  JParser ps{data, data + len};
-  JVal root;
-  ps.parse_value(root);
-  ps.ws();
-  if (ps.p != ps.end) serde_error("JSON error: trailing characters");
-  if (root.kind != JVal::Obj) serde_error("invalid type: expected struct SBTInfo");
-  SbtJson out;
-  out.d = (uint32_t)want_uint(root.get("d"), "d", UINT32_MAX);
-  out.version = (uint32_t)want_uint(root.get("version"), "version", UINT32_MAX);
-  const JVal* st = root.get("storage");
-  if (!st || st->kind != JVal::Obj) serde_error("missing field `storage`");
-  const JVal* args = st->get("args");
-  if (!args || args->kind != JVal::Obj) serde_error("missing field `args`");
-  out.storage_path = want_str(args->get("path"), "path");
-  const JVal* fac = root.get("factory");
-  if (!fac || fac->kind != JVal::Obj) serde_error("missing field `factory`");
-  out.factory_args = want_u64_array(fac->get("args"), "args");
-  auto entries = [&](const char* field, std::vector<SbtJsonEntry>& v, bool node) {
-    const JVal* m = root.get(field);
-    if (!m) serde_error(std::string("missing field `") + field + "`");
-    if (m->kind != JVal::Obj) serde_error(std::string("invalid type for field `") + field + "`: expected a map");
-    for (auto& kv : m->obj) {
-      SbtJsonEntry e;
-      char* endp = nullptr;
-      if (kv.first.empty() || !isdigit((unsigned char)kv.first[0])) serde_error("invalid map key: expected u64");
-      e.pos = strtoull(kv.first.c_str(), &endp, 10);
-      if (*endp) serde_error("invalid map key: expected u64");
-      e.filename = want_str(kv.second.get("filename"), "filename");
-      e.name = want_str(kv.second.get("name"), "name");
-      if (node) {
-        const JVal* md = kv.second.get("metadata");
-        if (!md || md->kind != JVal::Obj) serde_error("invalid type for field `metadata`: expected a map");
-        if (const JVal* mn = md->get("min_n_below")) {
-          e.has_min_n_below = true;
-          e.min_n_below = want_uint(mn, "min_n_below", UINT64_MAX);
+  try {
+    JParser ps{data, data + len};
+    JVal root;
+    ps.parse_value(root);
+    ps.ws();
+    if (ps.p != ps.end) serde_error("JSON error: trailing characters");
+    if (root.kind != JVal::Obj) serde_error("invalid type: expected struct SBTInfo");
+    SbtJson out;
+    out.d = (uint32_t)want_uint(root.get("d"), "d", UINT32_MAX);
+    out.version = (uint32_t)want_uint(root.get("version"), "version", UINT32_MAX);
+    const JVal* st = root.get("storage");
+    if (!st || st->kind != JVal::Obj) serde_error("missing field `storage`");
+    const JVal* args = st->get("args");
+    if (!args || args->kind != JVal::Obj) serde_error("missing field `args`");
+    out.storage_path = want_str(args->get("path"), "path");
+    const JVal* fac = root.get("factory");
+    if (!fac || fac->kind != JVal::Obj) serde_error("missing field `factory`");
+    out.factory_args = u64_elements(want_u64_array(fac->get("args"), "args", nullptr));
+    auto entries = [&](const char* field, std::vector<SbtJsonEntry>& v, bool node) {
+      const JVal* m = root.get(field);
+      if (!m) serde_error(std::string("missing field `") + field + "`");
+      if (m->kind != JVal::Obj) serde_error(std::string("invalid type for field `") + field + "`: expected a map");
+      for (auto& kv : m->obj) {
+        SbtJsonEntry e;
+        char* endp = nullptr;
+        if (kv.first.empty() || !isdigit((unsigned char)kv.first[0])) serde_error("invalid map key: expected u64");
+        e.pos = strtoull(kv.first.c_str(), &endp, 10);
+        if (*endp) serde_error("invalid map key: expected u64");
+        e.filename = want_str(kv.second.get("filename"), "filename");
+        e.name = want_str(kv.second.get("name"), "name");
+        if (node) {
+          const JVal* md = kv.second.get("metadata");
+          if (!md || md->kind != JVal::Obj) serde_error("invalid type for field `metadata`: expected a map");
+          if (const JVal* mn = md->get("min_n_below")) {
+            e.has_min_n_below = true;
+            e.min_n_below = want_uint(mn, "min_n_below", UINT64_MAX);
+          }
         }
+        v.push_back(std::move(e));
       }
-      v.push_back(std::move(e));
-    }
-  };
-  entries("nodes", out.nodes, true);
-  entries("leaves", out.leaves, false);
-  return out;
+    };
+    entries("nodes", out.nodes, true);
+    entries("leaves", out.leaves, false);
+    return out;
+  } catch (const JsonError& e) { rethrow(e); }
 }
 
 std::string read_file(const std::string& path) {

@@ -793,6 +793,45 @@ class ResidentIndex:
         idx.nodes = _OwnSketches(idx)
         return idx
 
+    # --- from signature JSON read on the device (additive ABI smh_signatures_*, smh_signatures_index*; the rules:
+    # include/sourmash_amd.h, "Signature JSON on the device")
+    @classmethod
+    def from_signatures(cls, source, ksize=0, moltype=None, ids=None, stream=None):
+        """An index of the sketches of signature JSON whose numbers were read on the device: the hashes go
+        from the text's values to the index device to device.  source: a signature.SignatureScan; bytes of one document; a
+        path or a list of paths (plain files and single-stream gzip are read on the host, concatenated and uploaded once; a
+        blocked-gzip file is inflated on the device).  ids: the scan's entries to take, any order, repeats allowed; None: the
+        entries load_signatures' filter keeps for ksize (0: any) and moltype (None: any).  The index answers every call as
+        ResidentIndex(load_signatures_buffer(...)) does; one refusal of its own (code 3): hashes that are not strictly
+        ascending.  `signatures` holds the chosen entries; `nodes` are the index's own sketches, read back when first asked."""
+        from .signature import SignatureScan, read_signature_text
+        L = lib()
+        if isinstance(source, SignatureScan):
+            scan = source
+        elif isinstance(source, (bytes, bytearray, memoryview)):
+            scan = SignatureScan.parse(source, stream=stream)
+        else:
+            data, offs = read_signature_text(source)
+            scan = SignatureScan.parse(data, offs, stream=stream)
+        entries = scan.entries
+        if ids is None:                                   # the filter exists once, in the library: its ids are the choice
+            v = np.zeros(max(len(entries), 1), dtype=np.uint32)
+            kept = call(L.smh_signatures_filter, scan._p, int(ksize), moltype.encode() if moltype else None, v.ctypes.data_as(u32p))
+            v = v[:kept]
+        else:
+            wide = np.asarray(ids, dtype=np.int64).reshape(-1)
+            if wide.size and (wide.min() < 0 or wide.max() > 0xFFFFFFFF):
+                raise ValueError("from_signatures: ids are ints in [0, 2^32)")
+            v = np.ascontiguousarray(wide, dtype=np.uint32)
+        chosen = [int(i) for i in v]
+        h = call(L.smh_signatures_index, scan._p, (v if v.size else np.zeros(1, np.uint32)).ctypes.data_as(u32p), int(v.size))
+        idx = cls((), _handle=h)
+        idx.signatures = [entries[i] for i in chosen]
+        track = idx.has_abundances
+        idx._node_templates = [(e.num, e.ksize, e.molecule, e.seed, e.max_hash, track) for e in idx.signatures]
+        idx.nodes = _OwnSketches(idx)
+        return idx
+
     @classmethod
     def concat(cls, parts):
         """A new index whose nodes are those of parts[0], then parts[1], ... (smh_index_concat): device-to-device copies, no
