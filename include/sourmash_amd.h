@@ -1220,7 +1220,7 @@ int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);
  *              when ids_out is not NULL, writes them (room for smh_signatures_len entries always suffices).  Needs no device.
  *   smh_signatures_index_filtered   smh_signatures_index of exactly those entries.
  * Out of scope: zip containers, single-stream gzip on the device (BGZF goes through smh_gzip_inflate_dev in front of
- * *_parse_dev), md5 verification, sorting unsorted `mins`, writing signatures.
+ * *_parse_dev), md5 verification, sorting unsorted `mins`.  (Writing signatures: the next section.)
  * smh_sigscan_geometry: bytes per workgroup tile (cut on 16-byte boundaries of the address) and threads per workgroup (tests,
  * tools).  Timers: "sigscan_summary", "sigscan_scan", "sigscan_compact", "sigscan_gather" (the checks of a gathered index; its
  * copy is timed as "downsample_copy"); event counters: "signatures_parsed", "index_from_signatures". */
@@ -1252,6 +1252,44 @@ SmhIndex *smh_signatures_index(const SmhSignatures *sigs, const uint32_t *ids, u
 uint32_t smh_signatures_filter(const SmhSignatures *sigs, uint64_t ksize, const char *moltype, uint32_t *ids_out);
 SmhIndex *smh_signatures_index_filtered(const SmhSignatures *sigs, uint64_t ksize, const char *moltype);
 void smh_sigscan_geometry(uint32_t *tile_bytes, uint32_t *threads);
+
+/* Signature JSON written on the device: the way out of a resident index.  An SmhSigText handle owns, in HBM,
+ * the byte string signatures_save_buffer gives for the index's own sketches (what smh_index_read returns, with the per-node
+ * parameters the index holds), each wrapped in a default Signature with the given name and filename; only 16 bytes per node
+ * cross to the host, and the skeleton of a few hundred bytes per node goes the other way.  The rules
+ * (tests/sigtext_restatement.py states them as plain Python and is normative):
+ *   Text       the documents one after another, no separator; a document is [SIG,SIG,...] of its nodes, an empty one is [];
+ *              compact serde_json: no blanks, no newline.
+ *   SIG        {"class":"sourmash_signature","email":"","hash_function":"0.murmur64","filename":F,"name":N,"license":"CC0",
+ *              "signatures":[{"num":..,"ksize":..,"seed":..,"max_hash":..,"mins":[h,h,...],"md5sum":"<32 lower-case hex>"
+ *              [,"abundances":[a,a,...]],"molecule":"DNA|protein|dayhoff|hp"}],"version":0.4}
+ *   F, N       null or the string, escaped as the host writer escapes it (one function, sigjson.hpp's json_escape).
+ *   abundances present on every node exactly when smh_index_has_abundances; the index's u32 values.
+ *   md5sum     the MD5 of the decimal ksize followed by the decimal hashes, no separator (an empty node: of the ksize alone).
+ * names / filenames: NULL = every one null; else n pointers, a NULL element = JSON null.  doc_starts: NULL = one document of all
+ * nodes (n_docs is not read); else n_docs + 1 ascending node numbers, [0] == 0, [n_docs] == n.  Refusals, code 3 with a message
+ * that begins "sigtext:", before anything is allocated: a bad doc_starts (the entry is named); an index that holds an abundance
+ * of 2^32 or more (the node is named: the index no longer has its value).  Without a device: code 2.  Both calls return
+ * complete, on the library's own stream.
+ * smh_sigtext_doc_offsets writes documents + 1 offsets from 0 (what smh_signatures_parse_dev takes); smh_sigtext_dev is the text
+ * in HBM, owned by the handle and valid while it lives; smh_sigtext_read copies text[offset, offset + len) to the host (a range
+ * outside the text: code 3).  smh_index_md5 writes the 16 n digest bytes alone and builds no text.
+ * Out of scope: compression of the output, zip containers, several sketches in one signature, `email`, `license` or `version`
+ * other than the defaults.
+ * smh_sigtext_geometry: values per workgroup tile of the measure and emit passes, threads per workgroup, values a wave formats
+ * per step of the md5 pass (tests, tools).  Timers: "sigtext_measure", "sigtext_scan", "sigtext_emit", "sigtext_md5"; event
+ * counter: "index_sigtext". */
+typedef struct SmhSigText SmhSigText;
+SmhSigText *smh_index_sigtext(SmhIndex *index, const char *const *names, const char *const *filenames, const uint32_t *doc_starts,
+                              uint32_t n_docs);
+uint64_t smh_sigtext_len(const SmhSigText *t);
+uint32_t smh_sigtext_documents(const SmhSigText *t);
+int smh_sigtext_doc_offsets(const SmhSigText *t, uint64_t *out);   /* documents + 1, from 0 */
+const void *smh_sigtext_dev(const SmhSigText *t);                  /* device */
+int smh_sigtext_read(const SmhSigText *t, uint64_t offset, uint64_t len, char *out);
+void smh_sigtext_free(SmhSigText *t);
+int smh_index_md5(SmhIndex *index, uint8_t *out);                  /* 16 n bytes */
+void smh_sigtext_geometry(uint32_t *values_per_tile, uint32_t *threads, uint32_t *md5_values_per_step);
 
 #ifdef __cplusplus
 }

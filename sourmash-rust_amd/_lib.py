@@ -244,6 +244,15 @@ _SIGS = {
     "smh_signatures_filter": (C.c_uint32, [C.c_void_p, C.c_uint64, C.c_char_p, u32p]),
     "smh_signatures_index_filtered": (C.c_void_p, [C.c_void_p, C.c_uint64, C.c_char_p]),
     "smh_sigscan_geometry": (None, [u32p, u32p]),
+    "smh_index_sigtext": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), u32p, C.c_uint32]),
+    "smh_sigtext_len": (C.c_uint64, [C.c_void_p]),
+    "smh_sigtext_documents": (C.c_uint32, [C.c_void_p]),
+    "smh_sigtext_doc_offsets": (C.c_int, [C.c_void_p, u64p]),
+    "smh_sigtext_dev": (C.c_void_p, [C.c_void_p]),
+    "smh_sigtext_read": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "smh_sigtext_free": (None, [C.c_void_p]),
+    "smh_index_md5": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "smh_sigtext_geometry": (None, [u32p, u32p, u32p]),
     "smh_index_has_abundances": (C.c_bool, [C.c_void_p]),
     "smh_index_norms2": (C.c_int, [C.c_void_p, u64p]),
     "smh_index_angular": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f64p, f64p]),

@@ -13,6 +13,7 @@
 #include "sbt.hpp"
 #include "signature.hpp"
 #include "sigscan.hpp"
+#include "sigtext.hpp"
 
 using smh::Error;
 using smh::require;
@@ -1145,6 +1146,55 @@ SmhIndex* smh_signatures_index_filtered(const SmhSignatures* sigs, uint64_t ksiz
   });
 }
 void smh_sigscan_geometry(uint32_t* tile_bytes, uint32_t* threads) { smh::sigscan_geometry(tile_bytes, threads); }
+
+// ------------------------------------------------------------------ signature JSON written on the device (sigtext.cpp)
+
+struct SmhSigText : smh::SigText {};
+
+SmhSigText* smh_index_sigtext(SmhIndex* index, const char* const* names, const char* const* filenames, const uint32_t* doc_starts,
+                              uint32_t n_docs) {
+  return pad<SmhSigText*>([&] {
+    auto& dev = smh::Device::get();
+    if (!index) throw Error(smh::kMsg, "sigtext: index is NULL");   // (MSG like every refusal of this call)
+    auto t = std::make_unique<SmhSigText>();
+    smh::index_sigtext(t.get(), *index, names, filenames, doc_starts, n_docs, dev);
+    return t.release();
+  });
+}
+uint64_t smh_sigtext_len(const SmhSigText* t) { return t ? t->len : 0; }
+uint32_t smh_sigtext_documents(const SmhSigText* t) { return t && !t->doc_offsets.empty() ? (uint32_t)(t->doc_offsets.size() - 1) : 0; }
+int smh_sigtext_doc_offsets(const SmhSigText* t, uint64_t* out) {
+  return pad_code([&] {
+    require(t, "text"); require(out, "out");
+    std::copy(t->doc_offsets.begin(), t->doc_offsets.end(), out);
+  });
+}
+const void* smh_sigtext_dev(const SmhSigText* t) { return t ? t->text_dev() : nullptr; }
+int smh_sigtext_read(const SmhSigText* t, uint64_t offset, uint64_t len, char* out) {
+  return pad_code([&] {
+    require(t, "text");
+    if (offset > t->len || len > t->len - offset)
+      throw Error(smh::kMsg, "sigtext: bytes " + std::to_string(offset) + " + " + std::to_string(len) + " of a text of " + std::to_string(t->len));
+    if (!len) return;
+    require(out, "out");
+    auto& dev = smh::Device::get();
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    HIP_CHECK(hipMemcpyAsync(out, t->text_dev() + offset, len, hipMemcpyDeviceToHost, dev.stream()));
+    HIP_CHECK(hipStreamSynchronize(dev.stream()));
+  });
+}
+void smh_sigtext_free(SmhSigText* t) { delete t; }
+int smh_index_md5(SmhIndex* index, uint8_t* out) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    if (!index) throw Error(smh::kMsg, "sigtext: index is NULL");
+    if (index->n) require(out, "out");
+    smh::index_md5(*index, out, dev);
+  });
+}
+void smh_sigtext_geometry(uint32_t* values_per_tile, uint32_t* threads, uint32_t* md5_values_per_step) {
+  smh::sigtext_geometry(values_per_tile, threads, md5_values_per_step);
+}
 
 int smh_index_compare(SmhIndex* rows, SmhIndex* cols, double* jaccard, uint64_t* common, uint64_t* size,
                       uint64_t* count_common, double* containment) {

@@ -208,6 +208,42 @@ void launch_sigscan_gather_check(const uint64_t* hashes, const uint64_t* offsets
                                  const uint64_t* abund_src_dev, uint32_t* out_abunds, unsigned long long* err, unsigned long long* n_wide,
                                  uint64_t* wide_pos, uint64_t wide_cap, Device& dev, hipStream_t s);
 
+// --- sigtext_kernels.hip ---------------------------------------------------------------
+// A resident index -> the decimal text of its arrays and every node's md5 (the rules are in
+// include/sourmash_amd.h, "Signature JSON written on the device", the shared pieces in sigtext_core.hpp).
+constexpr uint32_t kSigTextThreads = 256;
+constexpr uint32_t kSigTextTile = 1024;     // values per workgroup trip of the measure and emit passes (four per thread)
+constexpr uint32_t kSigTextMd5Step = 64;    // values a wave formats between two runs of the block function
+inline uint64_t sigtext_tiles(uint64_t total) { return (total + kSigTextTile - 1) / kSigTextTile; }
+struct SigTextPass {                        // the CSR as the kernels read it: values counted from off[0]
+  const uint64_t* hashes = nullptr;         // total of them (the pointer stands at element off[0])
+  const uint32_t* abunds = nullptr;         // likewise; null: an index without abundances (tile_a, node_a are then not touched)
+  uint64_t total = 0;
+  const uint64_t* off = nullptr;            // n + 1 node boundaries, device
+  uint32_t n = 0;
+  uint64_t *tile_h = nullptr, *tile_a = nullptr;   // sigtext_tiles(total) + 1 each: digit sums per tile, scanned in place (exclusive)
+  uint64_t *node_h = nullptr, *node_a = nullptr;   // n + 1 each: the digit prefix at every node boundary
+};
+struct SigTextPlace {                       // where everything goes, as the host laid it out
+  const uint8_t* skeleton = nullptr;        // the pieces one after another
+  uint64_t skeleton_len = 0;
+  const uint64_t *piece_src = nullptr, *piece_dst = nullptr;   // pieces + 1 starts in the skeleton; pieces places in the text
+  uint64_t pieces = 0;
+  const uint64_t *mins_at = nullptr, *abunds_at = nullptr;     // n each: where the inside of a node's array begins
+  const uint8_t* digests = nullptr;         // 16 n bytes, launch_sigtext_md5's
+  const uint64_t* md5_at = nullptr;         // n: where a node's 32 hex digits stand
+  uint8_t* text = nullptr;
+  uint64_t text_len = 0;
+};
+void sigtext_geometry(uint32_t* values_per_tile, uint32_t* threads, uint32_t* md5_values_per_step);
+// passes 1 and 2 (profile names sigtext_measure, sigtext_scan): tile_*, node_* are written
+void launch_sigtext_measure(const SigTextPass& p, Device& dev, hipStream_t s);
+// pass 3 (sigtext_emit): the skeleton pieces, both arrays of every node and, over the placeholders, the digests as lower-case hex
+void launch_sigtext_emit(const SigTextPass& p, const SigTextPlace& w, Device& dev, hipStream_t s);
+// pass 4 (sigtext_md5): digests[16 v ..) = the md5 of str(ksizes[v]) and node v's decimal hashes; hashes stands at element off[0]
+void launch_sigtext_md5(const uint64_t* hashes, const uint64_t* off, uint32_t n, const uint32_t* ksizes, uint8_t* digests, Device& dev,
+                        hipStream_t s);
+
 // --- sort.hip -----------------------------------------------------------------------
 // LSD radix sort, ping-pong between (k0,v0) and (k1,v1); returns which pair holds the result.
 // Only the byte passes [first_pass, last_pass) are run (default: all eight): a stable sort by a bit

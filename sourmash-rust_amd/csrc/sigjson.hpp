@@ -10,6 +10,7 @@
 #pragma once
 #include <cctype>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -49,6 +50,27 @@ struct JVal {
 };
 
 [[noreturn]] inline void serde_error(const std::string& m) { throw JsonError{m, false, 0}; }
+
+// a string as serde_json writes it: quoted, with the short escapes and \u00xx for the other control bytes; everything from
+// 0x20 on, UTF-8 included, as it is.  The one writer of strings: signature.cpp and the device route (sigtext.cpp) both use it.
+inline void json_escape(std::string& out, const std::string& s) {
+  out.push_back('"');
+  for (unsigned char c : s) {
+    switch (c) {
+      case '"': out += "\\\""; break;
+      case '\\': out += "\\\\"; break;
+      case '\b': out += "\\b"; break;
+      case '\f': out += "\\f"; break;
+      case '\n': out += "\\n"; break;
+      case '\r': out += "\\r"; break;
+      case '\t': out += "\\t"; break;
+      default:
+        if (c < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", c); out += b; }
+        else out.push_back((char)c);
+    }
+  }
+  out.push_back('"');
+}
 
 // The spans of one document, for a parse with holes.  rows[first .. first + n) are the document's own; doc_begin / doc_end are
 // its bounds in the text the spans were cut from.

@@ -5,6 +5,7 @@
 // writer reproduces serde_json's compact output (field order of the Serialize impls, no spaces).
 #include "signature.hpp"
 #include "sigjson.hpp"
+#include "sigtext_core.hpp"
 
 #include <cctype>
 #include <cmath>
@@ -18,82 +19,11 @@
 namespace smh {
 
 // ------------------------------------------------------------------------------------
-// MD5 (RFC 1321) -- only for the md5sum field of serialised sketches (src/lib.rs:72-77,86)
-namespace {
-
-struct Md5 {
-  uint32_t a = 0x67452301, b = 0xefcdab89, c = 0x98badcfe, d = 0x10325476;
-  uint64_t total = 0;
-  uint8_t buf[64];
-  size_t fill = 0;
-
-  static uint32_t rol(uint32_t x, int s) { return (x << s) | (x >> (32 - s)); }
-
-  void block(const uint8_t* p) {
-    static const uint32_t K[64] = {
-        0xd76aa478, 0xe8c7b756, 0x242070db, 0xc1bdceee, 0xf57c0faf, 0x4787c62a, 0xa8304613, 0xfd469501,
-        0x698098d8, 0x8b44f7af, 0xffff5bb1, 0x895cd7be, 0x6b901122, 0xfd987193, 0xa679438e, 0x49b40821,
-        0xf61e2562, 0xc040b340, 0x265e5a51, 0xe9b6c7aa, 0xd62f105d, 0x02441453, 0xd8a1e681, 0xe7d3fbc8,
-        0x21e1cde6, 0xc33707d6, 0xf4d50d87, 0x455a14ed, 0xa9e3e905, 0xfcefa3f8, 0x676f02d9, 0x8d2a4c8a,
-        0xfffa3942, 0x8771f681, 0x6d9d6122, 0xfde5380c, 0xa4beea44, 0x4bdecfa9, 0xf6bb4b60, 0xbebfbc70,
-        0x289b7ec6, 0xeaa127fa, 0xd4ef3085, 0x04881d05, 0xd9d4d039, 0xe6db99e5, 0x1fa27cf8, 0xc4ac5665,
-        0xf4292244, 0x432aff97, 0xab9423a7, 0xfc93a039, 0x655b59c3, 0x8f0ccc92, 0xffeff47d, 0x85845dd1,
-        0x6fa87e4f, 0xfe2ce6e0, 0xa3014314, 0x4e0811a1, 0xf7537e82, 0xbd3af235, 0x2ad7d2bb, 0xeb86d391};
-    static const int S[64] = {7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22,
-                              5, 9,  14, 20, 5, 9,  14, 20, 5, 9,  14, 20, 5, 9,  14, 20,
-                              4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23,
-                              6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21};
-    uint32_t M[16];
-    for (int i = 0; i < 16; i++)
-      M[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) |
-             ((uint32_t)p[4 * i + 3] << 24);
-    uint32_t A = a, B = b, C = c, D = d;
-    for (int i = 0; i < 64; i++) {
-      uint32_t F;
-      int g;
-      if (i < 16) { F = (B & C) | (~B & D); g = i; }
-      else if (i < 32) { F = (D & B) | (~D & C); g = (5 * i + 1) & 15; }
-      else if (i < 48) { F = B ^ C ^ D; g = (3 * i + 5) & 15; }
-      else { F = C ^ (B | ~D); g = (7 * i) & 15; }
-      F = F + A + K[i] + M[g];
-      A = D; D = C; C = B;
-      B = B + rol(F, S[i]);
-    }
-    a += A; b += B; c += C; d += D;
-  }
-
-  void update(const void* data, size_t n) {
-    const uint8_t* p = (const uint8_t*)data;
-    total += n;
-    while (n) {
-      size_t take = std::min(n, (size_t)64 - fill);
-      memcpy(buf + fill, p, take);
-      fill += take; p += take; n -= take;
-      if (fill == 64) { block(buf); fill = 0; }
-    }
-  }
-
-  std::string hex() {
-    uint64_t bits = total * 8;
-    uint8_t pad = 0x80;
-    update(&pad, 1);
-    uint8_t z = 0;
-    while (fill != 56) update(&z, 1);
-    uint8_t len[8];
-    for (int i = 0; i < 8; i++) len[i] = (uint8_t)(bits >> (8 * i));
-    update(len, 8);
-    uint32_t w[4] = {a, b, c, d};
-    char out[33];
-    for (int i = 0; i < 16; i++) snprintf(out + 2 * i, 3, "%02x", (w[i / 4] >> (8 * (i % 4))) & 0xff);
-    return std::string(out, 32);
-  }
-};
-
-}  // namespace
-
+// the md5sum field of serialised sketches (src/lib.rs:72-77,86): MD5 itself is sigtext_core.hpp's, shared with the device
+// writer
 std::string sketch_md5(const KmerMinHash& mh) {
   mh.materialize();
-  Md5 m;
+  sigtext::Md5 m;
   std::string k = std::to_string(mh.ksize);
   m.update(k.data(), k.size());
   char tmp[24];
@@ -132,25 +62,6 @@ KmerMinHash sketch_from_fields(const SketchFields& f) {
   mh.is_protein = mh.molecule != kMoleculeDNA;
   mh.num = f.num;
   return mh;
-}
-
-void json_escape(std::string& out, const std::string& s) {
-  out.push_back('"');
-  for (unsigned char c : s) {
-    switch (c) {
-      case '"': out += "\\\""; break;
-      case '\\': out += "\\\\"; break;
-      case '\b': out += "\\b"; break;
-      case '\f': out += "\\f"; break;
-      case '\n': out += "\\n"; break;
-      case '\r': out += "\\r"; break;
-      case '\t': out += "\\t"; break;
-      default:
-        if (c < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", c); out += b; }
-        else out.push_back((char)c);
-    }
-  }
-  out.push_back('"');
 }
 
 // shortest decimal that round-trips, in serde_json's (ryu) style for the values a version takes

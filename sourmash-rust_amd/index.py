@@ -741,6 +741,58 @@ class ResidentIndex:
             out.append(mh)
         return out
 
+    # --- signature JSON written on the device (additive ABI smh_index_sigtext, smh_sigtext_*, smh_index_md5; the rules:
+    # include/sourmash_amd.h, "Signature JSON written on the device")
+    def sigtext(self, names=None, filenames=None, doc_starts=None):
+        """The index as `.sig` text in HBM: a signature.SigText.  names / filenames: one str or None per node
+        (None: a JSON null); they default to those of `self.signatures` where from_signatures left them, else to null.
+        doc_starts: n_docs + 1 ascending node numbers from 0 to len(self), document d = the nodes [doc_starts[d],
+        doc_starts[d + 1]); None: one document."""
+        from .signature import SigText
+        n = len(self)
+        entries = getattr(self, "signatures", None)
+        if names is None and entries is not None:
+            names = [e.name for e in entries]
+        if filenames is None and entries is not None:
+            filenames = [e.filename for e in entries]
+
+        def strings(v, what):
+            if v is None:
+                return None
+            v = list(v)
+            if len(v) != n:
+                raise ValueError("%s: one per node" % what)
+            return (C.c_char_p * max(n, 1))(*[None if s is None else s.encode("utf-8") for s in v])
+        ds, n_docs = None, 0
+        if doc_starts is not None:
+            wide = np.asarray(doc_starts, dtype=np.int64).reshape(-1)
+            if wide.size < 1 or wide.min() < 0 or wide.max() > 0xFFFFFFFF:
+                raise ValueError("doc_starts: one more entry than documents, ints in [0, 2^32)")
+            ds = np.ascontiguousarray(wide, dtype=np.uint32)
+            n_docs = ds.size - 1
+        return SigText(call(self._L.smh_index_sigtext, self._h, strings(names, "names"), strings(filenames, "filenames"),
+                            ds.ctypes.data_as(u32p) if ds is not None else None, n_docs))
+
+    def save_signatures(self, path=None, names=None, filenames=None, doc_starts=None, device=False):
+        """The byte string signature.save_signatures gives for sketches() -- each in a default Signature with its name and
+        filename, the documents of doc_starts one after another -- formatted on the device (sigtext()).  Returns bytes; with
+        device=True (a CUDA uint8 tensor of its own, doc_offsets).  path: the text is also written to that file."""
+        t = self.sigtext(names, filenames, doc_starts)
+        if device and path is None:
+            return t.tensor(), t.doc_offsets
+        data = t.read()
+        if path is not None:
+            with open(path, "wb") as fh:
+                fh.write(data)
+        return (t.tensor(), t.doc_offsets) if device else data
+
+    def md5sums(self):
+        """every node's md5sum as sourmash names it, 32 hex digits: of str(ksize) and the decimal hashes (smh_index_md5)"""
+        n = len(self)
+        out = np.zeros(max(n, 1) * 16, dtype=np.uint8)
+        call(self._L.smh_index_md5, self._h, out.ctypes.data_as(C.c_void_p))
+        return [out[16 * v:16 * v + 16].tobytes().hex() for v in range(n)]
+
     # --- building from records, concatenation (additive ABI smh_index_from_*, smh_index_concat; the rules: include/sourmash_amd.h,
     # "Building an index from records")
     @classmethod

@@ -179,6 +179,52 @@ class SignatureScan:
         return view.clone().view(torch.int64)
 
 
+class SigText:
+    """Signature JSON written on the device (additive ABI smh_index_sigtext, smh_sigtext_*): the text of a
+    resident index in HBM, owned by this handle.  ResidentIndex.save_signatures makes one."""
+
+    def __init__(self, ptr):
+        self._L = lib()
+        self._p = ptr
+
+    def __del__(self):
+        try:
+            self._L.smh_sigtext_free(self._p)
+        except Exception:
+            pass
+
+    def __len__(self): return self._L.smh_sigtext_len(self._p)
+
+    @property
+    def doc_offsets(self):
+        """documents + 1 byte offsets from 0, as SignatureScan.parse takes them"""
+        out = np.zeros(self._L.smh_sigtext_documents(self._p) + 1, dtype=np.uint64)
+        call(self._L.smh_sigtext_doc_offsets, self._p, out.ctypes.data_as(u64p))
+        return out
+
+    def read(self, offset=0, length=None):
+        """text[offset:offset + length] as bytes (smh_sigtext_read)"""
+        length = len(self) - offset if length is None else length
+        buf = C.create_string_buffer(max(length, 1))
+        call(self._L.smh_sigtext_read, self._p, offset, length, buf)
+        return buf.raw[:length]
+
+    def tensor(self):
+        """the text as a CUDA uint8 tensor of its own (a device-to-device copy)"""
+        import torch
+        from .fastx import _DeviceSpan
+        n = len(self)
+        if n == 0:
+            return torch.empty(0, dtype=torch.uint8, device="cuda")
+        return torch.as_tensor(_DeviceSpan(self._L.smh_sigtext_dev(self._p), n), device="cuda").clone()
+
+    def view(self):
+        """the text in place as a CUDA uint8 tensor; valid only while this handle lives"""
+        import torch
+        from .fastx import _DeviceSpan
+        return torch.as_tensor(_DeviceSpan(self._L.smh_sigtext_dev(self._p), max(len(self), 1)), device="cuda")[:len(self)]
+
+
 def read_signature_text(paths):
     """The text of one .sig file or of several, one after another, as (data, doc_offsets): a CUDA uint8 tensor when a file is
     blocked gzip (it is inflated on the device, fastx.inflate), else host bytes.  Plain files and single-stream gzip are read
