@@ -1219,8 +1219,8 @@ int smh_profile_get(const char *name, double *total_ms, uint64_t *launches);
  *              "dna", "protein", "dayhoff" or "hp" in any case; any other string keeps none), ascending: returns how many and,
  *              when ids_out is not NULL, writes them (room for smh_signatures_len entries always suffices).  Needs no device.
  *   smh_signatures_index_filtered   smh_signatures_index of exactly those entries.
- * Out of scope: zip containers, single-stream gzip on the device (BGZF goes through smh_gzip_inflate_dev in front of
- * *_parse_dev), md5 verification, sorting unsorted `mins`.  (Writing signatures: the next section.)
+ * Out of scope: single-stream gzip on the device outside a zip collection (BGZF goes through smh_gzip_inflate_dev in front of
+ * *_parse_dev, a zip collection through smh_archive_inflate_dev: "Zip collections"), md5 verification, sorting unsorted `mins`.  (Writing signatures: the next section.)
  * smh_sigscan_geometry: bytes per workgroup tile (cut on 16-byte boundaries of the address) and threads per workgroup (tests,
  * tools).  Timers: "sigscan_summary", "sigscan_scan", "sigscan_compact", "sigscan_gather" (the checks of a gathered index; its
  * copy is timed as "downsample_copy"); event counters: "signatures_parsed", "index_from_signatures". */
@@ -1274,7 +1274,7 @@ void smh_sigscan_geometry(uint32_t *tile_bytes, uint32_t *threads);
  * smh_sigtext_doc_offsets writes documents + 1 offsets from 0 (what smh_signatures_parse_dev takes); smh_sigtext_dev is the text
  * in HBM, owned by the handle and valid while it lives; smh_sigtext_read copies text[offset, offset + len) to the host (a range
  * outside the text: code 3).  smh_index_md5 writes the 16 n digest bytes alone and builds no text.
- * Out of scope: compression of the output, zip containers, several sketches in one signature, `email`, `license` or `version`
+ * Out of scope: compression of the output, writing zip containers, several sketches in one signature, `email`, `license` or `version`
  * other than the defaults.
  * smh_sigtext_geometry: values per workgroup tile of the measure and emit passes, threads per workgroup, values a wave formats
  * per step of the md5 pass (tests, tools).  Timers: "sigtext_measure", "sigtext_scan", "sigtext_emit", "sigtext_md5"; event
@@ -1290,6 +1290,82 @@ int smh_sigtext_read(const SmhSigText *t, uint64_t offset, uint64_t len, char *o
 void smh_sigtext_free(SmhSigText *t);
 int smh_index_md5(SmhIndex *index, uint8_t *out);                  /* 16 n bytes */
 void smh_sigtext_geometry(uint32_t *values_per_tile, uint32_t *threads, uint32_t *md5_values_per_step);
+
+/* Zip collections: the container sourmash writes its databases in -- members signatures/<md5>.sig.gz, stored
+ * in the zip because they are gzip already, and a SOURMASH-MANIFEST.csv -- read into HBM with the compressed bytes uploaded
+ * once and every chosen member inflated on the device, each into its own slice of one text that smh_signatures_parse_dev
+ * takes.  tests/archive_restatement.py states the scan and the CRC fold as plain Python and is normative.
+ *   smh_archive_scan   reads data[0, len) on the host; no device is touched.  The end-of-central-directory record is looked
+ *              for in the last 22 + 65535 bytes: a place counts when the signature PK\5\6 stands there AND its comment length
+ *              leads exactly to the end of the data; the LOWEST such place is the record (a record spelled inside the comment
+ *              stands behind the true one).  A zip64 locator directly in front of it leads to the zip64 end record, whose
+ *              counts, size and offset then hold.  Every central-directory entry is read, with the zip64 extra field (id 1:
+ *              size, compressed size, header offset, disk; each present only when its fixed field is all ones) for sizes and
+ *              offsets; then the entry's local header, whose OWN name and extra lengths give the data offset (they may differ
+ *              from the central directory's).  Sizes and the CRC-32 come from the central directory, so data descriptors
+ *              (flag bit 3) are fine.  Offsets are taken as written: an archive with prepended data is out of scope.
+ *              kind is decided from content, not from the name: a name ending '/' with size 0 is SMH_ARCHIVE_DIRECTORY;
+ *              else method 8 is DEFLATE; method 0 whose data begins 1f 8b 08 is GZIP, other method 0 is STORED; any other
+ *              method is OTHER.  A GZIP entry is treated as ONE gzip member: its RFC 1952 header is read as smh_gzip_scan
+ *              reads one, without the BC requirement; the payload is everything up to the last 8 bytes, and CRC-32 and ISIZE
+ *              come from that trailer.  (A multi-member .gz is not detected here: the decoder reports it as
+ *              SMH_INFLATE_LEFTOVER, or as an output above or below ISIZE.)
+ *              device_ok is 0, with a reason string, and the entry is still listed, for: an encrypted entry (flag bit 0); a
+ *              method other than 0 or 8; a compressed or inflated size of 2^32 or more; a method-0 entry whose two sizes
+ *              differ; a GZIP entry shorter than its header plus trailer.
+ *              The whole archive is refused, code 3, with a message "archive: ... (entry I at byte B)" -- "(at byte B)" where
+ *              no entry is meant -- for: no end record; a multi-disk archive (any disk number other than 0, or a count on
+ *              this disk that is not the total); a zip64 end record outside the data or without its signature; a central
+ *              directory outside the data in front of the end record; a truncated central directory (an entry that does not
+ *              fit into the directory's announced size); a directory entry or a local header without its signature; a zip64
+ *              extra field missing or cut short; a local header or entry data outside data[0, len).
+ *   smh_archive_entry   fills an SmhArchiveEntry; its strings are NUL-terminated, owned by the handle and valid while it
+ *              lives.  payload_off / payload_len: what a device inflate reads (the DEFLATE stream of a DEFLATE or GZIP entry,
+ *              the bytes of a STORED one); text_size / text_crc: the size and CRC-32 of what it writes (GZIP: the trailer's
+ *              ISIZE and CRC-32; else the central directory's).  Only meaningful with device_ok.
+ *   smh_archive_inflate_dev   data_dev: the len scanned bytes in HBM at any alignment.  ids: n_ids entries, any order,
+ *              repeats allowed; entry ids[i] becomes out[out_offs[i], out_offs[i] + text_size): the caller lays out the text.
+ *              Refused before anything is launched, code 3: len other than the scanned length; an id past the entries or
+ *              whose device_ok is 0; a slice that leaves out_cap; two non-empty slices that overlap.  It follows the stream
+ *              contract at the top of this file and returns complete.  Members are inflated one wave each, handed out
+ *              longest payload first from a ticket (members differ by orders of magnitude; a wave decodes a few MB/s); STORED
+ *              members are copied.  verify: the CRC-32 of every text is taken in chunks of smh_archive_geometry's size spread
+ *              over the device, folded per member and compared -- with the gzip trailer's for GZIP (the zip's CRC over a
+ *              stored .gz's compressed bytes is not checked: the trailer covers the content), with the central directory's
+ *              for DEFLATE and STORED.  verify = 0 skips it; stored members are still copied and sizes are always checked.
+ *              status_out (host, one byte per id, or NULL) receives the SMH_INFLATE_* status of every position, also when
+ *              the call fails.  A failing call returns code 3 with "archive: <reason> (entry I 'name')" for the LOWEST bad
+ *              position of ids.  On ANY input no byte outside data[0, len) is read and none outside the given slices is
+ *              written.  Offsets into the text are 64-bit everywhere.
+ *   smh_archive_inflate   the same from host bytes, with one upload of the compressed file; on the library's own stream.
+ * smh_archive_geometry: bytes per CRC chunk and threads per workgroup (tests, tools).  smh_archive_set_sorted(0) is a
+ * measurement knob like smh_set_grid_cap: members are handed out in id order instead of longest first (default 1;
+ * smh_archive_sorted reads it back).  It is one word of the process, read without a lock by every call: not thread-safe, not
+ * for production use -- the result is the same either way, only the time differs.  Timers: "archive_inflate",
+ * "archive_chunks", "archive_crc".
+ * Out of scope: writing zips, SBT zips, FASTA / FASTQ inside zips, bzip2 / lzma / zstd methods, archives with prepended data. */
+typedef struct SmhArchive SmhArchive;
+enum { SMH_ARCHIVE_STORED = 0, SMH_ARCHIVE_DEFLATE = 1, SMH_ARCHIVE_GZIP = 2, SMH_ARCHIVE_DIRECTORY = 3, SMH_ARCHIVE_OTHER = 4 };
+typedef struct SmhArchiveEntry {
+  const char *name, *reason;              /* reason: why device_ok is 0, else "" */
+  uint32_t method, flags, crc32, kind;    /* as the central directory has them; kind: SMH_ARCHIVE_* */
+  uint32_t device_ok, text_size, text_crc, pad;
+  uint64_t comp_size, size;               /* central directory, or its zip64 extra field */
+  uint64_t header_off, data_off;          /* the local header; the entry's bytes are data[data_off, data_off + comp_size) */
+  uint64_t payload_off, payload_len;
+} SmhArchiveEntry;
+SmhArchive *smh_archive_scan(const void *data, uint64_t len);
+void smh_archive_free(SmhArchive *a);
+uint64_t smh_archive_entries(const SmhArchive *a);
+int smh_archive_entry(const SmhArchive *a, uint64_t i, SmhArchiveEntry *out);
+int smh_archive_inflate_dev(const SmhArchive *a, const void *data_dev, uint64_t len, const uint32_t *ids, const uint64_t *out_offs,
+                            uint64_t n_ids, void *out_dev, uint64_t out_cap, int verify, uint8_t *status_out /* host, or NULL */,
+                            void *stream);
+int smh_archive_inflate(const SmhArchive *a, const void *data, uint64_t len, const uint32_t *ids, const uint64_t *out_offs, uint64_t n_ids,
+                        void *out_dev, uint64_t out_cap, int verify, uint8_t *status_out);
+void smh_archive_geometry(uint32_t *chunk_bytes, uint32_t *threads);
+void smh_archive_set_sorted(int sorted);
+int smh_archive_sorted(void);
 
 #ifdef __cplusplus
 }

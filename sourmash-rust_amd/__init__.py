@@ -7,7 +7,8 @@ csrc/ (libsourmash_amd.so).  There is no CPU fallback.
 from ._lib import SO_PATH, build, exported_symbols, lib  # noqa: F401
 from .errors import SourmashError  # noqa: F401
 from .minhash import KmerMinHash, hash_murmur, hash_words  # noqa: F401
-from . import fastx, index, matrix, sbt  # noqa: F401
+from . import archive, fastx, index, matrix, sbt  # noqa: F401
+from .archive import ZipCollection  # noqa: F401
 from .fastx import Records  # noqa: F401
 from .sbt import SBT, Nodegraph  # noqa: F401
 

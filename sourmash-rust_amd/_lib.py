@@ -58,6 +58,13 @@ class SmhSigEntry(C.Structure):
                 ("n_mins", C.c_uint64), ("n_abundances", C.c_uint64), ("mins_span", C.c_uint64), ("abundances_span", C.c_uint64)]
 
 
+class SmhArchiveEntry(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("reason", C.c_char_p), ("method", C.c_uint32), ("flags", C.c_uint32), ("crc32", C.c_uint32),
+                ("kind", C.c_uint32), ("device_ok", C.c_uint32), ("text_size", C.c_uint32), ("text_crc", C.c_uint32), ("pad", C.c_uint32),
+                ("comp_size", C.c_uint64), ("size", C.c_uint64), ("header_off", C.c_uint64), ("data_off", C.c_uint64),
+                ("payload_off", C.c_uint64), ("payload_len", C.c_uint64)]
+
+
 class SmhFilter(C.Structure):
     _fields_ = [("operand_mode", C.c_uint32), ("abund_out", C.c_uint32), ("min_abund", C.c_uint32), ("max_abund", C.c_uint32),
                 ("min_owners", C.c_uint32), ("max_owners", C.c_uint32)]
@@ -147,6 +154,17 @@ _SIGS = {
     "smh_gzip_member": (C.c_int, [C.c_void_p, C.c_uint64, u64p, u32p, u32p, u32p]),
     "smh_gzip_inflate_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint8), C.c_void_p]),
     "smh_gzip_inflate": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint8)]),
+    "smh_archive_scan": (C.c_void_p, [C.c_char_p, C.c_uint64]),
+    "smh_archive_free": (None, [C.c_void_p]),
+    "smh_archive_entries": (C.c_uint64, [C.c_void_p]),
+    "smh_archive_entry": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(SmhArchiveEntry)]),
+    "smh_archive_inflate_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u32p, u64p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                                          C.POINTER(C.c_uint8), C.c_void_p]),
+    "smh_archive_inflate": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, u32p, u64p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                                      C.POINTER(C.c_uint8)]),
+    "smh_archive_geometry": (None, [u32p, u32p]),
+    "smh_archive_set_sorted": (None, [C.c_int]),
+    "smh_archive_sorted": (C.c_int, []),
     "smh_kmerminhash_new_molecule": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_bool]),
     "smh_kmerminhash_molecule": (C.c_int, [C.c_void_p]),
     "smh_add_protein": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64]),

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/sourmash_amd.h"
+#include "archive_core.hpp"
 #include "index.hpp"
 #include "sbt.hpp"
 #include "signature.hpp"
@@ -596,6 +597,63 @@ int smh_gzip_inflate(const void* data, uint64_t len, void* out_dev, uint64_t out
     smh::gzip_inflate_host(static_cast<const uint8_t*>(data), len, static_cast<uint8_t*>(out_dev), out_cap, verify_crc != 0, status_out, dev);
   });
 }
+
+// ------------------------------------------------------------------ zip collections (archive.cpp)
+
+struct SmhArchive : smh::archive::Archive {};
+static_assert(SMH_ARCHIVE_STORED == smh::archive::kStored && SMH_ARCHIVE_DEFLATE == smh::archive::kDeflate &&
+              SMH_ARCHIVE_GZIP == smh::archive::kGzip && SMH_ARCHIVE_DIRECTORY == smh::archive::kDirectory &&
+              SMH_ARCHIVE_OTHER == smh::archive::kOther, "the kinds of the header are archive_core.hpp's");
+
+SmhArchive* smh_archive_scan(const void* data, uint64_t len) {
+  return pad<SmhArchive*>([&] {
+    if (len) require(data, "data");
+    auto a = std::make_unique<SmhArchive>();
+    smh::archive_scan(a.get(), static_cast<const uint8_t*>(data), len);
+    return a.release();
+  });
+}
+void smh_archive_free(SmhArchive* a) { delete a; }
+uint64_t smh_archive_entries(const SmhArchive* a) { return a ? a->entries.size() : 0; }
+int smh_archive_entry(const SmhArchive* a, uint64_t i, SmhArchiveEntry* out) {
+  return pad_code([&] {
+    require(a, "a"); require(out, "out");
+    if (i >= a->entries.size()) throw Error(smh::kMsg, "archive: entry " + std::to_string(i) + " of " + std::to_string(a->entries.size()));
+    const smh::archive::Entry& e = a->entries[i];
+    memset(out, 0, sizeof *out);
+    out->name = e.name.c_str(); out->reason = e.reason.c_str();
+    out->method = e.method; out->flags = e.flags; out->crc32 = e.crc32; out->kind = e.kind;
+    out->device_ok = e.device_ok ? 1 : 0; out->text_size = e.text_size; out->text_crc = e.text_crc;
+    out->comp_size = e.comp_size; out->size = e.size; out->header_off = e.header_off; out->data_off = e.data_off;
+    out->payload_off = e.payload_off; out->payload_len = e.payload_len;
+  });
+}
+int smh_archive_inflate_dev(const SmhArchive* a, const void* data_dev, uint64_t len, const uint32_t* ids, const uint64_t* out_offs, uint64_t n_ids,
+                            void* out_dev, uint64_t out_cap, int verify, uint8_t* status_out, void* stream) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    require(a, "a");
+    std::lock_guard<std::recursive_mutex> lock(dev.mutex());
+    smh::archive_inflate_dev(*a, static_cast<const uint8_t*>(data_dev), len, ids, out_offs, n_ids, static_cast<uint8_t*>(out_dev), out_cap,
+                             verify != 0, status_out, dev.user_stream(stream), dev);
+  });
+}
+int smh_archive_inflate(const SmhArchive* a, const void* data, uint64_t len, const uint32_t* ids, const uint64_t* out_offs, uint64_t n_ids,
+                        void* out_dev, uint64_t out_cap, int verify, uint8_t* status_out) {
+  return pad_code([&] {
+    auto& dev = smh::Device::get();
+    require(a, "a");
+    if (len) require(data, "data");
+    smh::archive_inflate_host(*a, static_cast<const uint8_t*>(data), len, ids, out_offs, n_ids, static_cast<uint8_t*>(out_dev), out_cap,
+                              verify != 0, status_out, dev);
+  });
+}
+void smh_archive_geometry(uint32_t* chunk_bytes, uint32_t* threads) {
+  if (chunk_bytes) *chunk_bytes = smh::archive::kChunk;
+  if (threads) *threads = smh::kInflateThreads;
+}
+void smh_archive_set_sorted(int sorted) { smh::g_archive_sorted = sorted != 0; }
+int smh_archive_sorted(void) { return smh::g_archive_sorted ? 1 : 0; }
 
 int smh_add_records(KmerMinHash* ptr, const SmhRecords* r, bool force) {
   return pad_code([&] {

@@ -37,6 +37,8 @@ uint32_t le32(const uint8_t* p) { return le16(p) | le16(p + 2) << 16; }
 
 }  // namespace
 
+const char* inflate_reason_text(uint32_t reason) { return reason_text(reason); }
+
 void gzip_scan(Gzip* g, const uint8_t* data, uint64_t len) {
   g->members.clear(); g->header_off.clear();
   g->len = len; g->inflated = 0;

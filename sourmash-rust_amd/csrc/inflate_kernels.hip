@@ -1,7 +1,8 @@
 // inflate_kernels.hip -- blocked gzip inflated on the device: one wave per member, members walked in a
 // gridDim-stride loop.  The decoder is inflate_core.hpp, run lane-uniform: all 64 lanes read the same payload bytes, hold the
 // same bit buffer and counters and write the same values to the wave's tables in LDS (identical stores to one address; every
-// lane reads back what it has itself written, so the tables need no cross-lane ordering).  The lanes differ only in the sink:
+// lane reads back what it has itself written, so the tables need no cross-lane ordering).  The lanes differ only in the sink
+// (wave_sink.hpp, shared with archive_kernels.hip):
 // literal runs are kept one byte per lane and stored together, a match copy or a stored block is spread over the lanes.
 //
 // Cross-lane read-after-write: a copy reads bytes of the member's output slice -- the window is the slice itself, in global
@@ -10,51 +11,13 @@
 // byte the same copy writes: a distance below the length is expanded as the periodic pattern it is.
 #include "inflate_core.hpp"
 #include "kernels.hpp"
+#include "wave_sink.hpp"
 
 namespace smh {
 
 namespace {
 
 constexpr uint32_t kWavesPerBlock = kInflateThreads / 64;
-
-struct WaveSink {
-  uint8_t* out;        // the member's slice
-  uint32_t lane;
-  uint32_t nlit = 0;   // literals not stored yet: out[lit_pos + i] is lane i's `mine`
-  uint32_t lit_pos = 0;
-  uint8_t mine = 0;
-  __device__ WaveSink(uint8_t* o, uint32_t l) : out(o), lane(l) {}
-  __device__ void flush() {
-    if (nlit) {
-      if (lane < nlit) out[lit_pos + lane] = mine;
-      nlit = 0;
-    }
-  }
-  __device__ void lit(uint32_t pos, uint8_t b) {
-    if (nlit == 0) lit_pos = pos;
-    if (lane == nlit) mine = b;
-    if (++nlit == 64) flush();
-  }
-  // orders the loads that follow behind the stores every lane of the wave has issued
-  __device__ static void publish() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-  __device__ void copy(uint32_t pos, uint32_t dist, uint32_t len) {
-    flush();
-    publish();
-    const uint8_t* src = out + (pos - dist);
-    if (dist >= len) {
-      for (uint32_t i = lane; i < len; i += 64) out[pos + i] = src[i];
-    } else {
-      for (uint32_t i = lane; i < len; i += 64) out[pos + i] = src[i % dist];
-    }
-  }
-  __device__ void stored(uint32_t pos, const uint8_t* src, uint32_t n) {
-    flush();
-    for (uint32_t i = lane; i < n; i += 64) out[pos + i] = src[i];
-  }
-};
 
 // The decode is a chain of dependent round trips, so waves in flight are what it runs on: four per SIMD (128 VGPRs, two
 // spilled) measured 19 % faster than the three the compiler takes by itself at 144.

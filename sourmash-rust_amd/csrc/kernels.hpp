@@ -1,7 +1,7 @@
 // kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
 // gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip, collapse_kernels.hip,
-// index_build_kernels.hip, filter_kernels.hip, nearest_kernels.hip, inflate_kernels.hip).
+// index_build_kernels.hip, filter_kernels.hip, nearest_kernels.hip, inflate_kernels.hip, archive_kernels.hip).
 // Plain structs and pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -178,6 +178,36 @@ void gzip_inflate_dev(const Gzip& g, const uint8_t* data_dev, uint64_t len, uint
                       uint8_t* status_out, hipStream_t s, Device& dev);
 void gzip_inflate_host(const uint8_t* data, uint64_t len, uint8_t* out_dev, uint64_t out_cap, bool verify_crc, uint8_t* status_out,
                        Device& dev);
+
+const char* inflate_reason_text(uint32_t reason);   // the words of an inflate::Reason (error messages)
+
+// --- archive_kernels.hip, archive.cpp --------------------------------------------------
+// Zip collections inflated on the device (the rules are in include/sourmash_amd.h, "Zip collections").
+struct ArchiveMember {                       // one id of a call: what is read, where its text goes
+  uint64_t src_off;                          // the DEFLATE stream, or a stored entry's bytes: data[src_off, src_off + src_len)
+  uint64_t out_off;                          // its text: out[out_off, out_off + size)
+  uint32_t src_len, size, crc, inflated;     // crc: the text's expected CRC-32; inflated: 1 DEFLATE, 0 stored (a copy)
+};
+// status[m] = the inflate::Reason of order[...] = m; *ticket is zero; *err as launch_inflate's.  Profile name archive_inflate.
+void launch_inflate_queue(const uint8_t* data, const ArchiveMember* members, const uint64_t* order, uint64_t n_order, unsigned long long* ticket,
+                          uint8_t* out, uint8_t* status, unsigned long long* err, Device& dev, hipStream_t s);
+// prefix: n_members + 1 chunk counts summed (archive_core.hpp); terms: one register per chunk.  Copies the stored members;
+// verify: also leaves every chunk's CRC register.  Profile name archive_chunks.
+void launch_archive_chunks(const uint8_t* data, const ArchiveMember* members, const uint64_t* prefix, uint64_t n_members, uint64_t n_chunks,
+                           uint8_t* out, uint32_t* terms, bool verify, Device& dev, hipStream_t s);
+// folds the registers of every member whose status is still ok and compares.  Profile name archive_crc.
+void launch_archive_crc(const ArchiveMember* members, const uint64_t* prefix, uint64_t n_members, const uint32_t* terms, uint8_t* status,
+                        unsigned long long* err, Device& dev, hipStream_t s);
+namespace archive { struct Archive; }
+void archive_scan(archive::Archive* a, const uint8_t* data, uint64_t len);   // host only; throws Error(kMsg)
+// ids: n_ids entries of the scan, any order, repeats allowed; entry ids[i] becomes out[out_offs[i], + its text size).
+// status_out: host, one byte per id, or null.  Returns with the work complete; throws Error(kMsg) naming the entry of the
+// lowest bad position (status_out is filled first).
+void archive_inflate_dev(const archive::Archive& a, const uint8_t* data_dev, uint64_t len, const uint32_t* ids, const uint64_t* out_offs,
+                         uint64_t n_ids, uint8_t* out_dev, uint64_t out_cap, bool verify, uint8_t* status_out, hipStream_t s, Device& dev);
+void archive_inflate_host(const archive::Archive& a, const uint8_t* data, uint64_t len, const uint32_t* ids, const uint64_t* out_offs,
+                          uint64_t n_ids, uint8_t* out_dev, uint64_t out_cap, bool verify, uint8_t* status_out, Device& dev);
+extern bool g_archive_sorted;   // a measurement knob (smh_archive_set_sorted; default true): false hands members out in id order
 
 // --- sigscan_kernels.hip ---------------------------------------------------------------
 // Signature JSON text in device memory -> the u64 values of its number arrays, one row per span, and the skeleton

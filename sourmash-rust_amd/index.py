@@ -852,12 +852,16 @@ class ResidentIndex:
         """An index of the sketches of signature JSON whose numbers were read on the device: the hashes go
         from the text's values to the index device to device.  source: a signature.SignatureScan; bytes of one document; a
         path or a list of paths (plain files and single-stream gzip are read on the host, concatenated and uploaded once; a
-        blocked-gzip file is inflated on the device).  ids: the scan's entries to take, any order, repeats allowed; None: the
+        blocked-gzip file is inflated on the device; a path or bytes that begin PK\\3\\4 are a zip collection and go to from_zip).
+        ids: the scan's entries to take, any order, repeats allowed; None: the
         entries load_signatures' filter keeps for ksize (0: any) and moltype (None: any).  The index answers every call as
         ResidentIndex(load_signatures_buffer(...)) does; one refusal of its own (code 3): hashes that are not strictly
         ascending.  `signatures` holds the chosen entries; `nodes` are the index's own sketches, read back when first asked."""
         from .signature import SignatureScan, read_signature_text
+        from .archive import is_zip
         L = lib()
+        if ids is None and not isinstance(source, (SignatureScan, list, tuple)) and is_zip(source):
+            return cls.from_zip(source, ksize=ksize, moltype=moltype, stream=stream)   # a zip collection (bytes or a path)
         if isinstance(source, SignatureScan):
             scan = source
         elif isinstance(source, (bytes, bytearray, memoryview)):
@@ -883,6 +887,31 @@ class ResidentIndex:
         idx._node_templates = [(e.num, e.ksize, e.molecule, e.seed, e.max_hash, track) for e in idx.signatures]
         idx.nodes = _OwnSketches(idx)
         return idx
+
+    @classmethod
+    def from_zip(cls, source, ksize=0, moltype=None, md5=None, device_member_limit=None, stream=None):
+        """An index of the sketches of a zip collection: the compressed file is uploaded once, the chosen
+        members are inflated on the device (archive.ZipCollection.text), read there (SignatureScan.parse) and gathered device
+        to device (from_signatures).  source: a path, the archive's bytes, or an archive.ZipCollection.  The members are
+        chosen by the manifest where there is one (ZipCollection.select); the sketches by the library's own filter for ksize
+        (0: any) and moltype (None: any), and by md5 (a string or a collection of them) against each sketch's `md5sum`.
+        device_member_limit: members whose text is larger are inflated on the host (None: the default).  `signatures` holds
+        the chosen entries, as from_signatures leaves them."""
+        from .archive import ZipCollection
+        from .signature import SignatureScan
+        L = lib()
+        zc = source if isinstance(source, ZipCollection) else ZipCollection(source)
+        members = zc.select(ksize=ksize, moltype=moltype, md5=md5)
+        text, offs = zc.text(members, device_member_limit=device_member_limit, stream=stream)
+        scan = SignatureScan.parse(text, offs, stream=stream)
+        v = np.zeros(max(len(scan), 1), dtype=np.uint32)
+        kept = call(L.smh_signatures_filter, scan._p, int(ksize), moltype.encode() if moltype else None, v.ctypes.data_as(u32p))
+        chosen = [int(i) for i in v[:kept]]
+        if md5 is not None:
+            md5s = {md5} if isinstance(md5, str) else set(md5)
+            entries = scan.entries
+            chosen = [i for i in chosen if entries[i].md5sum in md5s]
+        return cls.from_signatures(scan, ids=chosen, stream=stream)
 
     @classmethod
     def concat(cls, parts):
