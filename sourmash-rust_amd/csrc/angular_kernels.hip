@@ -23,16 +23,12 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "wave_ops.hpp"
 
 namespace smh {
 namespace {
 
 constexpr uint32_t kAngularSamples = 4096;   // 32 KiB of hashes + 16 KiB of abundances: three workgroups per CU
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void k_angular_narrow(const uint64_t* __restrict__ counts, const uint32_t* __restrict__ starts,
                                                         uint32_t total, uint32_t n, uint32_t* __restrict__ out,

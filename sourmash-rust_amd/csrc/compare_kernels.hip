@@ -97,7 +97,7 @@ __global__ __launch_bounds__(THREADS) void k_pair_block(const uint64_t* __restri
   const PairCounts c = walk<false>(A, la, B, lb, pa, pb, t1 - t0, 0, 0);
   // workgroup exclusive scan of uni: wave scan + wave totals through LDS
   const uint64_t wave_excl = wave_excl_scan64(c.uni, lane);
-  const uint64_t wave_u = wave_sum64(c.uni), wave_c = wave_sum64(c.com);
+  const uint64_t wave_u = wave_sum_u64(c.uni), wave_c = wave_sum_u64(c.com);
   if (lane == 0) { w_u[w] = wave_u; w_c[w] = wave_c; }
   __syncthreads();
   uint64_t before = 0, tot_u = 0, tot_c = 0;
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(THREADS) void k_pair_block(const uint64_t* __restri
     else if (u0 <= n) mine = walk<true>(A, la, B, lb, pa, pb, t1 - t0, u0, n).com;
     else mine = 0;
   }
-  const uint64_t wave_m = wave_sum64(mine);
+  const uint64_t wave_m = wave_sum_u64(mine);
   if (lane == 0) w_m[w] = wave_m;
   __syncthreads();
   if (tid == 0) {
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void k_pair_grid(const uint64_t* __restrict__ 
     if (A[mid] <= B[t0 - 1 - mid]) lo = mid + 1; else hi = mid;
   }
   const PairCounts c = walk<false>(A, la, B, lb, lo, (uint32_t)(t0 - lo), (uint32_t)(t1 - t0), 0, 0);
-  const uint64_t wu = wave_sum64(c.uni), wc = wave_sum64(c.com);
+  const uint64_t wu = wave_sum_u64(c.uni), wc = wave_sum_u64(c.com);
   if ((threadIdx.x & 63) == 0) {
     if (wu) atomicAdd(&out->tot_u, (unsigned long long)wu);
     if (wc) atomicAdd(&out->tot_c, (unsigned long long)wc);
@@ -2217,7 +2217,7 @@ __global__ __launch_bounds__(256) void k_plan_ranges(const uint64_t* __restrict_
     mine_pairs = hi - lo;
   }
   if (st) {
-    const uint64_t wsum = wave_sum64(mine_pairs);
+    const uint64_t wsum = wave_sum_u64(mine_pairs);
     if ((threadIdx.x & 63) == 0 && wsum) atomicAdd(&st->pairs, (unsigned long long)wsum);
   }
 }
@@ -2292,7 +2292,7 @@ __global__ __launch_bounds__(256) void k_tiles_count16(TileTest t, PlanState* st
   uint32_t mine = 0;
   for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < all; x += (uint64_t)gridDim.x * blockDim.x)
     mine += tile_shares((uint32_t)(x / tiles_c), (uint32_t)(x % tiles_c), 16, t) ? 1u : 0u;
-  const uint32_t wsum = (uint32_t)wave_sum64(mine);
+  const uint32_t wsum = (uint32_t)wave_sum_u64(mine);
   if ((threadIdx.x & 63) == 0 && wsum) atomicAdd(&st->count16, wsum);
 }
 // The height of the tiles, from the number of 16-row tiles that hold sharing pairs (tools/sweep_pf*.sh,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wave_ops.hpp"
+
 namespace smh {
 namespace {
 
@@ -33,10 +35,6 @@ __device__ __forceinline__ PairCounts walk(const uint64_t* A, uint32_t la, const
   return {uni, com};
 }
 
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 __device__ __forceinline__ uint64_t wave_excl_scan64(uint64_t v, int lane) {
   uint64_t incl = v;
   for (int off = 1; off < 64; off <<= 1) {
@@ -69,8 +67,8 @@ __device__ __forceinline__ PairResult64 wave_compare_pair(const uint64_t* A, uin
   const uint32_t pa = lo, pb = t0 - lo;
   PairCounts c = walk<false>(A, la, B, lb, pa, pb, t1 - t0, 0, 0);
   const uint64_t u0 = wave_excl_scan64(c.uni, lane);
-  const uint64_t tot_u = wave_sum64(c.uni);
-  const uint64_t tot_c = wave_sum64(c.com);
+  const uint64_t tot_u = wave_sum_u64(c.uni);
+  const uint64_t tot_c = wave_sum_u64(c.com);
   uint64_t mine = c.com;
   if (n != 0 && tot_u > n) {
     if (u0 + c.uni <= n) mine = c.com;
@@ -78,7 +76,7 @@ __device__ __forceinline__ PairResult64 wave_compare_pair(const uint64_t* A, uin
     else mine = 0;
   }
   PairResult64 r;
-  r.common = wave_sum64(mine);
+  r.common = wave_sum_u64(mine);
   r.size = (n != 0 && tot_u > n) ? n : tot_u;
   r.tot_c = tot_c;
   return r;

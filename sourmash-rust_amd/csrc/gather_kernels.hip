@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "wave_ops.hpp"
 
 namespace smh {
 namespace {
@@ -42,15 +43,6 @@ struct GatherState {
   uint32_t pad;
   unsigned long long total_hits;
 };
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-  for (int off = 32; off; off >>= 1) { const uint64_t o = __shfl_xor(v, off); v = o > v ? o : v; }
-  return v;
-}
 
 // m = ceil(lq / 2^shift) <= kGatherSamples samples; shift == 0: the whole query sits in LDS and no global level is left
 __global__ __launch_bounds__(256) void k_gather_hits(SketchSet idx, const uint64_t* __restrict__ Q, uint32_t lq, uint32_t shift,

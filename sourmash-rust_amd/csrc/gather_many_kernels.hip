@@ -28,21 +28,13 @@
 
 #include "directory_probe.hpp"
 #include "kernels.hpp"
+#include "wave_ops.hpp"
 
 namespace smh {
 namespace {
 
 constexpr uint32_t kUnassigned = 0xffffffffu;
 constexpr uint32_t kPickThreads = 512;
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-  for (int off = 32; off; off >>= 1) { const uint64_t o = __shfl_xor(v, off); v = o > v ? o : v; }
-  return v;
-}
 
 // shift, m: directory_sampling
 __global__ __launch_bounds__(256) void k_gm_probe(MatchDirectory d, uint32_t shift, uint32_t m, const uint64_t* __restrict__ hashes,

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip, sort.hip,
+// kernels.hpp -- launch interfaces of the HIP kernels (sketch_kernels.hip and sketch_{dna,protein,amino}_kernels.hip, sort.hip,
 // compare_kernels.hip, parse_kernels.hip, gather_kernels.hip, angular_kernels.hip, downsample_kernels.hip, match_kernels.hip,
 // gather_many_kernels.hip, lca_kernels.hip, search_many_kernels.hip, cluster_kernels.hip, collapse_kernels.hip,
 // index_build_kernels.hip, filter_kernels.hip, nearest_kernels.hip, inflate_kernels.hip, archive_kernels.hip).
@@ -55,6 +55,9 @@ struct HashParams {
   uint64_t range_lo = 0, range_hi = 0;  // k-mer start positions [lo, hi) handled by this launch
 };
 
+// --- sketch_dna_kernels.hip: launch_dna_hash, launch_first_invalid, launch_first_bad_record, launch_record_stats;
+// --- sketch_protein_kernels.hip: launch_translate, launch_protein_fused, launch_hash_windows;
+// --- sketch_amino_kernels.hip: launch_amino_hash, amino_geometry; the others: sketch_kernels.hip ---
 // DNA arm of add_sequence (reference src/lib.rs:258-274): canonical k-mer + murmur64 + filter.
 // Picks the rolling 2-bit kernel for ksize <= 32 and the byte-wise kernel otherwise.
 void launch_dna_hash(const SeqBatch& b, const HashParams& p, const CandSink& sink, Device& dev,

@@ -25,16 +25,12 @@
 
 #include "directory_probe.hpp"
 #include "kernels.hpp"
+#include "wave_ops.hpp"
 
 namespace smh {
 namespace {
 
 constexpr uint32_t kShortOwners = 8;   // owner lists up to this length are walked by the lane that holds the run
-
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-  for (int off = 32; off; off >>= 1) { const uint64_t o = __shfl_xor(v, off); v = o > v ? o : v; }
-  return v;
-}
 
 __global__ __launch_bounds__(256) void k_match_owner_ids(const uint64_t* __restrict__ offsets, uint32_t n, uint64_t total,
                                                          uint32_t* __restrict__ ids) {

@@ -1,7 +1,7 @@
 // minhash.cpp -- host logic of KmerMinHash + the engine that feeds the HIP kernels.
 //
 // Division of labour (DESIGN.md "fold"):
-//   device : k-mer walk, canonicalisation, murmur64, threshold filter (sketch_kernels.hip);
+//   device : k-mer walk, canonicalisation, murmur64, threshold filter (sketch_{dna,protein,amino}_kernels.hip, sketch_kernels.hip);
 //            radix sort, distinct + run boundaries + first position, bottom-n cut (sort.hip);
 //            every sketch comparison (compare_kernels.hip)
 //   host   : applying the resulting delta (<= num entries in num mode, the distinct retained

@@ -21,6 +21,7 @@
 
 #include "compare_pair.hpp"
 #include "sbt.hpp"
+#include "wave_ops.hpp"
 
 namespace smh {
 namespace {
@@ -41,11 +42,6 @@ __global__ __launch_bounds__(256) void k_sbt_bins(const uint64_t* __restrict__ h
     const uint64_t h = hashes[i];
     for (uint32_t t = 0; t < T; t++) bins[i * T + t] = fastmod(h, magic[t], sizes[t]);
   }
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 template <bool InLds>

@@ -17,6 +17,7 @@
 // Every kernel walks its items in a gridDim-stride loop (grid_for).  Every store to the text is checked against its length.
 #include "kernels.hpp"
 #include "sigtext_core.hpp"
+#include "wave_ops.hpp"
 
 namespace smh {
 
@@ -38,10 +39,6 @@ __device__ __forceinline__ uint32_t digits_any(uint32_t v) { return digits_u32(v
 __device__ __forceinline__ uint32_t format_any(uint64_t v, uint8_t* out) { return format_u64(v, out); }
 __device__ __forceinline__ uint32_t format_any(uint32_t v, uint8_t* out) { return format_u32(v, out); }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-  for (uint32_t d = 32; d; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d, 64);
-  return x;
-}
 __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x, uint32_t lane) {
 #pragma unroll
   for (uint32_t d = 1; d < 64; d <<= 1) {

@@ -1,4 +1,4 @@
-"""The sketch kernels' filter on the open digest, restated in Python integers (sketch_kernels.hip: w2_fmix_pre,
+"""The sketch kernels' filter on the open digest, restated in Python integers (murmur_device.hpp: w2_fmix_pre,
 open_hi_sum1<true>, open_thr<true>, open_full).  murmur64 of a string is h = fmix(h1) + fmix(h2); the kernels stop each
 fmix in front of its last multiply, ka = pre(h1), kb = pre(h2), and test E = hi32((ka + kb) * C) + 1 against
 open_thr(thr) before they form a = ka * C, b = kb * C and h = (a ^ a >> 33) + (b ^ b >> 33).

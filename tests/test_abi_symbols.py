@@ -36,6 +36,21 @@ def test_library_exports_every_declared_symbol(pkg):
     assert {"smh_set_grid_cap", "smh_grid_cap", "smh_set_pool_fill", "smh_pool_fill"} <= exported   # the test knobs
 
 
+def test_makefile_names_every_source():
+    # a source file the Makefile does not name is not in the library; a name without a file does not build
+    csrc = os.path.join(ROOT, "sourmash-rust_amd", "csrc")
+    text = open(os.path.join(csrc, "Makefile")).read()
+    listed = []
+    for var in ("SRCS_HIP", "SRCS_CPP"):
+        m = re.search(r"^%s\s*:=\s*(.*)$" % var, text, flags=re.M)
+        assert m, var
+        listed += m.group(1).split()
+    assert len(listed) == len(set(listed)), sorted(n for n in set(listed) if listed.count(n) > 1)
+    present = {f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp"))}
+    assert present - set(listed) == set(), "not in the Makefile"
+    assert set(listed) - present == set(), "named in the Makefile, no such file"
+
+
 def test_loads_and_scalar_calls_work_without_gpu(pkg):
     L = pkg.lib()
     mh = pkg.KmerMinHash(3, 21, False, 42, 0, True)

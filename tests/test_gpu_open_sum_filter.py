@@ -1,4 +1,4 @@
-"""The sketch kernels' filter on the sum of the two open mixes (sketch_kernels.hip: open_hi_sum1<true> against
+"""The sketch kernels' filter on the sum of the two open mixes (murmur_device.hpp: open_hi_sum1<true> against
 open_thr<true>; k_dna_rolling and k_protein_fused), on the GPU, with thresholds that sit ON hashes of the input.
 
 The filter's value E is the digest's high dword plus 0, 1 or 2 (tests/test_open_sum_identity.py).  A window of class
